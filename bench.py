@@ -20,7 +20,12 @@ phase brackets the launch/copy loop INCLUDING the device->host copies, interface
           the gathered matrix and its slice of the host matrix, and rank 0 checks the assembled host matrix against the
           reference's per-column digests (tests/golden/digest_cfg2.npz).
 
-Printed JSON (rank 0): metric/value per the driver contract, plus
+A plain run sets up, warms up, times the --steps steps, writes the last step's result when --dump-outputs DIR is given
+(DIR/scores.npy, DIR/scores_index.npy, DIR/scores_column_sums.npy: see dump_outputs) and prints the JSON line: metric,
+value, unit, higher_is_better, dtype, ms_per_step, gcups and the workload.  Everything else below is measured and
+checked only with --full (the --no-* switches trim that run):
+
+Printed JSON (rank 0): metric/value per the driver contract, plus, with --full,
   device_resident -- the same pass with the result left in HBM (kernels only; >= value)
   host_boundary   -- sa_hip_align cold call (encode + upload + loop) and the `seqalign` CLI FASTA->HDF5 with -B
   roofline        -- dominant kernel vs the HBM roof, live HIP-event timing on the launch stream
@@ -30,6 +35,7 @@ Printed JSON (rank 0): metric/value per the driver contract, plus
   parity          -- the CPU scores of that leg compared, untimed, with the same prefix of the host-delivered matrix
   gcups, valu     -- the bound that actually constrains this integer DP
   extra.configs   -- cfg3 (Gotoh, full size) and the cfg4 shape (SW nuc44, one GPU's worth) measured the same way
+  N > 1 also: the re-scored windows and host matrix checked on every rank, rank 0's reference-digest check
 """
 from __future__ import annotations
 
@@ -70,6 +76,11 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--n", "--nseq", dest="n", type=int, default=None, help="override sequence count (parity/debug runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: device-resident pass, roofline, host boundary, "
+                         "CPU baseline and parity, extra configs (N > 1: per-rank verification, digests, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result matrix (a fixed sample of it) to DIR/*.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline duration of a bounded sample")
     ap.add_argument("--cpu-full-seconds", type=float, default=100.0,
                     help="run the CPU reference over the WHOLE workload (and compare every score) when that is projected to take at most this long")
@@ -401,6 +412,32 @@ def tool_end_to_end_leg(make_config) -> dict:
     return out
 
 
+DUMP_SAMPLE = 2_000_000  # scores written by --dump-outputs at most: with their indices 32 MB of float64
+DUMP_SEED = 20_240_601
+
+
+def dump_outputs(path: str, scores, num: int) -> None:
+    """--dump-outputs: the packed upper-triangular s32 score vector of the last timed step (what the caller of the timed
+    path receives), as float64 (exact for every s32).  scores.npy holds the elements at scores_index.npy: all of them
+    when that fits, else a fixed seeded uniform sample (sorted); scores_column_sums.npy sums every column j (the scores of
+    pairs (i, j), i < j, j >= 1) so that no element goes unchecked.  The same arguments give the same input and the same
+    indices on every run."""
+    import numpy as np
+    out = pathlib.Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    scores = np.asarray(scores)
+    total = scores.size
+    if total <= DUMP_SAMPLE:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+    np.save(out / "scores.npy", scores[idx].astype(np.float64))
+    np.save(out / "scores_index.npy", idx.astype(np.float64))
+    starts = np.arange(1, num, dtype=np.int64) * np.arange(0, num - 1, dtype=np.int64) // 2  # first element of column j = j(j-1)/2
+    sums = np.add.reduceat(scores, starts, dtype=np.int64) if num > 1 else np.zeros(0, np.int64)
+    np.save(out / "scores_column_sums.npy", sums.astype(np.float64))
+
+
 _json_fd = None
 
 
@@ -476,14 +513,18 @@ def main():
                 f"{cfg['method']} {cfg['matrix']} {cfg['gaps']}, all-vs-all packed triangular")
     if not use_dist:
         # ---- N = 1: the reference's phase = launch + device->host copy loop, page-locked destination ----
-        packed = torch.empty(pairs, dtype=torch.int32, device="cuda")
-        el_res, tm_res = time_resident_steps(ctx, packed, pairs, args.steps, args.warmup, torch)
+        # (the device-resident pass runs first, as its own warmed-up timing, only with --full or when it is the headline)
+        packed = None
+        if args.full or args.device_resident_only:
+            packed = torch.empty(pairs, dtype=torch.int32, device="cuda")
+            el_res, tm_res = time_resident_steps(ctx, packed, pairs, args.steps, args.warmup, torch)
         if args.device_resident_only:
             elapsed, tm, dest = el_res, tm_res, None
         else:
             dest = sa.PinnedMatrix(pairs)
             elapsed, tm = time_host_steps(ctx, dest, args.steps, args.warmup, torch)
-            assert np.array_equal(dest.array, packed.cpu().numpy()), "host-delivered result differs from device-resident result"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dest.array if dest is not None else packed.cpu().numpy(), store.num)
         sec = elapsed / args.steps
         out = {
             "metric": "pair-alignments/sec", "value": pairs / sec, "unit": "pair-alignments/s",
@@ -494,13 +535,23 @@ def main():
                                         "sa_ctx_align_host: launch + device->host copy loop into a page-locked packed host matrix "
                                         "(the reference's bench_align bracket, seqalign_cuda.c:182,292); inputs resident in HBM")},
             "gcups": cells / sec / 1e9,
+            "device": sa.device_name(local_rank),
+        }
+        if not args.full:
+            ctx.close()
+            if dest is not None:
+                dest.close()
+            emit(out)
+            return
+        if dest is not None:
+            assert np.array_equal(dest.array, packed.cpu().numpy()), "host-delivered result differs from device-resident result"
+        out.update({
             "device_resident": {"value": pairs * args.steps / el_res, "ms_per_step": el_res / args.steps * 1e3,
                                 "gcups": cells * args.steps / el_res / 1e9,
                                 "note": "same pass, result left in HBM (kernels only); round-1 headline definition"},
             "roofline": roofline_of(tm, store, args.steps, args.config, 1, args.n is None),
             "valu": valu_of(method, cells, sec),
-            "device": sa.device_name(local_rank),
-        }
+        })
         if not args.no_host_boundary:
             t1 = time.perf_counter()
             host = sa.hip_align(store, scoring, triangular=True)
@@ -631,42 +682,46 @@ def main():
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
 
-    # every rank re-scores a few random windows of the gathered vector with its own kernels (untimed) and compares; the
-    # host matrix -- filled by all ranks' direct stores during the last step -- must equal the gathered vector element
-    # for element: rank r checks slice r of it.  (The oracle-backed check of this schedule: tests/test_gpu_gather_step.py,
-    # the reference-digest check of placed shares and host matrix: tests/test_gpu_digests.py)
-    vrng = np.random.default_rng(1234 + rank)
-    okflag = 1
-    for _ in range(6):
-        w = int(min(pairs, 65536))
-        a0 = int(vrng.integers(0, pairs - w + 1))
-        chk = torch.empty(w, dtype=torch.int32, device="cuda")
-        ctx.align_range(a0, w, chk.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        if not torch.equal(chk, step.packed[a0:a0 + w]):
-            okflag = 0
-    fence()
-    if tiled:
-        per = (pairs + world - 1) // world
-        lo, hi = min(pairs, rank * per), min(pairs, (rank + 1) * per)
-        if not np.array_equal(host.array[lo:hi], step.packed[lo:hi].cpu().numpy()):
-            okflag = 0
-    else:
-        for lo, hi, ho in step.host_ranges():
-            if not torch.equal(step.host[ho:ho + hi - lo], step.packed[lo:hi].cpu()):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, host.array if tiled else step.packed.cpu().numpy(), store.num)
+
+    gather_ok = digest_ok = None
+    if args.full:
+        # every rank re-scores a few random windows of the gathered vector with its own kernels (untimed) and compares; the
+        # host matrix -- filled by all ranks' direct stores during the last step -- must equal the gathered vector element
+        # for element: rank r checks slice r of it.  (The oracle-backed check of this schedule: tests/test_gpu_gather_step.py,
+        # the reference-digest check of placed shares and host matrix: tests/test_gpu_digests.py)
+        vrng = np.random.default_rng(1234 + rank)
+        okflag = 1
+        for _ in range(6):
+            w = int(min(pairs, 65536))
+            a0 = int(vrng.integers(0, pairs - w + 1))
+            chk = torch.empty(w, dtype=torch.int32, device="cuda")
+            ctx.align_range(a0, w, chk.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            if not torch.equal(chk, step.packed[a0:a0 + w]):
                 okflag = 0
-    t = torch.tensor([okflag], dtype=torch.int32, device=rdev)
-    dist.all_reduce(t, op=dist.ReduceOp.MIN)
-    gather_ok = bool(t.item())
-    # rank 0: the assembled host matrix against the reference's per-column digests of this workload, when the build
-    # container committed them (tests/golden/digest_<config>.npz) -- every pair, bit for bit, no sampling
-    digest_ok = None
-    dpath = ROOT / "tests" / "golden" / f"digest_{args.config}.npz"
-    if tiled and rank == 0 and args.n is None and dpath.exists():
-        from tests.digest_util import column_digests
-        z = np.load(dpath)
-        got = column_digests(host.array, store.num)
-        digest_ok = all(bool(np.array_equal(got[k], z[k])) for k in ("sum", "xor", "crc32"))
+        fence()
+        if tiled:
+            per = (pairs + world - 1) // world
+            lo, hi = min(pairs, rank * per), min(pairs, (rank + 1) * per)
+            if not np.array_equal(host.array[lo:hi], step.packed[lo:hi].cpu().numpy()):
+                okflag = 0
+        else:
+            for lo, hi, ho in step.host_ranges():
+                if not torch.equal(step.host[ho:ho + hi - lo], step.packed[lo:hi].cpu()):
+                    okflag = 0
+        t = torch.tensor([okflag], dtype=torch.int32, device=rdev)
+        dist.all_reduce(t, op=dist.ReduceOp.MIN)
+        gather_ok = bool(t.item())
+        # rank 0: the assembled host matrix against the reference's per-column digests of this workload, when the build
+        # container committed them (tests/golden/digest_<config>.npz) -- every pair, bit for bit, no sampling
+        dpath = ROOT / "tests" / "golden" / f"digest_{args.config}.npz"
+        if tiled and rank == 0 and args.n is None and dpath.exists():
+            from tests.digest_util import column_digests
+            z = np.load(dpath)
+            got = column_digests(host.array, store.num)
+            digest_ok = all(bool(np.array_equal(got[k], z[k])) for k in ("sum", "xor", "crc32"))
 
     # rank 0 alone times the reference's CPU path on a bounded sample of the workload (all host cores) and compares its
     # scores with the same prefix of the host matrix the ranks filled; the other ranks sleep on a flag file meanwhile
@@ -674,7 +729,7 @@ def main():
     flag = cpu_flag
     if rank == 0:
         try:
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 result = host.array if tiled else step.packed.cpu().numpy()
                 base, parity = cpu_baseline(seqs, cfg, args.cpu_seconds, 0.0, result)
                 if parity is not None:
@@ -698,16 +753,15 @@ def main():
                                       f"({'int16 exchange, widened to s32 on device' if use16 else 's32'}), "
                                       f"{nchunks} overlapped super-chunks, " + ("every rank's kernels store its scores straight into the one page-locked host matrix (shared mapping)" if tiled else f"every rank copies its 1/{world} share to page-locked host memory"),
                        "timed_region": f"kernels (with host delivery) + all-gathers + widen-and-place ({'TiledGatherStep' if tiled else 'GatherStep'}); inputs resident in HBM",
-                       **({"super_chunk_trial_ms": tuned} if tuned else {}),
-                       "gathered_and_host_result_verified_on_every_rank": gather_ok,
-                       "host_matrix_equals_reference_digests": digest_ok},
+                       **({"super_chunk_trial_ms": tuned} if tuned else {})},
             "gcups": cells / sec / 1e9,
-            "roofline": roofline_of(tm, store, args.steps, args.config, world, args.n is None),
-            "valu": valu_of(method, my_cells, sec),
             "device": sa.device_name(local_rank),
-            "cpu_baseline": base,
-            "parity": parity,
         }
+        if args.full:
+            out["config"].update({"gathered_and_host_result_verified_on_every_rank": gather_ok,
+                                  "host_matrix_equals_reference_digests": digest_ok})
+            out.update({"roofline": roofline_of(tm, store, args.steps, args.config, world, args.n is None),
+                        "valu": valu_of(method, my_cells, sec), "cpu_baseline": base, "parity": parity})
         emit(out)
     ctx.close()
     dist.barrier()

@@ -89,7 +89,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(world):
                HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--nseq", "3000",
-           "--cpu-seconds", "2"]
+           "--cpu-seconds", "2", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])

@@ -9,6 +9,6 @@ timeout -k 10 600 python -m pytest tests/test_gpu_pk.py tests/test_gpu_parity.py
 for cfg in cfg2 cfg3; do
 for v in 1 0; do
   if [ $v = 1 ]; then export SA_HIP_NO_SORT=1; else unset SA_HIP_NO_SORT; fi
-  timeout -k 10 300 python3 bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $O/bench_${cfg}_nosort$v.json 2> $O/bench_${cfg}_nosort$v.err || { tail -5 $O/bench_${cfg}_nosort$v.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $O/bench_${cfg}_nosort$v.json 2> $O/bench_${cfg}_nosort$v.err || { tail -5 $O/bench_${cfg}_nosort$v.err; exit 1; }
   python3 tools/show_bench.py $O/bench_${cfg}_nosort$v.json | head -12
 done; done

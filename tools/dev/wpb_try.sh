@@ -7,7 +7,7 @@ for a in "nw 3000 80 120" "ga 3000 80 120" "sw 3000 120 180 4 dna"; do
 done
 for cfg in "cfg2" "cfg3" "cfg4 --n 12000"; do
   t=$(echo $cfg | cut -d" " -f1)
-  timeout -k 10 300 python3 bench.py --config $cfg --steps 8 --warmup 2 --no-cpu-baseline --no-extra --no-host-boundary > $O/bench_$t.json 2> $O/bench_$t.err || { tail -5 $O/bench_$t.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --config $cfg --steps 8 --warmup 2 --no-cpu-baseline --no-extra --no-host-boundary > $O/bench_$t.json 2> $O/bench_$t.err || { tail -5 $O/bench_$t.err; exit 1; }
   python3 - $O/bench_$t.json <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -10,4 +10,4 @@ step() { local name=$1 t=$2; shift 2
 	return 0; }
 step pytest 1000 python -m pytest tests -m gpu -q; tail -4 $O/pytest.txt
 step fuzz 400 python3 tools/gpu_fuzz.py 240 2024; tail -3 $O/fuzz.txt
-step bench 500 python3 bench.py; python3 tools/show_bench.py $O/bench.txt
+step bench 500 python3 bench.py --full; python3 tools/show_bench.py $O/bench.txt

@@ -116,6 +116,19 @@ def main():
                         params=np.array(json.dumps(dict(threshold=0.9, threads=1))))
     print(f"filter_f0.9: {len(fs)} -> {len(kept)} kept")
 
+    oracle_vs_ref()
+
+
+def oracle_vs_ref():
+    """tests/test_oracle_vs_ref.py's calls to the reference library and its answers, for checkouts without oracle/_ref"""
+    from tests.test_oracle_vs_ref import live_reference, stored_calls
+    data = {}
+    for key, method, matrix, gaps, store, full in stored_calls(sa):
+        data.update({f"{key}/{k}": v for k, v in live_reference(method, matrix, gaps, store, full).items()})
+        data[f"{key}/gaps"] = np.array(json.dumps(gaps))
+    np.savez_compressed(OUT / "oracle_vs_ref.npz", **data)
+    print(f"oracle_vs_ref: {len(data)} arrays")
+
 
 if __name__ == "__main__":
     main()
