@@ -144,10 +144,6 @@ SaPlanInputs sa_plan_inputs(const sa_ctx *ctx)
 	in.persistent_wgs = ctx->persistent_wgs;
 	in.env_chunk = ctx->env.chunk;
 	in.no_sort = ctx->env.no_sort;
-	in.one_tile_size = ctx->env.one_tile_size;
-	in.small_below = ctx->env.small_below;
-	in.small_div = ctx->env.small_div;
-	in.small_frac = ctx->env.small_frac;
 	return in;
 }
 
@@ -313,14 +309,6 @@ extern "C" void sa_ctx_destroy(sa_ctx *ctx)
 		if (ev)
 			(void)hipEventDestroy(ev);
 	(void)hipFree(ctx->d_long_scratch);
-	for (int k = 0; k < sa_ctx::NSIDE; k++) {
-		if (ctx->side[k])
-			(void)hipStreamDestroy(ctx->side[k]);
-		if (ctx->join_ev[k])
-			(void)hipEventDestroy(ctx->join_ev[k]);
-	}
-	if (ctx->fork_ev)
-		(void)hipEventDestroy(ctx->fork_ev);
 	delete ctx;
 }
 

@@ -56,11 +56,6 @@ struct sa_ctx {
 	int64_t long_stride = 0;           /* ints per workgroup                                          */
 	int long_wgs = 0;
 	int persistent_wgs = 0;         /* workgroups of a persistent systolic launch  */
-	/* a range with SEVERAL launches (more than one packed bundle, s32 classes beside packed ones) runs them concurrently
-	 * on side streams forked from / joined into the caller's stream; created on first use */
-	enum { NSIDE = 8 };
-	hipStream_t side[NSIDE] = {};
-	hipEvent_t fork_ev = nullptr, join_ev[NSIDE] = {};
 	/* systolic fast path: parameters and validity (see systolic_setup) */
 	bool sys_ok = false;
 	int32_t sys_pconst = 0, sys_q = 0;

@@ -20,15 +20,8 @@ SaEnv sa_env_read()
 	e.no_pk = flag("SA_HIP_NO_PK");
 	e.no_pk16 = flag("SA_HIP_NO_PK16");
 	e.no_sort = flag("SA_HIP_NO_SORT");
-	e.concurrent_classes = flag("SA_HIP_CONCURRENT_CLASSES");
-	e.one_tile_size = flag("SA_HIP_ONE_TILE_SIZE");
 	e.chunk = number("SA_HIP_CHUNK", 0, 1, 32);
-	e.pk_wgs = number("SA_HIP_PK_WGS", 0, 0, 1 << 20);
 	e.stagger = number("SA_HIP_STAGGER", 0, 0, 64);
-	e.rotate_prio = getenv("SA_HIP_ROTATE_PRIO") ? (atoi(getenv("SA_HIP_ROTATE_PRIO")) != 0) : -1;
-	e.small_below = number("SA_HIP_SMALL_BELOW", 16, 0, 1 << 20);
-	e.small_div = number("SA_HIP_SMALL_DIV", 4, 2, 64);
-	e.small_frac = number("SA_HIP_SMALL_FRAC", 5, 2, 1 << 20);
 	e.no_pin = flag("SA_HIP_NO_PIN");
 	e.no_direct = flag("SA_HIP_NO_DIRECT");
 	e.no_shells = flag("SA_HIP_NO_SHELLS");

@@ -13,16 +13,8 @@ struct SaEnv {
 	bool no_pk16 = false;       /* SA_HIP_NO_PK16       : no 16-lane packed kernels                                 */
 	bool no_sort = false;       /* SA_HIP_NO_SORT       : row streams in store order (no arranged copies)           */
 	/* launch structure */
-	bool concurrent_classes = false; /* SA_HIP_CONCURRENT_CLASSES : several launches of a range side by side on side streams
-	                                  * (round 3's default; one after the other measured 4-8 % faster)        */
-	bool one_tile_size = false;  /* SA_HIP_ONE_TILE_SIZE  : no small tiles at the end of a short launch             */
 	int chunk = 0;               /* SA_HIP_CHUNK=n        : fixed row-stream length (1..32)                         */
-	int pk_wgs = 0;              /* SA_HIP_PK_WGS=n       : persistent workgroups of a packed launch                */
 	int stagger = 0;             /* SA_HIP_STAGGER=n      : start delay per wave slot (sleep periods)               */
-	int rotate_prio = -1;        /* SA_HIP_ROTATE_PRIO=0/1: rotating wave priority (-1: by method)                   */
-	int small_below = 16;        /* SA_HIP_SMALL_BELOW=n  : two tile sizes below n tiles per slot                   */
-	int small_div = 4;           /* SA_HIP_SMALL_DIV=n    : small tiles = big / n                                   */
-	int small_frac = 5;          /* SA_HIP_SMALL_FRAC=n   : 1/n of the range's pairs run in small tiles             */
 	/* host delivery */
 	bool no_pin = false;    /* SA_HIP_NO_PIN    : never page-lock the destination                                   */
 	bool no_direct = false; /* SA_HIP_NO_DIRECT : batched copies instead of direct stores into a locked packed matrix */

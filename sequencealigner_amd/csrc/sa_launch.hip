@@ -260,206 +260,176 @@ static void print_stamps(const sa_ctx *ctx, const char *name, bool is_pk, const 
 	fprintf(stderr, "\n");
 }
 
-/* share: world >= 1 runs the tiles of `rank` only and stores them densely (sa_ctx_align_share); 0: the whole range */
-static int align_range_launches(sa_ctx *ctx, int64_t start, int64_t count, int32_t *d_scores, hipStream_t s, bool out16,
-				int world, int rank, int32_t *host_out, size_t slot)
+/* One systolic launch of a range, as the builder of its kernel family (pk_launch, sys_launch) hands it to run_launch */
+struct Launch {
+	SaSysArgs a{};
+	bool is_pk = false; /* which launcher: sa_launch_systolic_pk(g, klo, f16, lds) or sa_launch_systolic(cls) */
+	int cls = -1, g = 0, klo = 0;
+	bool f16 = false;
+	unsigned lds = 0;
+	int wgs = 0;                        /* grid */
+	int32_t ntiles = 0;                 /* tiles, pairs and cells of this rank (progress, timing) */
+	int64_t pairs = 0, cells = 0;
+	size_t nstamp = 0, stamp_words = 0; /* SA_HIP_STAMPS: tiles that leave stamps, and the words they take */
+	char name[96] = "";                 /* template arguments as rocprofv3 prints them (+ the classes a bundle walks) */
+};
+
+static bool timed_begin(sa_ctx *ctx, hipStream_t s, hipEvent_t &e0, hipEvent_t &e1)
 {
-	const bool share = world >= 1;
-	const sa_ctx::Plan &pl = *ctx->plan;
-	const SaHostPlan &hp = pl.h;
-
-	auto timed_begin = [&](hipEvent_t &e0, hipEvent_t &e1) -> bool {
-		if (!ctx->timing)
-			return true;
-		SA_HIP_CHECK(hipEventCreate(&e0), return false);
-		SA_HIP_CHECK(hipEventCreate(&e1), return false);
-		SA_HIP_CHECK(hipEventRecord(e0, s), return false);
+	if (!ctx->timing)
 		return true;
-	};
-	auto timed_end = [&](const std::string &name, hipEvent_t e0, hipEvent_t e1, int64_t pairs, int64_t cells) -> bool {
-		if (!ctx->timing)
-			return true;
-		SA_HIP_CHECK(hipEventRecord(e1, s), return false);
-		ctx->events.push_back(sa_ctx::Timed{ name, e0, e1, pairs, cells });
+	SA_HIP_CHECK(hipEventCreate(&e0), return false);
+	SA_HIP_CHECK(hipEventCreate(&e1), return false);
+	SA_HIP_CHECK(hipEventRecord(e0, s), return false);
+	return true;
+}
+
+static bool timed_end(sa_ctx *ctx, hipStream_t s, const std::string &name, hipEvent_t e0, hipEvent_t e1, int64_t pairs, int64_t cells)
+{
+	if (!ctx->timing)
 		return true;
-	};
+	SA_HIP_CHECK(hipEventRecord(e1, s), return false);
+	ctx->events.push_back(sa_ctx::Timed{ name, e0, e1, pairs, cells });
+	return true;
+}
 
-	/* Systolic streaming kernels.  Packed classes: one persistent launch per BUNDLE (normally one for the whole range).
-	 * s32 classes: one persistent launch per class.  Several launches of a range run ONE AFTER THE OTHER on the caller's
-	 * stream, the bundle of the largest K first: every one of them fills the chip by itself, and side by side (round 3: side
-	 * streams forked from / joined into the caller's) their workgroups -- different LDS sizes, different code -- crowd each
-	 * other out of the CUs: cfg 4's two bundles 49.6 -> 46.1 ms, cfg 5's 30.8 -> 29.7 ms, three bundles of a mixed-length
-	 * store 12.35 -> 11.54 ms (profiles/r04_bundles_side_by_side_vs_serial.txt).  SA_HIP_CONCURRENT_CLASSES=1: side by side. */
-	const int rk = share ? rank : 0;
-	struct Item {
-		int bundle, cls; /* index into the plan's bundles, or into its classes (s32 classes) */
-	};
-	std::vector<Item> items;
-	for (size_t bi = 0; bi < hp.bundles.size(); bi++)
-		if (hp.bundles[bi].nlocal[(size_t)rk] > 0)
-			items.push_back({ (int)bi, -1 });
-	for (size_t ci = 0; ci < hp.classes.size(); ci++) {
-		const auto &cl = hp.classes[ci];
-		if (cl.cls >= SA_PK_CLASS0)
-			continue;
-		if (share && cl.rank_first[(size_t)rank + 1] == cl.rank_first[(size_t)rank])
-			continue;
-		items.push_back({ -1, (int)ci });
-	}
-	const bool fan_out = items.size() > 1 && ctx->env.concurrent_classes;
-	unsigned *const counters = ctx->d_counters + slot * sa_ctx::COUNTERS_PER_SLOT;
-	if (fan_out) {
-		if (!ctx->fork_ev) {
-			SA_HIP_CHECK(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming), return 1);
-		}
-		for (int k = 0; k < sa_ctx::NSIDE && k < (int)items.size(); k++)
-			if (!ctx->side[k]) {
-				SA_HIP_CHECK(hipStreamCreateWithFlags(&ctx->side[k], hipStreamNonBlocking), return 1);
-				SA_HIP_CHECK(hipEventCreateWithFlags(&ctx->join_ev[k], hipEventDisableTiming), return 1);
-			}
-		SA_HIP_CHECK(hipEventRecord(ctx->fork_ev, s), return 1);
-	}
-	hipStream_t caller = s;
-	int launch_no = 0;
-	ctx->prog_items.clear();
-	for (const Item &it : items) {
-		const int side_k = launch_no++ % sa_ctx::NSIDE;
-		if (fan_out) {
-			s = ctx->side[side_k];
-			SA_HIP_CHECK(hipStreamWaitEvent(s, ctx->fork_ev, 0), return 1);
-		}
-		const bool is_pk = it.bundle >= 0;
-		const SaHostBundle *pb = is_pk ? &hp.bundles[(size_t)it.bundle] : nullptr;
-		const SaHostClass *clp = is_pk ? nullptr : &hp.classes[(size_t)it.cls];
-		const int cls = is_pk ? -1 : clp->cls;
-		const bool is_long = cls == SA_SYS_CLASS_LONG;
-		SaSysArgs a{};
-		a.codes = ctx->d_codes;
-		a.off = ctx->d_off;
-		a.sub8 = ctx->d_sub8;
-		a.num = ctx->num;
-		a.start = start;
-		a.end = start + count;
-		a.out = d_scores;
-		a.out16 = out16 ? 1 : 0;
-		a.gap_g = ctx->sc.gap_pen;
-		a.gap_o = ctx->sc.gap_opn;
-		a.gap_e = ctx->sc.gap_ext;
-		a.host_out = host_out;
-		int32_t ntiles_here;
-		int64_t pairs_here, cells_here;
-		char name[96];
-		if (is_pk) {
-			const auto &db = pl.db[(size_t)it.bundle];
-			a.pconst = ctx->pk_pconst;
-			a.q = ctx->sc.method == SA_METHOD_SW ? 0 : ctx->pk_q;
-			a.out_nt = ctx->out_is_host && !share ? 1 : 0;
-			a.pk_f16 = pb->f16;
-			a.chunk = hp.chunk_pk; /* (the kernel takes chunk and arranged copies of every tile from its class block) */
-			a.stagger = ctx->env.stagger;
-			/* (measured: Gotoh's share of cfg 3 at 8 ranks 5.08 -> 5.01 ms, at 4 ranks 97.0 -> 98.0 % of ideal; NW needs all four
-			 * waves to fill a SIMD, nobody starves, and the rotation costs it 1 %) */
-			a.rotate_prio = ctx->env.rotate_prio >= 0 ? ctx->env.rotate_prio : ctx->sc.method != SA_METHOD_NW;
-			a.pkc = db.d_args;
-			a.ulist = db.d_ulist + pb->ufirst[(size_t)rk];
-			a.npkc = (int32_t)pb->cls.size();
-			a.nlocal = ntiles_here = pb->nlocal[(size_t)rk];
-			pairs_here = pb->pairs[(size_t)rk];
-			cells_here = pb->cells[(size_t)rk];
-			a.counter = counters + 2 * (SA_PK_CLASS0 + it.bundle);
-			int klo_seen = pb->kmax;
-			for (int ci : pb->cls)
-				klo_seen = std::min(klo_seen, sa_pk_decode(hp.classes[(size_t)ci].cls).k);
-			/* template arguments as rocprofv3 prints them, then the classes this launch walks */
-			snprintf(name, sizeof(name), "sa_k_systolic_pk_bundle<%s,%d,%d,%s>[K%d-%d]", METHOD_TAG[ctx->sc.method], pb->g, pb->klo,
-				 pb->f16 ? "true" : "false", klo_seen, pb->kmax);
-		} else {
-			const auto &cl = *clp;
-			const auto &dc = pl.dc[(size_t)it.cls];
-			const int64_t W = is_long ? ((int64_t)ctx->max_len + SA_SYS_LONG_W - 1) / SA_SYS_LONG_W * SA_SYS_LONG_W
-						  : SA_SYS_CLASSES[cls].G * SA_SYS_CLASSES[cls].K;
-			a.jlist = dc.d_jlist;
-			a.tprefix = dc.d_tprefix;
-			a.npart = cl.npart;
-			a.ncols = cl.ncols;
-			a.pconst = ctx->sys_pconst;
-			a.q = ctx->sys_q;
-			a.delta = (int32_t)(ctx->sys_gain * W + ctx->sys_slack);
-			a.counter = counters + 2 * cls;
-			a.chunk = is_long ? std::min(hp.chunk, 16) : hp.chunk;
-			ntiles_here = cl.ntiles;
-			pairs_here = cl.pairs;
-			cells_here = cl.cells;
-			if (share) {
-				a.tlist = dc.d_tlist + cl.rank_first[(size_t)rank];
-				a.nlocal = ntiles_here = cl.rank_first[(size_t)rank + 1] - cl.rank_first[(size_t)rank];
-				a.dense_off = dc.d_doff;
-				pairs_here = cl.rank_pairs[(size_t)rank];
-				cells_here = cl.rank_cells[(size_t)rank];
-			}
-			if (is_long) {
-				/* scratch: two lines (V and X) of a wave's longest possible row stream, for every wave of as many
-				 * workgroups as fit a 4 GiB budget */
-				if (!ctx->d_long_scratch) {
-					ctx->long_stride = 2 * (16 * ((int64_t)ctx->max_len + 1) + 64);
-					const int64_t budget_ints = ((int64_t)4 << 30) / 4;
-					const int64_t wpb = SA_SYS_WPB(64, true); /* one pair of lines per wave */
-					ctx->long_wgs = (int)std::max<int64_t>(16, std::min<int64_t>(ctx->persistent_wgs / 4, budget_ints / (ctx->long_stride * wpb)));
-					SA_HIP_CHECK(hipMalloc(&ctx->d_long_scratch, sizeof(int32_t) * (size_t)(ctx->long_stride * ctx->long_wgs * wpb)), return 1);
-				}
-				a.long_scratch = ctx->d_long_scratch;
-				a.long_stride = ctx->long_stride;
-				snprintf(name, sizeof(name), "sa_k_systolic<%s,G64,K16,strips>", METHOD_TAG[ctx->sc.method]);
-			} else {
-				snprintf(name, sizeof(name), "sa_k_systolic<%s,G%d,K%d>", METHOD_TAG[ctx->sc.method],
-					 SA_SYS_CLASSES[cls].G, SA_SYS_CLASSES[cls].K);
-			}
-		}
-		/* diagnostics: SA_HIP_STAMPS=1 makes every launch synchronous and prints the main-loop
-		 * cycles per step and the shader clock the chip held (never enabled in timed runs) */
-		unsigned long long *d_stamps = nullptr;
-		const size_t nstamp = is_pk ? (size_t)ntiles_here : (size_t)clp->ntiles; /* (packed bundle: 7 words per tile) */
-		const size_t stamp_words = is_pk ? 7 * nstamp : 3 * nstamp;
-		if (ctx->env.stamps) {
-			SA_HIP_CHECK(hipMalloc(&d_stamps, sizeof(unsigned long long) * std::max<size_t>(stamp_words, 1)), return 1);
-			SA_HIP_CHECK(hipMemset(d_stamps, 0, sizeof(unsigned long long) * std::max<size_t>(stamp_words, 1)), return 1);
-			a.stamps = d_stamps;
-		}
-		ctx->prog_items.push_back({ a.counter, ntiles_here });
-		hipEvent_t e0 = nullptr, e1 = nullptr;
-		if (!timed_begin(e0, e1))
-			return 1;
-		/* packed bundle: four workgroups per CU fill its LDS (4 x 39.9 KB at K = 13..16) and saturate the SIMDs (measured:
-		 * a grid of 4 per CU = 8 per CU; 3 per CU: NW -8 %, Gotoh -1 %).  leave_room: three per CU, so that kernels of other
-		 * streams -- an RCCL collective, the placement of the previous super-chunk -- find LDS and wave slots beside them
-		 * (beside four they wait for the launch to end: a 0.05 ms placement took 0.73 ms and held the next kernel up) */
-		const int pk_wgs = ctx->env.pk_wgs ? ctx->env.pk_wgs : ctx->persistent_wgs / 32 * (ctx->leave_room ? 3 : 4);
-		const int wgs = (int)std::min<int64_t>(is_pk ? pk_wgs : is_long ? ctx->long_wgs : ctx->persistent_wgs, ntiles_here);
-		if (is_pk) {
-			SA_HIP_CHECK(sa_launch_systolic_pk(ctx->sc.method, pb->g, pb->klo, pb->f16, a, wgs,
-							   (unsigned)sa_pk_lds_bytes(ctx->sc.method, pb->g, pb->kmax), s), return 1);
-		} else {
-			SA_HIP_CHECK(sa_launch_systolic(ctx->sc.method, cls, a, wgs, s), return 1);
-		}
-		if (d_stamps) {
-			std::vector<unsigned long long> h(stamp_words);
-			SA_HIP_CHECK(hipStreamSynchronize(s), return 1);
-			SA_HIP_CHECK(hipMemcpy(h.data(), d_stamps, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost), return 1);
-			(void)hipFree(d_stamps);
-			print_stamps(ctx, name, is_pk, h, nstamp);
-		}
-		if (!timed_end(name, e0, e1, pairs_here, cells_here))
-			return 1;
-		if (fan_out) {
-			SA_HIP_CHECK(hipEventRecord(ctx->join_ev[side_k], s), return 1);
-			SA_HIP_CHECK(hipStreamWaitEvent(caller, ctx->join_ev[side_k], 0), return 1);
-		}
-	}
-	s = caller;
-	SA_HIP_CHECK(hipEventRecord(ctx->slot_done[slot], s), return 1);
+/* One persistent launch for a packed BUNDLE (normally one for the whole range): its tiles of rank `rk` */
+static Launch pk_launch(const sa_ctx *ctx, const sa_ctx::Plan &pl, size_t bi, int rk, bool share, unsigned *counters, const SaSysArgs &common)
+{
+	const SaHostBundle &b = pl.h.bundles[bi];
+	Launch L;
+	L.is_pk = true;
+	L.g = b.g;
+	L.klo = b.klo;
+	L.f16 = b.f16;
+	L.lds = (unsigned)sa_pk_lds_bytes(ctx->sc.method, b.g, b.kmax);
+	SaSysArgs &a = L.a = common;
+	a.pconst = ctx->pk_pconst;
+	a.q = ctx->sc.method == SA_METHOD_SW ? 0 : ctx->pk_q;
+	a.out_nt = ctx->out_is_host && !share ? 1 : 0;
+	a.pk_f16 = b.f16;
+	a.chunk = pl.h.chunk_pk; /* (the kernel takes chunk and arranged copies of every tile from its class block) */
+	a.stagger = ctx->env.stagger;
+	/* (measured: Gotoh's share of cfg 3 at 8 ranks 5.08 -> 5.01 ms, at 4 ranks 97.0 -> 98.0 % of ideal; NW needs all four
+	 * waves to fill a SIMD, nobody starves, and the rotation costs it 1 %) */
+	a.rotate_prio = ctx->sc.method != SA_METHOD_NW;
+	a.pkc = pl.db[bi].d_args;
+	a.ulist = pl.db[bi].d_ulist + b.ufirst[(size_t)rk];
+	a.npkc = (int32_t)b.cls.size();
+	a.nlocal = L.ntiles = b.nlocal[(size_t)rk];
+	a.counter = counters + 2 * (SA_PK_CLASS0 + (int)bi);
+	L.pairs = b.pairs[(size_t)rk];
+	L.cells = b.cells[(size_t)rk];
+	L.nstamp = (size_t)L.ntiles;
+	L.stamp_words = 7 * L.nstamp;
+	/* four workgroups per CU fill its LDS (4 x 39.9 KB at K = 13..16) and saturate the SIMDs (measured: a grid of 4 per
+	 * CU = 8 per CU; 3 per CU: NW -8 %, Gotoh -1 %).  leave_room: three per CU, so that kernels of other streams -- an RCCL
+	 * collective, the placement of the previous super-chunk -- find LDS and wave slots beside them (beside four they wait
+	 * for the launch to end: a 0.05 ms placement took 0.73 ms and held the next kernel up) */
+	L.wgs = (int)std::min<int64_t>(ctx->persistent_wgs / 32 * (ctx->leave_room ? 3 : 4), L.ntiles);
+	int klo_seen = b.kmax;
+	for (int ci : b.cls)
+		klo_seen = std::min(klo_seen, sa_pk_decode(pl.h.classes[(size_t)ci].cls).k);
+	snprintf(L.name, sizeof(L.name), "sa_k_systolic_pk_bundle<%s,%d,%d,%s>[K%d-%d]", METHOD_TAG[ctx->sc.method], b.g, b.klo,
+		 b.f16 ? "true" : "false", klo_seen, b.kmax);
+	return L;
+}
 
-	/* everything the fast path does not cover: pair-per-wave kernels on contiguous packed runs */
-	/* (share: this rank's pieces of those runs, each at its offset of the dense share) */
+/* scratch of the strip-mined kernel, allocated when a range first needs it: two lines (V and X) of a wave's longest
+ * possible row stream, for every wave of as many workgroups as fit a 4 GiB budget */
+static bool long_scratch_ready(sa_ctx *ctx)
+{
+	if (ctx->d_long_scratch)
+		return true;
+	ctx->long_stride = 2 * (16 * ((int64_t)ctx->max_len + 1) + 64);
+	const int64_t budget_ints = ((int64_t)4 << 30) / 4;
+	const int64_t wpb = SA_SYS_WPB(64, true); /* one pair of lines per wave */
+	ctx->long_wgs = (int)std::max<int64_t>(16, std::min<int64_t>(ctx->persistent_wgs / 4, budget_ints / (ctx->long_stride * wpb)));
+	SA_HIP_CHECK(hipMalloc(&ctx->d_long_scratch, sizeof(int32_t) * (size_t)(ctx->long_stride * ctx->long_wgs * wpb)), return false);
+	return true;
+}
+
+/* One persistent launch for an s32 class, the strip-mined class among them; share: its tiles of `rank`, stored densely */
+static bool sys_launch(sa_ctx *ctx, const sa_ctx::Plan &pl, size_t ci, bool share, int rank, unsigned *counters, const SaSysArgs &common,
+		       Launch &L)
+{
+	const SaHostClass &cl = pl.h.classes[ci];
+	const auto &dc = pl.dc[ci];
+	const int cls = L.cls = cl.cls;
+	const bool is_long = cls == SA_SYS_CLASS_LONG;
+	const int64_t W = is_long ? ((int64_t)ctx->max_len + SA_SYS_LONG_W - 1) / SA_SYS_LONG_W * SA_SYS_LONG_W
+				  : SA_SYS_CLASSES[cls].G * SA_SYS_CLASSES[cls].K;
+	SaSysArgs &a = L.a = common;
+	a.jlist = dc.d_jlist;
+	a.tprefix = dc.d_tprefix;
+	a.npart = cl.npart;
+	a.ncols = cl.ncols;
+	a.pconst = ctx->sys_pconst;
+	a.q = ctx->sys_q;
+	a.delta = (int32_t)(ctx->sys_gain * W + ctx->sys_slack);
+	a.counter = counters + 2 * cls;
+	a.chunk = is_long ? std::min(pl.h.chunk, 16) : pl.h.chunk;
+	L.ntiles = cl.ntiles;
+	L.pairs = cl.pairs;
+	L.cells = cl.cells;
+	if (share) {
+		a.tlist = dc.d_tlist + cl.rank_first[(size_t)rank];
+		a.nlocal = L.ntiles = cl.rank_first[(size_t)rank + 1] - cl.rank_first[(size_t)rank];
+		a.dense_off = dc.d_doff;
+		L.pairs = cl.rank_pairs[(size_t)rank];
+		L.cells = cl.rank_cells[(size_t)rank];
+	}
+	L.nstamp = (size_t)cl.ntiles; /* (the class's tiles, not the rank's: a tile stamps at its index in the class) */
+	L.stamp_words = 3 * L.nstamp;
+	if (is_long) {
+		if (!long_scratch_ready(ctx))
+			return false;
+		a.long_scratch = ctx->d_long_scratch;
+		a.long_stride = ctx->long_stride;
+		snprintf(L.name, sizeof(L.name), "sa_k_systolic<%s,G64,K16,strips>", METHOD_TAG[ctx->sc.method]);
+	} else {
+		snprintf(L.name, sizeof(L.name), "sa_k_systolic<%s,G%d,K%d>", METHOD_TAG[ctx->sc.method], SA_SYS_CLASSES[cls].G,
+			 SA_SYS_CLASSES[cls].K);
+	}
+	L.wgs = (int)std::min<int64_t>(is_long ? ctx->long_wgs : ctx->persistent_wgs, L.ntiles);
+	return true;
+}
+
+/* what every systolic launch has in common: progress item, stamps, timing, the launch itself */
+static bool run_launch(sa_ctx *ctx, Launch &L, hipStream_t s)
+{
+	/* diagnostics: SA_HIP_STAMPS=1 makes every launch synchronous and prints the main-loop
+	 * cycles per step and the shader clock the chip held (never enabled in timed runs) */
+	unsigned long long *d_stamps = nullptr;
+	if (ctx->env.stamps) {
+		SA_HIP_CHECK(hipMalloc(&d_stamps, sizeof(unsigned long long) * std::max<size_t>(L.stamp_words, 1)), return false);
+		SA_HIP_CHECK(hipMemset(d_stamps, 0, sizeof(unsigned long long) * std::max<size_t>(L.stamp_words, 1)), return false);
+		L.a.stamps = d_stamps;
+	}
+	ctx->prog_items.push_back({ L.a.counter, L.ntiles });
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	if (!timed_begin(ctx, s, e0, e1))
+		return false;
+	if (L.is_pk) {
+		SA_HIP_CHECK(sa_launch_systolic_pk(ctx->sc.method, L.g, L.klo, L.f16, L.a, L.wgs, L.lds, s), return false);
+	} else {
+		SA_HIP_CHECK(sa_launch_systolic(ctx->sc.method, L.cls, L.a, L.wgs, s), return false);
+	}
+	if (d_stamps) {
+		std::vector<unsigned long long> h(L.stamp_words);
+		SA_HIP_CHECK(hipStreamSynchronize(s), return false);
+		SA_HIP_CHECK(hipMemcpy(h.data(), d_stamps, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost), return false);
+		(void)hipFree(d_stamps);
+		print_stamps(ctx, L.name, L.is_pk, h, L.nstamp);
+	}
+	return timed_end(ctx, s, L.name, e0, e1, L.pairs, L.cells);
+}
+
+/* everything the fast path does not cover: pair-per-wave kernels on contiguous packed runs
+ * (share: this rank's pieces of those runs, each at its offset of the dense share) */
+static bool generic_runs(sa_ctx *ctx, const SaHostPlan &hp, int64_t start, int32_t *d_scores, hipStream_t s, bool out16, bool share, int rank,
+			 int32_t *host_out)
+{
 	std::vector<std::pair<int64_t, int64_t>> runs = hp.generic;
 	std::vector<int64_t> run_out;
 	if (share) {
@@ -489,18 +459,68 @@ static int align_range_launches(sa_ctx *ctx, int64_t start, int64_t count, int32
 		a.scratch_stride = ctx->scratch_stride;
 		const int blocks = (int)std::min<int64_t>(ctx->generic_blocks, (run.second + 3) / 4);
 		hipEvent_t e0 = nullptr, e1 = nullptr;
-		if (!timed_begin(e0, e1))
-			return 1;
-		SA_HIP_CHECK(sa_launch_generic(ctx->sc.method, a, blocks, s), return 1);
+		if (!timed_begin(ctx, s, e0, e1))
+			return false;
+		SA_HIP_CHECK(sa_launch_generic(ctx->sc.method, a, blocks, s), return false);
 		int64_t run_cells = 0;
 		if (ctx->timing) {
 			SaPairPlan pp(ctx->meta.data(), ctx->num);
 			run_cells = pp.cells_before(run.first + run.second) - pp.cells_before(run.first);
 		}
-		if (!timed_end(sa_generic_kernel_name(ctx->sc.method), e0, e1, run.second, run_cells))
+		if (!timed_end(ctx, s, sa_generic_kernel_name(ctx->sc.method), e0, e1, run.second, run_cells))
+			return false;
+	}
+	return true;
+}
+
+/* share: world >= 1 runs the tiles of `rank` only and stores them densely (sa_ctx_align_share); 0: the whole range */
+static int align_range_launches(sa_ctx *ctx, int64_t start, int64_t count, int32_t *d_scores, hipStream_t s, bool out16,
+				int world, int rank, int32_t *host_out, size_t slot)
+{
+	const bool share = world >= 1;
+	const sa_ctx::Plan &pl = *ctx->plan;
+	const int rk = share ? rank : 0;
+	unsigned *const counters = ctx->d_counters + slot * sa_ctx::COUNTERS_PER_SLOT;
+	SaSysArgs common{};
+	common.codes = ctx->d_codes;
+	common.off = ctx->d_off;
+	common.sub8 = ctx->d_sub8;
+	common.num = ctx->num;
+	common.start = start;
+	common.end = start + count;
+	common.out = d_scores;
+	common.out16 = out16 ? 1 : 0;
+	common.gap_g = ctx->sc.gap_pen;
+	common.gap_o = ctx->sc.gap_opn;
+	common.gap_e = ctx->sc.gap_ext;
+	common.host_out = host_out;
+
+	/* Systolic streaming kernels: the packed bundles in plan order (the bundle of the largest K first), then the s32
+	 * classes.  Several launches of a range run ONE AFTER THE OTHER on the caller's stream: every one of them fills the chip
+	 * by itself, and side by side (round 3: side streams forked from / joined into the caller's) their workgroups --
+	 * different LDS sizes, different code -- crowd each other out of the CUs: cfg 4's two bundles 49.6 -> 46.1 ms, cfg 5's
+	 * 30.8 -> 29.7 ms, three bundles of a mixed-length store 12.35 -> 11.54 ms
+	 * (profiles/r04_bundles_side_by_side_vs_serial.txt). */
+	ctx->prog_items.clear();
+	for (size_t bi = 0; bi < pl.h.bundles.size(); bi++) {
+		if (pl.h.bundles[bi].nlocal[(size_t)rk] <= 0)
+			continue;
+		Launch L = pk_launch(ctx, pl, bi, rk, share, counters, common);
+		if (!run_launch(ctx, L, s))
 			return 1;
 	}
-	return 0;
+	for (size_t ci = 0; ci < pl.h.classes.size(); ci++) {
+		const SaHostClass &cl = pl.h.classes[ci];
+		if (cl.cls >= SA_PK_CLASS0)
+			continue;
+		if (share && cl.rank_first[(size_t)rank + 1] == cl.rank_first[(size_t)rank])
+			continue;
+		Launch L;
+		if (!sys_launch(ctx, pl, ci, share, rank, counters, common, L) || !run_launch(ctx, L, s))
+			return 1;
+	}
+	SA_HIP_CHECK(hipEventRecord(ctx->slot_done[slot], s), return 1); /* (the pair-per-wave kernels do not use the counters) */
+	return generic_runs(ctx, pl.h, start, d_scores, s, out16, share, rank, host_out) ? 0 : 1;
 }
 
 int sa_align_range_impl(sa_ctx *ctx, int64_t start, int64_t count, int32_t *d_scores, void *stream, bool out16, int world, int rank,

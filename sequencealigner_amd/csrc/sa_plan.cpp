@@ -190,25 +190,26 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 			cpk = in.env_chunk;
 		cpk = std::min(cpk, in.pk_chunk_cap);
 		plan.chunk_pk = cpk;
-		/* Two tile sizes for a launch that gives a workgroup slot fewer than `small_below` tiles (one rank's share of a
+		/* Two tile sizes for a launch that gives a workgroup slot fewer than TWO_SIZES_BELOW tiles (one rank's share of a
 		 * multi-GPU run; a super-chunk): when the tiles run out the slots finish their last ones over a whole tile's
 		 * duration, and only work in small units can fill that triangle.  So the bulk runs in tiles as large as leave
 		 * >= 2.5 per slot, and the lowest columns of the range -- a fifth of its pairs -- in tiles a quarter of that size,
 		 * which the launch order puts last (small tiles cost more per row, so not everywhere). */
+		constexpr int TWO_SIZES_BELOW = 16, SMALL_TILE_DIV = 4, SMALL_PAIRS_FRAC = 5;
 		const int64_t slots = (int64_t)in.persistent_wgs / 8;
-		if (!in.env_chunk && !in.one_tile_size && mine / ((int64_t)2 * SA_PK_WPB * 8 * cpk) < (int64_t)in.small_below * slots) {
+		if (!in.env_chunk && mine / ((int64_t)2 * SA_PK_WPB * 8 * cpk) < (int64_t)TWO_SIZES_BELOW * slots) {
 			int32_t big = SA_SYS_CHUNK;
 			while (big > 16 && 2 * mine / ((int64_t)2 * SA_PK_WPB * 8 * big) < 5 * slots)
 				big >>= 1;
 			big = std::min(std::max(big, cpk), in.pk_chunk_cap);
 			if (big >= 16) {
 				plan.chunk_pk = big;
-				plan.chunk_pk_small = std::max(4, big / std::max(2, in.small_div));
+				plan.chunk_pk_small = std::max(4, big / SMALL_TILE_DIV);
 				const int64_t jlo = sa_column_of(start), jhi = sa_column_of(end - 1) + 1;
 				int64_t lo = jlo, hi = jhi; /* smallest column with >= a fifth of the range's pairs below it */
 				while (lo < hi) {
 					const int64_t mid = (lo + hi) / 2;
-					if (mid * (mid - 1) / 2 - start >= count / std::max(2, in.small_frac))
+					if (mid * (mid - 1) / 2 - start >= count / SMALL_PAIRS_FRAC)
 						hi = mid;
 					else
 						lo = mid + 1;

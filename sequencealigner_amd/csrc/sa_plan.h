@@ -59,8 +59,7 @@ struct SaPlanInputs {
 	int persistent_wgs = 256 * 32; /* 32 x CUs */
 	/* development switches (sa_env.h) */
 	int env_chunk = 0;
-	bool no_sort = false, one_tile_size = false;
-	int small_below = 16, small_div = 4, small_frac = 5;
+	bool no_sort = false;
 };
 
 /* Which kernel families reproduce the reference exactly for a scoring and a store's length range, and their constants

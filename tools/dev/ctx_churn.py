@@ -5,7 +5,7 @@ import torch
 import sequencealigner_amd as sa
 from tests.synth import make_protein_set
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1500
-store = sa.SequenceStore.from_sequences(make_protein_set(300, 20, 230, 3))  # two bundles -> side streams are used
+store = sa.SequenceStore.from_sequences(make_protein_set(300, 20, 230, 3))  # two bundles -> two launches per range
 sc = sa.Scoring.from_names("nw", "blosum62", gap_pen=4)
 out = torch.empty(store.pairs, dtype=torch.int32, device="cuda")
 for k in range(n):
