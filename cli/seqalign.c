@@ -105,6 +105,8 @@ static void usage(const char *argv0)
 	       "  -l, --list-matrices      List available substitution matrices\n"
 	       "  -f, --filter FLOAT       Filter sequences with similarity above threshold [0.0-1.0]\n"
 	       "  -z, --compression N      Compression level for HDF5 datasets [0-9]\n"
+	       "                           0: none; 1-6: fast parse on the device (between zlib -1 and -4);\n"
+	       "                           7-9: smaller files (8-byte pair matches, between zlib -4 and -6)\n"
 	       "  -B, --benchmark          Enable timing of various steps\n"
 	       "  -T, --threads N          Number of host threads (0 = auto)\n"
 	       "  -C, --no-cuda            Not available: this build has no CPU alignment path\n"
@@ -428,9 +430,11 @@ int main(int argc, char **argv)
 						  * with -z the walk itself runs on all of them (sa_hip_tiles_begin: block b -> device b mod n) */
 						 : sa_hip_device_count() == 1);
 	if (device_deflate) {
-		/* the packed scores + one tile row: raw, or raw + worst-case slots and streams (1 + 2 x 2.02 x the row's raw bytes) */
+		/* the packed scores + one tile row: raw, or raw + worst-case slots and streams (1 + 2 x 2.02 x the row's raw bytes); the
+		 * pair parse (-z 7..9) keeps two more bytes per element: what its match finder leaves for the encoder */
 		const size_t row_raw = ((n + zchunk - 1) / zchunk) * zchunk * zchunk * sizeof(int32_t);
-		device_deflate = sa_hip_memory(sizeof(int32_t) * (size_t)npairs + (o.compression ? 6 : 1) * row_raw);
+		device_deflate = sa_hip_memory(sizeof(int32_t) * (size_t)npairs + (o.compression ? 6 : 1) * row_raw +
+					       (o.compression >= SA_HIP_Z_PAIR_LEVEL ? row_raw / 2 : 0));
 		stamp("device memory probed (runtime up)");
 	}
 	if (!o.no_write && !device_deflate) {

@@ -203,8 +203,12 @@ int sa_ctx_expand_full(sa_ctx *ctx, const int32_t *d_packed, int32_t *d_full, vo
  * the scores are: a job walks the tile rows of the full symmetric matrix (zero diagonal, zeros beyond N: exactly what
  * H5Dwrite hands the filter) over a DEVICE-resident matrix -- packed by pair index (d_packed) or full N x N (d_full,
  * used when d_packed is NULL) -- and returns every tile as a complete zlib stream (RFC 1950 / 1951) in page-locked host
- * memory, ready for H5Dwrite_chunk (filter mask 0); any inflate reads them.  The parse is fixed: the ratio
- * on score matrices sits between zlib -1 and -6, whatever level > 0 the dataset's property list names.  Level 0 returns the
+ * memory, ready for H5Dwrite_chunk (filter mask 0); any inflate reads them.  `level` chooses the parse:
+ * 1 .. 6 the fixed parse (every element by itself: its low byte, then a length-3 match onto one of its eight predecessors;
+ * the ratio on score matrices sits between zlib -1 and -4), SA_HIP_Z_PAIR_LEVEL .. 9 the pair parse (8-byte matches onto
+ * equal pairs of elements anywhere in the 32 KB of the tile before them, found by one more kernel; 5 to 7 % fewer bytes
+ * on NW scores, between zlib -4 and -6, at about twice the encoder time, for two more bytes of device memory per element of a line of tiles).  The same
+ * level on the same matrix gives the same bytes, run after run.  Level 0 returns the
  * tiles as they are (chunk_dim^2 int32 each), for a chunked dataset without filters: the same H5Dwrite_chunk loop then
  * replaces H5Dwrite's gather of every tile out of N-wide rows in the writing thread (hdf5.c:148-194).
  *   sa_zjob_create       buffers for one line of tiles; chunk_dim: a power of two in [64, 4096] (sa_host_hdf5_chunk_dim)
@@ -224,6 +228,7 @@ int sa_ctx_expand_full(sa_ctx *ctx, const int32_t *d_packed, int32_t *d_full, vo
  *   sa_zjob_align_seconds  device time of the alignment so far (sum over the finished column blocks: the bracket of
  *                        sa_hip_last_align_seconds).
  * NULL / non-zero + sa_last_error on failure. */
+#define SA_HIP_Z_PAIR_LEVEL 7 /* levels from here on: the pair parse */
 typedef struct sa_zjob sa_zjob;
 sa_zjob *sa_zjob_create(int device, const int32_t *d_packed, const int32_t *d_full, int32_t num, size_t chunk_dim, int level);
 size_t sa_zjob_tiles_per_row(const sa_zjob *job);

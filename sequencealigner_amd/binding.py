@@ -560,8 +560,8 @@ class Context:
 
 class DeflateJob:
     """Device-side DEFLATE of a device-resident result matrix (sa_zjob_*, the -z option): the tiles (HDF5 chunks) of
-    the full symmetric matrix as zlib streams (level > 0) or as they are (level 0).  d_packed_ptr: scores by packed pair
-    index; or d_full_ptr: N x N."""
+    the full symmetric matrix as zlib streams (level 1..6: the fixed parse, 7..9: the pair parse, smaller) or as they are
+    (level 0).  d_packed_ptr: scores by packed pair index; or d_full_ptr: N x N."""
 
     def __init__(self, num: int, chunk_dim: int, d_packed_ptr: int = 0, d_full_ptr: int = 0, device: int = 0, level: int = 6, _handle=None):
         self._lib = load_library()

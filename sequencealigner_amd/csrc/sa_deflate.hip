@@ -11,6 +11,13 @@
  *
  * A tile is cut into SEGMENTS of ZSEG elements (64 KB of its row-major bytes), each an independent dynamic-Huffman block
  * that ends byte-aligned; ZGROUP consecutive segments (1 MB) share one set of Huffman codes.  Per tile row:
+ *   sa_k_deflate_pairs    levels SA_Z_PAIR_LEVEL .. 9 only, one workgroup per segment: the match finder of the pair parse
+ *                         (sa_deflate_core.h) -- an LDS hash table keyed on (element, next element), pre-rolled with the
+ *                         32 KB of the tile before the segment, then the segment in sub-blocks that look up before they
+ *                         insert (atomic max on the position: the nearest candidate wins, run after run), the two claim
+ *                         rounds, and per element a u16: how far back the 8-byte match it starts lies, 0: none (an element
+ *                         after a start is the match's second half).  sa_k_deflate_hist_pairs then counts every segment both
+ *                         ways and keeps the pairs only where they make it smaller; sa_k_deflate_encode<true> codes them.
  *   sa_k_deflate_hist     one workgroup per segment: its elements straight from the packed triangle (lower part:
  *                         contiguous; upper part: the mirrored element; diagonal and the padding beyond N: 0) into LDS,
  *                         match choice, histograms (LDS atomics, then one global atomic per used symbol into the
@@ -38,6 +45,8 @@
 
 #include "sa_ctx.h"
 #include "sa_deflate_core.h"
+
+static_assert(SA_Z_PAIR_LEVEL == SA_HIP_Z_PAIR_LEVEL, "the public header names the level the pair parse starts at");
 
 namespace {
 
@@ -72,6 +81,7 @@ struct SaZArgs {
 	uint32_t *tile_adler;  /* [tile]                                                                            */
 	uint8_t *out;          /* the row's streams, compact (every tile starts on a 64-byte boundary)              */
 	uint32_t *raw;         /* [tile][chunk][chunk]: the row's tiles as they are (sa_k_tiles_raw)                 */
+	uint16_t *pairs;       /* [tile][chunk][chunk]: elements back to the 8-byte match that starts here, 0: none  */
 };
 
 __device__ __forceinline__ uint32_t z_fetch(const SaZArgs &A, int64_t i, int64_t j)
@@ -116,6 +126,15 @@ __device__ __forceinline__ const uint4 *z_segment(const SaZArgs &A, int seg, int
 	return reinterpret_cast<const uint4 *>(A.raw + (size_t)tile * tile_elems + e0);
 }
 
+/* what the match finder left for the four elements of quad q: st[1 + t] = elements back if element 4 q + t starts a pair
+ * match, st[0] the same for the element before the quad (which then is the match's first half) */
+__device__ __forceinline__ void z_load_pairs(const uint16_t *segp, uint32_t q, uint32_t (&st)[5])
+{
+	const uint2 c = reinterpret_cast<const uint2 *>(segp)[q];
+	st[0] = q ? segp[4u * q - 1u] : 0u; /* (a match never crosses a segment's start) */
+	st[1] = c.x & 0xffffu, st[2] = c.x >> 16, st[3] = c.y & 0xffffu, st[4] = c.y >> 16;
+}
+
 __device__ __forceinline__ void z_or_bits(uint32_t *stage, uint32_t pos, uint64_t bits, uint32_t n)
 {
 	if (!n)
@@ -131,6 +150,63 @@ __device__ __forceinline__ void z_or_bits(uint32_t *stage, uint32_t pos, uint64_
 		atomicOr(&stage[w + 1], x1);
 	if (x2)
 		atomicOr(&stage[w + 2], x2);
+}
+
+/* The match finder of the pair parse (sa_deflate_core.h; tests/host_c/deflate_pairs_test.cpp is this kernel, serially).
+ * LDS: 32 KB of table + 32 KB of candidates = 64 KB, two workgroups (eight waves) per CU.  The elements are read from the
+ * raw tile where they are -- the 96 KB a segment and its window span stay in the caches -- and nothing but the table's
+ * atomic max is shared between lanes inside a phase, so the result does not depend on the order they run in. */
+__global__ __launch_bounds__(ZT) void sa_k_deflate_pairs(SaZArgs A)
+{
+	__shared__ uint32_t table[SA_Z_PAIR_TABLE];
+	__shared__ uint16_t cand[ZSEG];
+	static_assert(SA_Z_PAIR_SUB == 4 * ZT, "a thread looks up one quad per sub-block");
+	static_assert(SA_Z_PAIR_WINDOW < 65536, "a candidate's distance fits 16 bits");
+	static_assert(sizeof(table) + sizeof(cand) <= 80 * 1024, "two workgroups per CU");
+	const int tid = threadIdx.x;
+	const int seg = blockIdx.x, tile = blockIdx.y;
+	uint32_t n;
+	(void)z_segment(A, seg, tile, &n);
+	const size_t tile_elems = (size_t)A.chunk * (size_t)A.chunk;
+	const uint32_t *const e = A.raw + (size_t)tile * tile_elems; /* the tile: positions are elements of it */
+	const uint32_t s0 = (uint32_t)seg * ZSEG, base = s0 >= (uint32_t)SA_Z_PAIR_WINDOW ? s0 - SA_Z_PAIR_WINDOW : 0u;
+	for (int s = tid; s < SA_Z_PAIR_TABLE; s += ZT)
+		table[s] = 0;
+	__syncthreads();
+	for (uint32_t p = base + (uint32_t)tid; p < s0; p += ZT) /* (p + 1 <= s0: inside the tile) */
+		atomicMax(&table[sa_z_pair_hash(e[p], e[p + 1u])], p - base + 1u);
+	__syncthreads();
+	for (uint32_t b0 = 0; b0 < n; b0 += SA_Z_PAIR_SUB) {
+		const uint32_t k0 = b0 + 4u * (uint32_t)tid;
+		uint32_t v[5] = {};
+		if (k0 < n) { /* (n is a multiple of four: the whole quad; element k has a pair if k + 1 < n) */
+			const uint4 c = reinterpret_cast<const uint4 *>(e + s0)[k0 / 4u];
+			v[0] = c.x, v[1] = c.y, v[2] = c.z, v[3] = c.w;
+			if (k0 + 4u < n)
+				v[4] = e[s0 + k0 + 4u];
+#pragma unroll
+			for (uint32_t t = 0; t < 4; t++)
+				cand[k0 + t] = (uint16_t)(k0 + t + 1u < n ? sa_z_pair_candidate(e, table, base, s0 + k0 + t, v[t], v[t + 1u]) : 0u);
+		}
+		__syncthreads();
+		if (k0 < n) {
+#pragma unroll
+			for (uint32_t t = 0; t < 4; t++)
+				if (k0 + t + 1u < n)
+					atomicMax(&table[sa_z_pair_hash(v[t], v[t + 1u])], s0 + k0 + t - base + 1u);
+		}
+		__syncthreads();
+	}
+	uint2 *const out = reinterpret_cast<uint2 *>(A.pairs + (size_t)tile * tile_elems + s0);
+	for (uint32_t k0 = 4u * (uint32_t)tid; k0 < n; k0 += 4u * ZT) {
+		uint32_t st[4];
+#pragma unroll
+		for (uint32_t t = 0; t < 4; t++) {
+			const uint32_t k = k0 + t;
+			st[t] = sa_z_pair_claim(k, k ? cand[k - 1u] : 0u, cand[k], k + 1u < n ? cand[k + 1u] : 0u);
+		}
+		out[k0 / 4u] = make_uint2(st[0] | st[1] << 16, st[2] | st[3] << 16);
+	}
 }
 
 __global__ __launch_bounds__(ZT) void sa_k_deflate_hist(SaZArgs A)
@@ -197,6 +273,154 @@ __global__ __launch_bounds__(ZT) void sa_k_deflate_hist(SaZArgs A)
 	uint32_t *const gh = A.ghist + ((size_t)tile * (size_t)A.ngrp + (size_t)(seg / ZGROUP)) * ZHIST;
 	for (int s = tid; s < ZHIST; s += ZT) {
 		const uint32_t c = hist[s] + (s == SA_Z_EOB ? 1u : 0u); /* every segment ends its block */
+		if (c)
+			atomicAdd(&gh[s], c);
+	}
+	if (tid == 0) {
+		const size_t at = (size_t)tile * (size_t)A.nseg + (size_t)seg;
+		A.seg_s1[at] = (uint32_t)(s_s1 % 65521ull);
+		A.seg_s2[at] = (uint32_t)(s_s2 % 65521ull);
+	}
+}
+
+/* sums over a wave, in lane 0 */
+__device__ __forceinline__ uint32_t z_wave_sum(uint32_t v)
+{
+	for (int d = 32; d > 0; d >>= 1)
+		v += (uint32_t)__shfl_down((int)v, d);
+	return v;
+}
+__device__ __forceinline__ unsigned long long z_wave_sum(unsigned long long v)
+{
+	for (int d = 32; d > 0; d >>= 1)
+		v += ((unsigned long long)(uint32_t)__shfl_down((int)(v >> 32), d) << 32) | (uint32_t)__shfl_down((int)(uint32_t)v, d);
+	return v;
+}
+
+/* sa_k_deflate_hist for the pair parse (levels SA_Z_PAIR_LEVEL .. 9): the segment is counted BOTH ways -- h[0] with what
+ * the match finder left (a pair start: symbol 262 and its distance, the element after it: nothing, every other element as in
+ * the fixed parse), h[1] as the fixed parse alone -- and the smaller of the two by sa_z_parse_cost goes into the group's
+ * histogram.  A segment the pairs do not pay for (zero padding, a few small values: a pair match costs up to 13 extra bits
+ * where two such elements cost next to nothing) gets its pair starts cleared, so that sa_k_deflate_encode<true> sees the
+ * fixed parse there.  Integer sums only: the choice does not depend on the order the lanes run in. */
+__global__ __launch_bounds__(ZT) void sa_k_deflate_hist_pairs(SaZArgs A)
+{
+	__shared__ uint32_t h[2][ZHIST];
+	__shared__ uint32_t s_total[2][2], s_extra[2]; /* [parse][literals, distances]; extra distance bits */
+	__shared__ unsigned long long s_s1, s_s2, s_cost[2];
+	const int tid = threadIdx.x, lane = tid & 63;
+	const int seg = blockIdx.x, tile = blockIdx.y;
+	uint32_t n;
+	const uint4 *const seg4 = z_segment(A, seg, tile, &n);
+	uint16_t *const segp = A.pairs + ((const uint32_t *)seg4 - A.raw);
+	for (int s = tid; s < 2 * ZHIST; s += ZT)
+		(&h[0][0])[s] = 0;
+	if (tid == 0) {
+		s_s1 = s_s2 = s_cost[0] = s_cost[1] = 0ull;
+		s_total[0][0] = s_total[0][1] = s_total[1][0] = s_total[1][1] = s_extra[0] = s_extra[1] = 0u;
+	}
+	__syncthreads();
+
+	unsigned long long s1 = 0, s2 = 0;
+	uint32_t extra[2] = { 0u, 0u };
+	const unsigned long long len = 4ull * n;
+	for (uint32_t q0 = 0; q0 < n / 4; q0 += ZT) {
+		const uint32_t q = q0 + tid;
+		const bool live = q < n / 4;
+		uint32_t e[12] = {}, st[5] = {};
+		if (live) {
+			z_load_quad(seg4, q, e);
+			z_load_pairs(segp, q, st);
+		}
+#pragma unroll
+		for (int t = 0; t < 4; t++) {
+			const uint32_t k = 4u * q + (uint32_t)t, v = e[8 + t];
+			int j[2] = { -1, -1 }; /* the element's length-3 match in either parse (-1: not coded that way) */
+			bool starts = false;
+			if (live) {
+				starts = !st[t] && st[t + 1];
+				j[1] = z_match_quad(e, k, t);
+				j[0] = st[t] || st[t + 1] ? -1 : j[1];
+				if (starts) {
+					uint32_t xb, xv;
+					atomicAdd(&h[0][288 + sa_z_dist_code(4u * st[t + 1], &xb, &xv)], 1u);
+					extra[0] += xb;
+				}
+#pragma unroll
+				for (int w = 0; w < 2; w++) {
+					if (j[w] < 0)
+						continue;
+					atomicAdd(&h[w][v & 255u], 1u);
+					if (!j[w]) {
+						atomicAdd(&h[w][(v >> 8) & 255u], 1u);
+						atomicAdd(&h[w][(v >> 16) & 255u], 1u);
+						atomicAdd(&h[w][v >> 24], 1u);
+					} else if (j[w] > 1) {
+						atomicAdd(&h[w][288 + sa_z_dcode(j[w])], 1u);
+						extra[w] += sa_z_dext_bits(j[w]);
+					}
+				}
+				const uint32_t b0 = v & 255u, b1 = (v >> 8) & 255u, b2 = (v >> 16) & 255u, b3 = v >> 24;
+				const uint32_t sum = b0 + b1 + b2 + b3;
+				s1 += sum;
+				s2 += (len - 4ull * k) * sum - (b1 + 2u * b2 + 3u * b3);
+			}
+			/* (the symbols nearly every element has are counted per wave, as in sa_k_deflate_hist) */
+			const unsigned long long m_pair = __ballot(starts);
+			if (lane == 0 && m_pair)
+				atomicAdd(&h[0][SA_Z_LEN8], (uint32_t)__popcll(m_pair));
+#pragma unroll
+			for (int w = 0; w < 2; w++) {
+				const unsigned long long m_any = __ballot(j[w] > 0), m_one = __ballot(j[w] == 1);
+				if (lane == 0) {
+					if (m_any)
+						atomicAdd(&h[w][SA_Z_LEN3], (uint32_t)__popcll(m_any));
+					if (m_one)
+						atomicAdd(&h[w][288 + sa_z_dcode(1)], (uint32_t)__popcll(m_one));
+				}
+			}
+		}
+	}
+	s1 = z_wave_sum(s1), s2 = z_wave_sum(s2);
+	extra[0] = z_wave_sum(extra[0]), extra[1] = z_wave_sum(extra[1]);
+	if (lane == 0) {
+		atomicAdd(&s_s1, s1);
+		atomicAdd(&s_s2, s2);
+		atomicAdd(&s_extra[0], extra[0]);
+		atomicAdd(&s_extra[1], extra[1]);
+	}
+	__syncthreads();
+	/* ---- which parse: symbols per alphabet, then sa_z_parse_cost, a counter or two per thread ---- */
+	static_assert(ZHIST <= 2 * ZT, "a thread takes counters tid and tid + ZT");
+#pragma unroll
+	for (int w = 0; w < 2; w++) {
+		const uint32_t lit = z_wave_sum(h[w][tid] + (tid + ZT < 288 ? h[w][tid + ZT] : 0u));
+		const uint32_t dist = z_wave_sum(tid + ZT >= 288 && tid + ZT < ZHIST ? h[w][tid + ZT] : 0u);
+		if (lane == 0) {
+			atomicAdd(&s_total[w][0], lit);
+			atomicAdd(&s_total[w][1], dist);
+		}
+	}
+	__syncthreads();
+#pragma unroll
+	for (int w = 0; w < 2; w++) {
+		unsigned long long c = sa_z_symbol_cost(h[w][tid], s_total[w][0]);
+		if (tid + ZT < ZHIST)
+			c += sa_z_symbol_cost(h[w][tid + ZT], s_total[w][tid + ZT < 288 ? 0 : 1]);
+		if (tid == 0)
+			c += 256ull * s_extra[w];
+		c = z_wave_sum(c);
+		if (lane == 0)
+			atomicAdd(&s_cost[w], c);
+	}
+	__syncthreads();
+	const int w = s_cost[0] < s_cost[1] ? 0 : 1;
+	if (w == 1) /* the pairs do not pay here */
+		for (uint32_t q = tid; q < n / 4; q += ZT)
+			reinterpret_cast<uint2 *>(segp)[q] = make_uint2(0u, 0u);
+	uint32_t *const gh = A.ghist + ((size_t)tile * (size_t)A.ngrp + (size_t)(seg / ZGROUP)) * ZHIST;
+	for (int s = tid; s < ZHIST; s += ZT) {
+		const uint32_t c = h[w][s] + (s == SA_Z_EOB ? 1u : 0u); /* every segment ends its block */
 		if (c)
 			atomicAdd(&gh[s], c);
 	}
@@ -275,12 +499,15 @@ __global__ __launch_bounds__(ZT) void sa_k_deflate_codes(SaZArgs A)
 		G.hdr_bits = s_hdr_bits;
 }
 
-__global__ __launch_bounds__(ZT) void sa_k_deflate_encode(SaZArgs A)
+/* PAIRS: a pair start is symbol 262 and its distance (at most SA_Z_PAIR_BITS <= SA_Z_ELEM_BITS bits: the stage and the
+ * slot bounds hold as they are), the element after it no bits at all */
+template <bool PAIRS> __global__ __launch_bounds__(ZT) void sa_k_deflate_encode(SaZArgs A)
 {
 	__shared__ uint32_t lcode[288], dcode[32], stage[ZSTAGE_WORDS];
 	__shared__ uint32_t wave_sum[ZT / 64];
 	__shared__ uint32_t s_tail_bytes;
 	static_assert(ZE == 4, "a thread encodes one quad per round");
+	static_assert(SA_Z_PAIR_BITS <= SA_Z_ELEM_BITS, "ZSTAGE_WORDS and ZSLOT_WORDS count SA_Z_ELEM_BITS per element");
 
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int seg = blockIdx.x, tile = blockIdx.y;
@@ -304,15 +531,25 @@ __global__ __launch_bounds__(ZT) void sa_k_deflate_encode(SaZArgs A)
 		{
 			const uint32_t q = r0 / 4 + (uint32_t)tid;
 			uint32_t el[12] = {};
+			[[maybe_unused]] uint32_t st[5] = {};
 			const bool live = q < n / 4;
-			if (live)
+			if (live) {
 				z_load_quad(seg4, q, el);
+				if constexpr (PAIRS)
+					z_load_pairs(A.pairs + ((const uint32_t *)seg4 - A.raw), q, st);
+			}
 #pragma unroll
 			for (int e = 0; e < ZE; e++) {
 				nb[e] = 0;
 				bits[e] = 0;
-				if (live)
-					nb[e] = sa_z_element(lcode, dcode, el[8 + e], z_match_quad(el, 4u * q + (uint32_t)e, e), &bits[e]);
+				if (live) {
+					if (PAIRS && st[e]) /* the second half of a pair match */
+						;
+					else if (PAIRS && st[e + 1])
+						nb[e] = sa_z_pair_bits(lcode, dcode, st[e + 1], &bits[e]);
+					else
+						nb[e] = sa_z_element(lcode, dcode, el[8 + e], z_match_quad(el, 4u * q + (uint32_t)e, e), &bits[e]);
+				}
 				mine += nb[e];
 			}
 		}
@@ -496,6 +733,7 @@ struct sa_zjob {
 	int device = 0;
 	int32_t num = 0, chunk = 0, chunk_shift = 0, nc = 0, nseg = 0, ngrp = 0;
 	bool stored = false; /* level 0: raw tiles */
+	bool pairs = false;  /* levels SA_Z_PAIR_LEVEL .. 9: the pair parse */
 	const int32_t *d_packed = nullptr, *d_full = nullptr;
 	int32_t *d_owned = nullptr; /* the packed matrix, when the job made it (sa_hip_tiles_begin) */
 	sa_ctx *ctx = nullptr;
@@ -506,6 +744,7 @@ struct sa_zjob {
 	uint8_t *d_out[2] = {};
 	unsigned long long *d_info[2] = {}; /* tile_bytes[nc], tile_base[nc + 1] */
 	uint32_t *d_raw = nullptr; /* the batch's raw tiles (level 0: d_out itself) */
+	uint16_t *d_pairs = nullptr; /* what the match finder leaves for a batch: two bytes per element (the pair parse only) */
 	size_t tile_bound = 0, row_bound = 0;
 	unsigned long long *h_info[2] = {};
 	uint8_t *h_buf[2] = {};
@@ -561,6 +800,7 @@ static void zjob_free(sa_zjob *z)
 	(void)hipFree(z->d_groups);
 	if (!z->stored)
 		(void)hipFree(z->d_raw);
+	(void)hipFree(z->d_pairs);
 	(void)hipFree(z->d_owned);
 	for (int k = 0; k < 2; k++) {
 		(void)hipFree(z->d_out[k]);
@@ -627,6 +867,7 @@ static SaZArgs zjob_args(const sa_zjob *z, const SaZBatch &b, int par)
 	a.tile_adler = z->d_tile_adler;
 	a.out = z->d_out[par];
 	a.raw = z->stored ? reinterpret_cast<uint32_t *>(z->d_out[par]) : z->d_raw;
+	a.pairs = z->d_pairs;
 	return a;
 }
 
@@ -687,11 +928,15 @@ static bool zjob_enqueue_encode(sa_zjob *z, int64_t id)
 	SA_HIP_CHECK(hipGetLastError(), return false);
 	if (!z->stored) {
 		SA_HIP_CHECK(hipMemsetAsync(z->d_ghist, 0, sizeof(uint32_t) * (size_t)nt * (size_t)z->ngrp * ZHIST, z->stream), return false);
-		hipLaunchKernelGGL(sa_k_deflate_hist, per_seg, dim3(ZT), 0, z->stream, a);
+		if (z->pairs) {
+			hipLaunchKernelGGL(sa_k_deflate_pairs, per_seg, dim3(ZT), 0, z->stream, a);
+			SA_HIP_CHECK(hipGetLastError(), return false);
+		}
+		hipLaunchKernelGGL(z->pairs ? sa_k_deflate_hist_pairs : sa_k_deflate_hist, per_seg, dim3(ZT), 0, z->stream, a);
 		SA_HIP_CHECK(hipGetLastError(), return false);
 		hipLaunchKernelGGL(sa_k_deflate_codes, per_grp, dim3(ZT), 0, z->stream, a);
 		SA_HIP_CHECK(hipGetLastError(), return false);
-		hipLaunchKernelGGL(sa_k_deflate_encode, per_seg, dim3(ZT), 0, z->stream, a);
+		hipLaunchKernelGGL(z->pairs ? sa_k_deflate_encode<true> : sa_k_deflate_encode<false>, per_seg, dim3(ZT), 0, z->stream, a);
 		SA_HIP_CHECK(hipGetLastError(), return false);
 		hipLaunchKernelGGL(sa_k_deflate_offsets, dim3(nt), dim3(ZT), 0, z->stream, a);
 		SA_HIP_CHECK(hipGetLastError(), return false);
@@ -723,8 +968,10 @@ static bool zjob_enqueue_copy(sa_zjob *z, int64_t id, int which, size_t bytes)
 	return true;
 }
 
-static sa_zjob *zjob_make(int device, const int32_t *d_packed, const int32_t *d_full, int32_t num, size_t chunk_dim, bool stored)
+/* level: 0 raw tiles, 1 .. SA_Z_PAIR_LEVEL - 1 the fixed parse, SA_Z_PAIR_LEVEL .. 9 the pair parse */
+static sa_zjob *zjob_make(int device, const int32_t *d_packed, const int32_t *d_full, int32_t num, size_t chunk_dim, int level)
 {
+	const bool stored = level == 0;
 	if (num < 2 || (!d_packed && !d_full)) {
 		sa_set_error("sa_zjob: no matrix");
 		return nullptr;
@@ -751,6 +998,7 @@ static sa_zjob *zjob_make(int device, const int32_t *d_packed, const int32_t *d_
 	z->d_packed = d_packed;
 	z->d_full = d_packed ? nullptr : d_full;
 	z->stored = stored;
+	z->pairs = level >= SA_Z_PAIR_LEVEL;
 	const size_t segs = (size_t)z->nc * (size_t)z->nseg;
 	/* a tile's stream at its very worst (header, 63 bits per element, the segments' ends), on a 64-byte boundary */
 	z->tile_bound = stored ? chunk_dim * chunk_dim * sizeof(int32_t) : (((size_t)z->nseg * ZSLOT_WORDS * 4 + 64) + 255) & ~(size_t)255;
@@ -783,6 +1031,9 @@ static sa_zjob *zjob_make(int device, const int32_t *d_packed, const int32_t *d_
 			break;
 		}
 		SA_HIP_CHECK(hipMalloc(&z->d_raw, (size_t)z->nc * chunk_dim * chunk_dim * sizeof(uint32_t)), break);
+		if (z->pairs) {
+			SA_HIP_CHECK(hipMalloc(&z->d_pairs, (size_t)z->nc * chunk_dim * chunk_dim * sizeof(uint16_t)), break);
+		}
 		SA_HIP_CHECK(hipMalloc(&z->d_slots, segs * ZSLOT_WORDS * sizeof(uint32_t)), break);
 		SA_HIP_CHECK(hipMalloc(&z->d_seg, 4 * segs * sizeof(uint32_t)), break);
 		SA_HIP_CHECK(hipMalloc(&z->d_ghist, sizeof(uint32_t) * (size_t)z->nc * (size_t)z->ngrp * ZHIST), break);
@@ -902,7 +1153,7 @@ static int zjob_fetch(sa_zjob *z, int64_t id, const uint8_t **streams, size_t *s
 
 extern "C" sa_zjob *sa_zjob_create(int device, const int32_t *d_packed, const int32_t *d_full, int32_t num, size_t chunk_dim, int level)
 {
-	return sa_guard("sa_zjob_create", (sa_zjob *)nullptr, [&] { return zjob_make(device, d_packed, d_full, num, chunk_dim, level == 0); });
+	return sa_guard("sa_zjob_create", (sa_zjob *)nullptr, [&] { return zjob_make(device, d_packed, d_full, num, chunk_dim, level); });
 }
 
 extern "C" void sa_zjob_destroy(sa_zjob *job)
@@ -1006,7 +1257,7 @@ extern "C" double sa_zjob_align_seconds(const sa_zjob *z)
 
 /* one device's part of a walk in shells: context, the packed matrix (whole: a block's place in it is its own), a job over
  * the column blocks `first`, `first + step`, ...; the first two of them are on their way when this returns */
-static sa_zjob *zjob_begin_on(int device, struct sa_input in, const struct sa_scoring *sc, size_t chunk_dim, bool stored, int first, int step)
+static sa_zjob *zjob_begin_on(int device, struct sa_input in, const struct sa_scoring *sc, size_t chunk_dim, int level, int first, int step)
 {
 	sa_ctx *ctx = sa_ctx_create(device, in, sc);
 	if (!ctx)
@@ -1018,7 +1269,7 @@ static sa_zjob *zjob_begin_on(int device, struct sa_input in, const struct sa_sc
 		const int64_t pairs = sa_ctx_pairs(ctx);
 		SA_HIP_CHECK(hipSetDevice(device), break);
 		SA_HIP_CHECK(hipMalloc(&d_packed, sizeof(int32_t) * (size_t)pairs), break);
-		z = zjob_make(device, d_packed, nullptr, in.num, chunk_dim, stored);
+		z = zjob_make(device, d_packed, nullptr, in.num, chunk_dim, level);
 		if (!z)
 			break;
 		z->shells = true;
@@ -1072,11 +1323,11 @@ extern "C" sa_zjob *sa_hip_tiles_begin(struct sa_input in, const struct sa_scori
 			parts = env.tiles_split;
 		const int nc = chunk_dim ? (int)(((size_t)in.num + chunk_dim - 1) / chunk_dim) : 1;
 		parts = std::max(1, std::min(parts, nc)); /* (a device without a column block would have nothing to do) */
-		sa_zjob *z = zjob_begin_on(0, in, sc, chunk_dim, level == 0, 0, parts);
+		sa_zjob *z = zjob_begin_on(0, in, sc, chunk_dim, level, 0, parts);
 		if (!z)
 			return nullptr;
 		for (int k = 1; k < parts; k++) {
-			sa_zjob *p = zjob_begin_on(folded ? 0 : k, in, sc, chunk_dim, level == 0, k, parts);
+			sa_zjob *p = zjob_begin_on(folded ? 0 : k, in, sc, chunk_dim, level, k, parts);
 			if (!p) {
 				zjob_free(z);
 				return nullptr;

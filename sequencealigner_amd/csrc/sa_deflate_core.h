@@ -302,4 +302,127 @@ SA_HD inline void sa_z_adler_append(uint32_t &a, uint32_t &b, uint32_t s1, uint3
 	a = (a + s1) % 65521u;
 }
 
+/* ---- the pair parse (levels SA_Z_PAIR_LEVEL .. 9) -------------------------------------------------------------------------
+ * Neighbouring scores repeat as PAIRS far more often than the fixed parse can use: on a tile of NW scores three elements in
+ * four sit inside an 8-byte match onto an earlier (element, next element) pair of the same tile, somewhere in the 32 KB
+ * before them.  A pair match at element k: length 8 (symbol 262, no extra bits), distance 4 (k - p), e[p] == e[k],
+ * e[p + 1] == e[k + 1], k - p <= SA_Z_PAIR_WINDOW, k and k + 1 in one segment (a symbol belongs to one block); p may lie in
+ * an earlier segment of the tile (a stream's window runs through its blocks), never in another tile.
+ *
+ * Still a data-parallel parse -- no chains, no lazy evaluation:
+ *   candidates   a hash table keyed on the pair holds, per key, the LATEST position inserted (a max on the position: the
+ *                nearest candidate wins whatever order the insertions land in).  It is pre-rolled with the window before the
+ *                segment, then the segment goes by in sub-blocks of SA_Z_PAIR_SUB elements: all of a sub-block look up, then
+ *                all of it insert -- a candidate lies before the sub-block of its element.  A candidate is verified on the
+ *                elements themselves: a collision or a stale entry loses a match, it never makes a wrong one.
+ *   claims       round 1: every even k with a candidate takes k, k + 1.  Round 2: every odd k with a candidate whose two
+ *                elements are still free takes them (k - 1 and k + 1 are even: free means they have no candidate).
+ *   the rest     every element left over is coded as in the fixed parse (sa_z_match / sa_z_element).
+ *   where        a pair match costs its length symbol, a distance symbol and up to 13 extra bits -- a gain where the two
+ *                elements would have cost two nearly random low bytes, a loss where they cost next to nothing (zero
+ *                padding beyond N, a few small values).  So every SEGMENT is counted both ways, and takes the pair parse
+ *                only where that comes out smaller under codes of its own (sa_z_parse_cost: integer arithmetic, the same
+ *                answer on every run and in the host harness); a segment that declines is the fixed parse's, bit for bit
+ *                up to the codes it shares with its group. */
+enum : int {
+	SA_Z_PAIR_LEVEL = 7,       /* -z levels from here on use the pair parse; 1 .. 6: the fixed parse, unchanged          */
+	SA_Z_LEN8 = 262,           /* match length 8 (no extra bits)                                                        */
+	SA_Z_PAIR_WINDOW = 8192,   /* elements a pair match may reach back: DEFLATE's 32 768 bytes                          */
+	SA_Z_PAIR_SUB = 1024,      /* elements per sub-block of the match finder                                            */
+	SA_Z_PAIR_TABLE_BITS = 13, /* the finder's hash table: 8192 entries for the 8192 positions of a window              */
+	SA_Z_PAIR_TABLE = 1 << SA_Z_PAIR_TABLE_BITS,
+	SA_Z_PAIR_BITS = 43        /* a pair start never takes more: 15 + 15 + 13 (<= SA_Z_ELEM_BITS)                      */
+};
+
+/* distance d bytes, 1 <= d <= 32768: code (RFC 1951 3.2.5), number of extra bits, their value.  sa_z_dcode / _dext_bits /
+ * _dext_val are this for d = 4 j, j <= 8. */
+SA_HD inline uint32_t sa_z_dist_code(uint32_t d, uint32_t *ext_bits, uint32_t *ext_val)
+{
+	const uint32_t x = d - 1u;
+	if (x < 4u) {
+		*ext_bits = *ext_val = 0u;
+		return x;
+	}
+	uint32_t msb = 2;
+	while (x >> (msb + 1u))
+		msb++;
+	*ext_bits = msb - 1u;
+	*ext_val = x & ((1u << (msb - 1u)) - 1u);
+	return 2u * msb + ((x >> (msb - 1u)) & 1u);
+}
+
+/* table slot of the pair (a, b) */
+SA_HD inline uint32_t sa_z_pair_hash(uint32_t a, uint32_t b)
+{
+	return ((a * 2654435761u + b) * 2246822519u) >> (32 - SA_Z_PAIR_TABLE_BITS);
+}
+
+/* The candidate of the element at position `at` of the tile e[], (a, b) = (e[at], e[at + 1]): how many elements back the
+ * pair was seen, 0: none.  A table entry is (position - base) + 1 of the latest insertion under its key, 0: empty;
+ * base = the first position of the window the table was pre-rolled with. */
+SA_HD inline uint32_t sa_z_pair_candidate(const uint32_t *e, const uint32_t *table, uint32_t base, uint32_t at, uint32_t a, uint32_t b)
+{
+	const uint32_t c = table[sa_z_pair_hash(a, b)];
+	if (!c)
+		return 0u;
+	const uint32_t p = base + c - 1u;
+	if (p >= at || at - p > (uint32_t)SA_Z_PAIR_WINDOW || e[p] != a || e[p + 1u] != b)
+		return 0u;
+	return at - p;
+}
+
+/* The two claim rounds for element k of a segment from the candidates of k - 1, k, k + 1 (0 where there is no such element
+ * in the segment): the distance in elements if k starts a pair match, else 0.  Element k is the second half of a match
+ * exactly when this is nonzero for k - 1. */
+SA_HD inline uint32_t sa_z_pair_claim(uint32_t k, uint32_t before, uint32_t own, uint32_t after)
+{
+	if (!(k & 1u))
+		return own;
+	return before || after ? 0u : own;
+}
+
+/* log2(x) in 1/256 bit, x >= 1: the exponent, and a straight line through the mantissa (at most 0.09 bit low) */
+SA_HD inline uint32_t sa_z_lg(uint32_t x)
+{
+	const int e = 31 - __builtin_clz(x);
+	return 256u * (uint32_t)e + ((e >= 8 ? x >> (e - 8) : x << (8 - e)) & 255u);
+}
+/* what `count` symbols of an alphabet that holds `total` in all cost, in 1/256 bit: their share of the entropy, at least a
+ * bit each (a Huffman code has no shorter one) */
+SA_HD inline uint64_t sa_z_symbol_cost(uint32_t count, uint32_t total)
+{
+	if (!count)
+		return 0;
+	const uint32_t each = sa_z_lg(total) - sa_z_lg(count);
+	return (uint64_t)count * (each < 256u ? 256u : each);
+}
+/* a segment's size under codes of its own, in 1/256 bit, from its histograms (lit[0 .. 288): literals and lengths with their
+ * sum lit_total, dist[0 .. 32) likewise) and the extra bits of its distances -- the measure the two parses are compared by */
+SA_HD inline uint64_t sa_z_parse_cost(const uint32_t *lit, uint32_t lit_total, const uint32_t *dist, uint32_t dist_total, uint32_t extra_bits)
+{
+	uint64_t c = 256ull * extra_bits;
+	for (int s = 0; s < 288; s++)
+		c += sa_z_symbol_cost(lit[s], lit_total);
+	for (int s = 0; s < 32; s++)
+		c += sa_z_symbol_cost(dist[s], dist_total);
+	return c;
+}
+
+/* the bits of a pair start `back` elements behind its match (LSB first); returns their number (<= SA_Z_PAIR_BITS) */
+SA_HD inline uint32_t sa_z_pair_bits(const uint32_t *lcode, const uint32_t *dcode, uint32_t back, uint64_t *bits)
+{
+	uint32_t xb, xv;
+	const uint32_t ds = sa_z_dist_code(4u * back, &xb, &xv);
+	uint32_t c = lcode[SA_Z_LEN8];
+	uint64_t acc = c & 0xffffu;
+	uint32_t n = c >> 16;
+	c = dcode[ds];
+	acc |= (uint64_t)(c & 0xffffu) << n;
+	n += c >> 16;
+	acc |= (uint64_t)xv << n;
+	n += xb;
+	*bits = acc;
+	return n;
+}
+
 #endif /* SA_DEFLATE_CORE_H */

@@ -1,6 +1,7 @@
 """tools/gpu_fuzz_deflate.py [seed] [cases] -- random matrices through the device-side tile / DEFLATE path (csrc/sa_deflate.hip):
 random N, the product's chunk rule or a random power of two, score distributions from benign to adversarial, packed and full
-device matrices, level 6 (zlib streams, inflated with stock zlib) and level 0 (raw tiles); every tile of every case against the
+device matrices, a level drawn per case -- 1 .. 6 the fixed parse, 7 .. 9 the pair parse (zlib streams, inflated with stock
+zlib), 0 raw tiles; every tile of every case against the
 full symmetric matrix built on the host.  Then sa_hip_tiles_begin / sa_zjob_next (the walk in shells while the alignment runs)
 on random small stores against the oracle."""
 import os
@@ -55,7 +56,7 @@ for case in range(cases):
     n = int(rng.integers(257, 2600))
     chunk = chunk_rule(n) if rng.random() < 0.6 else int(2 ** rng.integers(6, 11))
     kind = int(rng.integers(0, 7))
-    level = 6 if rng.random() < 0.75 else 0
+    level = int(rng.integers(1, 10)) if rng.random() < 0.8 else 0
     tri = draw(n, kind)
     full = tri_to_full(tri, n)
     nc = -(-n // chunk)
@@ -88,7 +89,7 @@ for case in range(max(4, cases // 6)):
     store = sa.SequenceStore.from_sequences(seqs)
     scoring = sa.Scoring.from_names(method, "nuc44" if dna else "blosum62", **gaps)
     chunk = chunk_rule(n)
-    level = 6 if rng.random() < 0.7 else 0
+    level = int(rng.integers(1, 10)) if rng.random() < 0.8 else 0
     full = tri_to_full(oracle.align(store, scoring, triangular=True, threads=16), n)
     nc = -(-n // chunk)
     pad = np.zeros((nc * chunk, nc * chunk), np.int32)
