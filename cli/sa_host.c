@@ -625,8 +625,41 @@ static int write_deflated_tiles(hid_t mset, size_t chunk, size_t dim, const int3
 
 /* the file, /sequences and the (empty) /similarity_matrix dataset: everything of flush_hdf5 (src/io/format/hdf5.c:14-112) up to
  * the matrix data.  0 on success: *file_out, *mset_out open, *chunk_out = the chunk dimension (dim when contiguous). */
+static int create_with_sequences(const char *path, const struct sa_host_store *s, hid_t *file_out);
 static int open_output(const char *path, const struct sa_host_store *s, unsigned compression, hid_t *file_out, hid_t *mset_out,
 		       size_t *chunk_out)
+{
+	const size_t dim = (size_t)s->in.num;
+	hid_t file;
+	if (create_with_sequences(path, s, &file))
+		return 1;
+
+	/* /similarity_matrix: N x N int32 little endian */
+	hsize_t md[2] = { dim, dim };
+	hid_t mspace = H5Screate_simple(2, md, NULL);
+	hid_t plist = H5Pcreate(H5P_DATASET_CREATE);
+	const size_t chunk = sa_host_hdf5_chunk_dim(dim);
+	if (dim > 256) {
+		hsize_t cd[2] = { chunk, chunk };
+		H5Pset_chunk(plist, 2, cd);
+		if (compression)
+			H5Pset_deflate(plist, compression);
+	}
+	hid_t mset = H5Dcreate2(file, "/similarity_matrix", H5T_STD_I32LE, mspace, H5P_DEFAULT, plist, H5P_DEFAULT);
+	H5Pclose(plist);
+	H5Sclose(mspace);
+	if (mset < 0) {
+		H5Fclose(file);
+		return fail("Failed to create HDF5 dataset for Similarity Matrix");
+	}
+	*file_out = file;
+	*mset_out = mset;
+	*chunk_out = chunk;
+	return 0;
+}
+
+/* the file and /sequences (src/io/format/hdf5.c:14-68); 0 on success: *file_out open */
+static int create_with_sequences(const char *path, const struct sa_host_store *s, hid_t *file_out)
 {
 	const size_t dim = (size_t)s->in.num;
 	hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
@@ -660,29 +693,49 @@ static int open_output(const char *path, const struct sa_host_store *s, unsigned
 		H5Fclose(file);
 		return fail("Failed to write sequence data to HDF5 dataset");
 	}
-
-	/* /similarity_matrix: N x N int32 little endian */
-	hsize_t md[2] = { dim, dim };
-	hid_t mspace = H5Screate_simple(2, md, NULL);
-	hid_t plist = H5Pcreate(H5P_DATASET_CREATE);
-	const size_t chunk = sa_host_hdf5_chunk_dim(dim);
-	if (dim > 256) {
-		hsize_t cd[2] = { chunk, chunk };
-		H5Pset_chunk(plist, 2, cd);
-		if (compression)
-			H5Pset_deflate(plist, compression);
-	}
-	hid_t mset = H5Dcreate2(file, "/similarity_matrix", H5T_STD_I32LE, mspace, H5P_DEFAULT, plist, H5P_DEFAULT);
-	H5Pclose(plist);
-	H5Sclose(mspace);
-	if (mset < 0) {
-		H5Fclose(file);
-		return fail("Failed to create HDF5 dataset for Similarity Matrix");
-	}
 	*file_out = file;
-	*mset_out = mset;
-	*chunk_out = chunk;
 	return 0;
+}
+
+/* /neighbor_indices and /neighbor_scores: N x k int32 little endian, contiguous -- row r lists the k best partners of
+ * sequence r (include/seqalign_hip.h: sa_hip_neighbors).  create = 0: added to the finished file at `path`, whose other
+ * datasets stay as they are; create = 1: a new file with /sequences and these two, no /similarity_matrix. */
+int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int32_t k, const int32_t *index, const int32_t *score,
+			    int create)
+{
+	if (!path || !s || !index || !score)
+		return fail("Neighbor data missing");
+	const size_t dim = (size_t)s->in.num;
+	if (k < 1 || k > SA_HIP_NEIGHBORS_MAX || dim < 2 || (size_t)k > dim - 1)
+		return fail("Neighbor count must be between 1 and %d and below the number of sequences", SA_HIP_NEIGHBORS_MAX);
+	hid_t file;
+	if (create) {
+		if (create_with_sequences(path, s, &file))
+			return 1;
+	} else {
+		hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
+		H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
+		H5Pset_alignment(fapl, 4096, 4096);
+		H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
+		H5Pclose(fapl);
+		if (file < 0)
+			return fail("Failed to open HDF5 file: %s", path);
+	}
+	const char *names[2] = { "/neighbor_indices", "/neighbor_scores" };
+	const int32_t *data[2] = { index, score };
+	hsize_t nd[2] = { dim, (hsize_t)k };
+	hid_t space = H5Screate_simple(2, nd, NULL);
+	int rc = 0;
+	for (int d = 0; d < 2 && !rc; d++) {
+		hid_t set = H5Dcreate2(file, names[d], H5T_STD_I32LE, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || H5Dwrite(set, H5T_NATIVE_INT32, H5S_ALL, H5S_ALL, H5P_DEFAULT, data[d]) < 0)
+			rc = fail("Failed to write %s to HDF5", names[d] + 1);
+		if (set >= 0)
+			H5Dclose(set);
+	}
+	H5Sclose(space);
+	H5Fclose(file);
+	return rc;
 }
 
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder

@@ -73,6 +73,11 @@ size_t sa_host_hdf5_chunk_dim(size_t dim); /* exposed for tests */
 typedef int (*sa_host_tiles_fn)(void *user, uint32_t *rows, uint32_t *cols, const uint8_t **streams, size_t *sizes);
 int sa_host_write_hdf5_streams(const char *path, const struct sa_host_store *s, unsigned compression, sa_host_tiles_fn next,
 			       void *user);
+/* The -k option: /neighbor_indices and /neighbor_scores, N x k I32LE each, contiguous (the arrays of sa_hip_neighbors /
+ * sa_zjob_neighbors).  create = 0 reopens the finished file at `path` and adds the two datasets; create = 1 writes a new
+ * file with /sequences and the two, no /similarity_matrix (--neighbors-only). */
+int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int32_t k, const int32_t *index, const int32_t *score,
+			    int create);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,9 @@
  *             -C/--no-cuda  -W/--no-write  -P/--no-progress  -D/--no-detail  -F/--force-proceed
  *             -Q/--quiet  -V/--verbose  -h/--help
  *   added     --column N  --no-header   (non-interactive answers to the reference's DSV column prompt)
- * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> -B report.
+ *             -k/--neighbors K  --neighbors-only   (the K best partners of every sequence, selected on the device:
+ *             /neighbor_indices and /neighbor_scores; with --neighbors-only no /similarity_matrix at all)
+ * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
 #define _GNU_SOURCE
@@ -90,6 +92,8 @@ struct options {
 	int threads;
 	bool benchmark, no_device, no_write, list;
 	int dsv_column, dsv_has_header;
+	int neighbors; /* -k: 0 = not given */
+	bool neighbors_only;
 };
 
 static void usage(const char *argv0)
@@ -116,6 +120,9 @@ static void usage(const char *argv0)
 	       "  -F, --force-proceed      Force proceed without user prompts (for CI)\n"
 	       "  -Q, --quiet              Suppress all non-error printing\n"
 	       "  -V, --verbose            Enable verbose printing\n"
+	       "  -k, --neighbors K        Also write the K best partners of every sequence [1-64]:\n"
+	       "                           /neighbor_indices and /neighbor_scores (score descending, index ascending)\n"
+	       "      --neighbors-only     With -k: no /similarity_matrix, the matrix never leaves the device\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -146,7 +153,8 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "benchmark", 'B', false }, { "threads", 'T', true }, { "no-cuda", 'C', false },
 		     { "no-write", 'W', false }, { "no-progress", 'P', false }, { "no-detail", 'D', false },
 		     { "force-proceed", 'F', false }, { "quiet", 'Q', false }, { "verbose", 'V', false },
-		     { "help", 'h', false }, { "column", 1, true }, { "no-header", 2, false }, { NULL, 0, false } };
+		     { "help", 'h', false }, { "column", 1, true }, { "no-header", 2, false },
+		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -246,6 +254,14 @@ static int parse_args(int argc, char **argv, struct options *o)
 				o->dsv_column = (int)v - 1;
 				break;
 			case 2: o->dsv_has_header = 0; break;
+			case 'k':
+				if (!parse_long(val, 1, SA_HIP_NEIGHBORS_MAX, &v)) {
+					err("Neighbor count must be between 1-%d", SA_HIP_NEIGHBORS_MAX);
+					return 1;
+				}
+				o->neighbors = (int)v;
+				break;
+			case 3: o->neighbors_only = true; break;
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -322,6 +338,8 @@ int main(int argc, char **argv)
 		ok = (err("Options -o, --output and -W, --no-write conflict"), false);
 	if (ok && !o.output && !o.no_write)
 		ok = (err("Missing required option: -o, --output"), false);
+	if (ok && o.neighbors_only && !o.neighbors)
+		ok = (err("Option --neighbors-only requires -k, --neighbors"), false);
 	if (ok && sa_matrix_load(o.matrix, sc.lut, sc.sub))
 		ok = (err("Invalid substitution matrix name"), false);
 	if (ok && (sc.method = sa_method_parse(o.align)) < 0)
@@ -380,8 +398,10 @@ int main(int argc, char **argv)
 		info("Gap open: %d, extend: %d", sc.gap_opn, sc.gap_ext);
 	if (o.filter > 0.0f)
 		info("Filter threshold: %.1f%%", (double)o.filter * 100.0);
+	if (o.neighbors)
+		info("Neighbors: %d per sequence%s", o.neighbors, o.neighbors_only ? " (no similarity matrix)" : "");
 
-	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t0;
+	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t0;
 	stamp("options parsed");
 	struct sa_host_store store;
 	t0 = now();
@@ -411,6 +431,22 @@ int main(int argc, char **argv)
 	info("Loaded %d sequences", store.in.num);
 	info("Average sequence length: %.2f", (double)store.blob_bytes / (double)store.in.num - 1.0);
 
+	if (o.neighbors && (long long)o.neighbors > (long long)store.in.num - 1) {
+		err("Neighbor count %d exceeds the %d other sequences", o.neighbors, store.in.num - 1);
+		fprintf(stderr, "Use %s -h, --help for usage information\n", argv[0]);
+		return 1;
+	}
+	int32_t *nb_index = NULL, *nb_score = NULL;
+	bool nb_done = false, nb_second_pass = false;
+	if (o.neighbors) {
+		nb_index = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
+		nb_score = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
+		if (!nb_index || !nb_score) {
+			err("Out of memory allocating neighbor data");
+			return 1;
+		}
+	}
+
 	/* output_load (src/io/output.c:35-55): a full matrix that exceeds 3/4 of the available RAM goes to temporary
 	 * file storage and is stored triangular; so is one the device(s) cannot hold */
 	const size_t n = (size_t)store.in.num;
@@ -422,7 +458,7 @@ int main(int argc, char **argv)
 	 * SA_HOST_CPU_DEFLATE=1 keeps zlib at exactly the level asked for (all cores, sa_host_write_hdf5). */
 	const long long npairs = (long long)n * ((long long)n - 1) / 2;
 	const size_t zchunk = sa_host_hdf5_chunk_dim(n);
-	bool device_deflate = !o.no_write && n > 256 && !getenv("SA_HOST_MATRIX") &&
+	bool device_deflate = !o.no_write && !o.neighbors_only && n > 256 && !getenv("SA_HOST_MATRIX") &&
 			      (o.compression > 0 ? !getenv("SA_HOST_CPU_DEFLATE") && !getenv("SA_HOST_SERIAL_DEFLATE")
 						 /* without -z the same walk returns the tiles as they are: H5Dwrite_chunk instead of H5Dwrite's
 						  * gather of every tile out of N-wide rows.  On several devices the plain path stays with sa_hip_align
@@ -437,7 +473,7 @@ int main(int argc, char **argv)
 					       (o.compression >= SA_HIP_Z_PAIR_LEVEL ? row_raw / 2 : 0));
 		stamp("device memory probed (runtime up)");
 	}
-	if (!o.no_write && !device_deflate) {
+	if (!o.no_write && !device_deflate && !o.neighbors_only) {
 		const size_t full_bytes = sizeof(int32_t) * n * n;
 		const bool tmpf = sa_host_matrix_needs_file(n);
 		out.triangular = tmpf || !sa_hip_memory(full_bytes);
@@ -510,8 +546,37 @@ int main(int argc, char **argv)
 		verb("%s on the device: %.2f GB -> %.2f GB (%.2f : 1); the writer waited %.0f ms for the encoder, %.0f ms for gather + copy",
 		     o.compression ? "Deflated" : "Tiled", (double)raw / 1e9, (double)outb / 1e9, outb ? (double)raw / (double)outb : 0.0, enc_ms,
 		     copy_ms);
+		/* the finished matrix is still on the device: the neighbours come from it, nothing is aligned twice */
+		if (o.neighbors) {
+			if (sa_zjob_neighbors(job, o.neighbors, nb_index, nb_score) == 0) {
+				nb_done = true;
+				t_select = sa_hip_last_neighbors_seconds();
+				verb("Neighbors selected from the device's finished matrix (no second alignment)");
+			} else {
+				verb("Neighbors: %s", sa_last_error());
+			}
+		}
 		sa_zjob_destroy(job);
 		stamp("HDF5 written");
+	} else if (o.neighbors_only) {
+		/* no host matrix, no tiles, no matrix transfer: align into device memory, select there, copy back 2 N K ints */
+		info("Similarity Matrix stays on the device: %d neighbors per sequence are selected there", o.neighbors);
+		t0 = now();
+		if (!sa_hip_neighbors(store.in, &sc, o.neighbors, nb_index, nb_score)) {
+			err("%s", sa_last_error());
+			return 1;
+		}
+		const double call = now() - t0;
+		stamp("sa_hip_neighbors returned");
+		if (show_progress) {
+			progress_line(1.0, NULL);
+			fputc('\n', stderr);
+			sa_hip_set_progress(NULL, NULL);
+		}
+		nb_done = true;
+		t_align = sa_hip_last_align_seconds();
+		t_select = sa_hip_last_neighbors_seconds();
+		t_setup = call > t_align + t_select ? call - t_align - t_select : 0.0;
 	} else {
 		t0 = now();
 		if (!sa_hip_align(store.in, out, &sc)) {
@@ -541,6 +606,27 @@ int main(int argc, char **argv)
 			stamp("HDF5 written");
 		}
 	}
+	if (o.neighbors && !nb_done) {
+		/* the other paths (N <= 256, SA_HOST_* switches, -W, several devices, a walk dealt over several jobs) no longer hold
+		 * the matrix on one device: a second pass aligns into device memory again and selects there */
+		verb("Neighbors: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
+		if (!sa_hip_neighbors(store.in, &sc, o.neighbors, nb_index, nb_score)) {
+			err("%s", sa_last_error());
+			return 1;
+		}
+		nb_done = nb_second_pass = true;
+		t_select = sa_hip_last_neighbors_seconds();
+		stamp("sa_hip_neighbors returned");
+	}
+	if (o.neighbors && !o.no_write) {
+		t0 = now();
+		if (sa_host_write_neighbors(o.output, &store, o.neighbors, nb_index, nb_score, o.neighbors_only ? 1 : 0)) {
+			err("%s", sa_host_error());
+			return 1;
+		}
+		t_out += now() - t0;
+		stamp("neighbors written");
+	}
 	if (o.benchmark) { /* -B: src/util/benchmark.c:50-64 */
 		const double total = t_in + t_filter + t_align + t_out;
 		printf("Timing breakdown:\n  Input: %.3f sec\n  Filter: %.3f sec\n  Alignment: %.3f sec\n  Output: %.3f sec\n"
@@ -549,14 +635,20 @@ int main(int argc, char **argv)
 		printf("  (device set-up and upload, outside the phases as in the reference: %.3f sec)\n", t_setup);
 		printf("  (schedule: %s)\n", device_deflate ? (o.compression ? "column blocks into device memory, their tiles deflated on the device and written meanwhile"
 								       : "column blocks into device memory, their tiles delivered as HDF5 chunks meanwhile")
-				       : schedule == 2
+				       : o.neighbors_only ? "the packed matrix stays in device memory, only the neighbors come back"
+			       : schedule == 2
 					       ? "tiles dealt over the devices, RCCL all-gather of the dense shares, placement on every device"
 					       : "every device delivers its slice of the packed index straight into the host matrix");
+		if (o.neighbors)
+			printf("  (neighbor selection on the device, K = %d: %.6f sec%s)\n", o.neighbors, t_select,
+			       nb_second_pass ? ", after a second alignment pass into device memory" : "");
 		printf("Alignments per second: %.2f\n", t_align > 0 ? (double)pairs / t_align : 0.0);
 	}
 	if (pinned)
 		sa_hip_host_unregister(out.matrix);
 	sa_host_matrix_free(out.matrix, n, out.triangular);
+	free(nb_index);
+	free(nb_score);
 	sa_host_store_free(&store);
 	stamp("released");
 	/* everything is written and closed: leave without the runtime's teardown (device reset, queue and signal

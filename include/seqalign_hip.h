@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -239,6 +239,30 @@ double sa_zjob_align_seconds(const sa_zjob *job);
 void sa_zjob_destroy(sa_zjob *job);
 sa_zjob *sa_hip_tiles_begin(struct sa_input in, const struct sa_scoring *sc, size_t chunk_dim, int level);
 
+/* ---- nearest neighbours: the k best partners of every sequence, selected on the device ---------------------------
+ * No reference counterpart: the reference delivers the N x N matrix, and whoever clusters, builds a graph or looks up
+ * nearest hits sorts every row of it on the host.  The scores sit in device memory when the alignment ends; selecting
+ * there reads them once and returns N x k indices and N x k scores.
+ * Contract: the candidates of sequence r are all c != r with score(r, c), the symmetric matrix entry (the diagonal is not a
+ * candidate); larger is better for all three methods.  Order: score DESCENDING, then index c ASCENDING.  Row r of the
+ * result holds the first k candidates in that order: index[r * k + t], score[r * k + t], t = 0 .. k - 1.  The tie rule is
+ * part of the contract: the same store and scoring give the same bytes run after run.
+ * 1 <= k <= min(N - 1, SA_HIP_NEIGHBORS_MAX); anything else is an error through sa_last_error(). */
+#define SA_HIP_NEIGHBORS_MAX 64
+/* device-resident: d_packed = whole packed matrix of ctx's store; d_index, d_score: N*k int32 each, device memory.
+ * Asynchronous on `stream`.  Needs no scratch memory. */
+int sa_ctx_neighbors(sa_ctx *ctx, const int32_t *d_packed, int32_t k, int32_t *d_index, int32_t *d_score, void *stream);
+/* one call, host in / host out: align into device memory, select, copy back 2*N*k ints.  The matrix never leaves the
+ * device and no host matrix exists.  One device (the first).  Fails cleanly when the packed matrix does not fit.
+ * sa_hip_last_align_seconds() then tells the device time of the alignment inside it. */
+bool sa_hip_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score);
+/* on a tile job whose device holds the finished packed matrix.  For sa_hip_tiles_begin on one device: after
+ * sa_zjob_next has returned 0.  For sa_zjob_create with d_packed: any time.  Host arrays out.  Non-zero + sa_last_error
+ * when the job does not hold the whole matrix on one device (several devices, SA_HIP_TILES_SPLIT > 1, a d_full job). */
+int sa_zjob_neighbors(sa_zjob *job, int32_t k, int32_t *index, int32_t *score);
+/* device time (seconds) of the selection kernel in the last successful sa_hip_neighbors / sa_zjob_neighbors call */
+double sa_hip_last_neighbors_seconds(void);
+
 /* ---- pair-space planning (host only, no device needed) -------------------
  * DP cells (sum of len_i*len_j) of the packed pair range [start, start+count),
  * the numerator of GCUPS; -1 on a bad range. */
@@ -275,7 +299,8 @@ const char *sa_method_name(int method);   /* long alias, e.g. "Gotoh"       */
 int sa_method_gap_kind(int method);       /* enum sa_gap_kind               */
 
 /* ---- misc ---------------------------------------------------------------- */
-/* Seconds the launch/copy loop of the last successful sa_hip_align() took: the phase the reference
+/* Seconds the launch/copy loop of the last successful sa_hip_align() took (after sa_hip_neighbors: the device time of
+ * its alignment): the phase the reference
  * brackets with bench_align_start()/bench_align_end() (src/interface/seqalign_cuda.c:182,292 --
  * uploads, allocations and context set-up are outside it, the device->host copies inside). */
 double sa_hip_last_align_seconds(void);

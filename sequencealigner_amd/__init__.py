@@ -32,6 +32,8 @@ from .binding import (  # noqa: F401
     hip_align,
     hip_filter,
     hip_memory,
+    hip_neighbors,
+    last_neighbors_seconds,
     library_path,
     load_library,
     matrix_names,
@@ -42,5 +44,5 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "AlignError", "Context", "PinnedMatrix", "Scoring", "SequenceStore", "device_count", "device_name", "last_align_breakdown", "last_align_path", "last_align_seconds", "hip_align", "hip_filter",
-    "hip_memory", "library_path", "load_library", "matrix_names", "method_names", "pair_count", "set_progress",
+    "hip_memory", "hip_neighbors", "last_neighbors_seconds", "library_path", "load_library", "matrix_names", "method_names", "pair_count", "set_progress",
 ]

@@ -15,6 +15,7 @@ _LIB_PATH = pathlib.Path(__file__).resolve().parent / "lib" / "libseqalign_hip.s
 _lib: Optional[C.CDLL] = None
 
 LUT_SIZE = 128
+NEIGHBORS_MAX = 64  # SA_HIP_NEIGHBORS_MAX
 SUB_DIM = 24
 SCORE_MIN = -(1 << 30)  # reference src/bio/align.h:19
 
@@ -54,6 +55,7 @@ ABI_SYMBOLS = (
     "sa_ctx_share_elems", "sa_ctx_align_share", "sa_ctx_place_shares", "sa_hip_last_align_breakdown", "sa_ctx_leave_room", "sa_hip_set_progress",
     "sa_hip_last_align_path",
     "sa_zjob_create", "sa_zjob_destroy", "sa_zjob_tiles_per_row", "sa_zjob_tile_row", "sa_zjob_stats", "sa_zjob_next", "sa_zjob_align_seconds", "sa_hip_tiles_begin",
+    "sa_ctx_neighbors", "sa_hip_neighbors", "sa_zjob_neighbors", "sa_hip_last_neighbors_seconds",
 )
 
 
@@ -176,6 +178,13 @@ def load_library() -> C.CDLL:
     lib.sa_zjob_align_seconds.restype = C.c_double
     lib.sa_hip_tiles_begin.argtypes = [_Input, C.POINTER(_Scoring), C.c_size_t, C.c_int]
     lib.sa_hip_tiles_begin.restype = C.c_void_p
+    lib.sa_ctx_neighbors.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_neighbors.restype = C.c_int
+    lib.sa_hip_neighbors.argtypes = [_Input, C.POINTER(_Scoring), C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_hip_neighbors.restype = C.c_bool
+    lib.sa_zjob_neighbors.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_zjob_neighbors.restype = C.c_int
+    lib.sa_hip_last_neighbors_seconds.restype = C.c_double
     _lib = lib
     return lib
 
@@ -393,6 +402,26 @@ def hip_align(store: SequenceStore, scoring: Scoring, triangular: bool = False, 
     return matrix if triangular else matrix.reshape(n, n)
 
 
+def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int) -> tuple[np.ndarray, np.ndarray]:
+    """sa_hip_neighbors: the k best partners of every sequence, selected on the device -- (index, score), two (N, k) int32
+    arrays; row r lists the c != r by score descending, then index ascending.  The matrix never leaves the device.
+    1 <= k <= min(N - 1, NEIGHBORS_MAX)."""
+    n, k = store.num, int(k)
+    if not -2**31 <= k < 2**31:
+        raise AlignError(f"k = {k} is not an int32")
+    rows = max(n, 1) * max(min(k, NEIGHBORS_MAX), 1)
+    index, score = np.empty(rows, np.int32), np.empty(rows, np.int32)
+    sc = scoring._as_c()
+    if not load_library().sa_hip_neighbors(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data):
+        raise AlignError(_err())
+    return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k)
+
+
+def last_neighbors_seconds() -> float:
+    """device time of the selection kernel in the last hip_neighbors / DeflateJob.neighbors call"""
+    return float(load_library().sa_hip_last_neighbors_seconds())
+
+
 class PinnedMatrix:
     """A host result matrix page-locked once (what a C host does in output_load with sa_hip_host_register), so that
     repeated deliveries into it are pure DMA / direct stores.  `.array` is the flat int32 numpy view.
@@ -543,6 +572,13 @@ class Context:
         if self._lib.sa_ctx_expand_full(self._h, C.c_void_p(d_packed_ptr), C.c_void_p(d_full_ptr), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def neighbors(self, d_packed_ptr: int, k: int, d_index_ptr: int, d_score_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_neighbors: from the whole packed device matrix of this store, the k best partners of every sequence into
+        the device arrays d_index / d_score (N * k int32 each), asynchronously on `stream`"""
+        if self._lib.sa_ctx_neighbors(self._h, C.c_void_p(d_packed_ptr), int(k), C.c_void_p(d_index_ptr), C.c_void_p(d_score_ptr),
+                                      C.c_void_p(stream)):
+            raise AlignError(_err())
+
     def timing(self, enable: bool) -> None:
         self._lib.sa_ctx_timing(self._h, int(enable))
 
@@ -570,6 +606,7 @@ class DeflateJob:
         if not self._h:
             raise AlignError(_err())
         self.tiles_per_row = int(self._lib.sa_zjob_tiles_per_row(self._h))
+        self.num = int(num)
 
     @classmethod
     def begin(cls, store: "SequenceStore", scoring: "Scoring", chunk_dim: int, level: int = 6) -> "DeflateJob":
@@ -604,6 +641,16 @@ class DeflateJob:
         if self._lib.sa_zjob_tile_row(self._h, int(row), ptrs, sizes):
             raise AlignError(_err())
         return [C.string_at(ptrs[t], sizes[t]) for t in range(self.tiles_per_row)]
+
+    def neighbors(self, k: int) -> tuple[np.ndarray, np.ndarray]:
+        """sa_zjob_neighbors: (index, score), two (N, k) int32 arrays, from the finished packed matrix this job's device
+        holds -- after next() has returned [] for a begin() job; raises when the matrix is dealt over several jobs"""
+        n, k = self.num, int(k)
+        rows = max(n, 1) * max(min(k, NEIGHBORS_MAX), 1)
+        index, score = np.empty(rows, np.int32), np.empty(rows, np.int32)
+        if self._lib.sa_zjob_neighbors(self._h, k, index.ctypes.data, score.ctypes.data):
+            raise AlignError(_err())
+        return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k)
 
     def stats(self) -> dict:
         e, c, r, o = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()

@@ -421,6 +421,71 @@ extern "C" bool sa_hip_align(struct sa_input in, struct sa_output out, const str
 	return sa_guard("sa_hip_align", false, [&] { return align_impl(in, out, sc); });
 }
 
+/* ---- sa_hip_neighbors: align into device memory, select there, return N x k indices and scores ---------------------- */
+static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score)
+{
+	if (!sc || !index || !score) {
+		sa_set_error("sa_hip_neighbors: null argument");
+		return false;
+	}
+	if (sa_hip_device_count() <= 0) {
+		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
+		return false;
+	}
+	if (!sa_neighbors_check("sa_hip_neighbors", in.num, k))
+		return false;
+	struct Run { /* (released whatever way the function is left) */
+		sa_ctx *ctx = nullptr;
+		int32_t *d_packed = nullptr;
+		hipStream_t stream = nullptr;
+		hipEvent_t e0 = nullptr, e1 = nullptr;
+		~Run()
+		{
+			if (stream) {
+				(void)hipStreamSynchronize(stream);
+				(void)hipStreamDestroy(stream);
+			}
+			if (e0)
+				(void)hipEventDestroy(e0);
+			if (e1)
+				(void)hipEventDestroy(e1);
+			(void)hipFree(d_packed);
+			if (ctx)
+				sa_ctx_destroy(ctx);
+		}
+	} run;
+	run.ctx = sa_ctx_create(0, in, sc);
+	if (!run.ctx)
+		return false;
+	const int64_t pairs = run.ctx->pairs;
+	SA_HIP_CHECK(hipSetDevice(0), return false);
+	if (hipMalloc(&run.d_packed, sizeof(int32_t) * (size_t)pairs) != hipSuccess) {
+		(void)hipGetLastError();
+		run.d_packed = nullptr;
+		sa_set_error("sa_hip_neighbors: the packed matrix of %d sequences (%.2f GiB) does not fit the device's memory", in.num,
+			     (double)pairs * 4.0 / (double)(1 << 30));
+		return false;
+	}
+	SA_HIP_CHECK(hipStreamCreateWithFlags(&run.stream, hipStreamNonBlocking), return false);
+	SA_HIP_CHECK(hipEventCreate(&run.e0), return false);
+	SA_HIP_CHECK(hipEventCreate(&run.e1), return false);
+	SA_HIP_CHECK(hipEventRecord(run.e0, run.stream), return false);
+	if (sa_ctx_align_range(run.ctx, 0, pairs, run.d_packed, run.stream) != 0)
+		return false;
+	SA_HIP_CHECK(hipEventRecord(run.e1, run.stream), return false);
+	if (!sa_neighbors_to_host(run.d_packed, in.num, k, index, score, run.stream))
+		return false;
+	float ms = 0.f;
+	SA_HIP_CHECK(hipEventElapsedTime(&ms, run.e0, run.e1), return false);
+	g_last_align_seconds.store((double)ms * 1e-3);
+	return true;
+}
+
+extern "C" bool sa_hip_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score)
+{
+	return sa_guard("sa_hip_neighbors", false, [&] { return neighbors_impl(in, sc, k, index, score); });
+}
+
 extern "C" int sa_hip_last_align_path(void) { return g_last_align_path.load(); }
 
 extern "C" int sa_hip_last_align_breakdown(double *ms, int n)

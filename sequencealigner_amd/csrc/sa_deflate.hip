@@ -1255,6 +1255,35 @@ extern "C" double sa_zjob_align_seconds(const sa_zjob *z)
 	});
 }
 
+/* The k best partners of every sequence from the job's packed matrix (sa_neighbors.hip), in order behind whatever the job
+ * has on its stream.  Only a job that holds the WHOLE matrix on one device can answer: a walk dealt over several jobs
+ * (several devices, SA_HIP_TILES_SPLIT) has every column block on its own device, and a d_full job has no packed index. */
+extern "C" int sa_zjob_neighbors(sa_zjob *z, int32_t k, int32_t *index, int32_t *score)
+{
+	return sa_guard("sa_zjob_neighbors", 1, [&]() -> int {
+		if (!z || !index || !score) {
+			sa_set_error("sa_zjob_neighbors: null argument");
+			return 1;
+		}
+		if (!z->peers.empty()) {
+			sa_set_error("sa_zjob_neighbors: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+			return 1;
+		}
+		if (!z->d_packed) {
+			sa_set_error("sa_zjob_neighbors: the job walks a full matrix; the selection reads the packed index");
+			return 1;
+		}
+		if (z->shells && z->next_batch < zjob_batches(z)) {
+			sa_set_error("sa_zjob_neighbors: the walk is not finished (sa_zjob_next has not returned 0 yet)");
+			return 1;
+		}
+		if (!sa_neighbors_check("sa_zjob_neighbors", z->num, k))
+			return 1;
+		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
+		return sa_neighbors_to_host(z->d_packed, z->num, k, index, score, z->stream) ? 0 : 1;
+	});
+}
+
 /* one device's part of a walk in shells: context, the packed matrix (whole: a block's place in it is its own), a job over
  * the column blocks `first`, `first + step`, ...; the first two of them are on their way when this returns */
 static sa_zjob *zjob_begin_on(int device, struct sa_input in, const struct sa_scoring *sc, size_t chunk_dim, int level, int first, int step)

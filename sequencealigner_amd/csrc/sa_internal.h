@@ -110,4 +110,10 @@ hipError_t sa_launch_expand_shell(const int32_t *packed, int64_t pbase, int32_t 
 				  hipStream_t s);
 hipError_t sa_launch_widen16(const int16_t *src, int32_t *dst, int64_t count, hipStream_t s);
 
+/* nearest neighbours (sa_neighbors.hip): the k best partners of every row of a packed device matrix */
+bool sa_neighbors_check(const char *who, int64_t num, int32_t k); /* 1 <= k <= min(num - 1, SA_HIP_NEIGHBORS_MAX), or sa_set_error */
+hipError_t sa_launch_neighbors(const int32_t *packed, int32_t num, int32_t k, int32_t *index, int32_t *score, hipStream_t s);
+/* ... into host arrays, in order on `s`, which is synchronised; the kernel's device time goes to sa_hip_last_neighbors_seconds */
+bool sa_neighbors_to_host(const int32_t *d_packed, int32_t num, int32_t k, int32_t *index, int32_t *score, hipStream_t s);
+
 #endif /* SA_INTERNAL_H */
