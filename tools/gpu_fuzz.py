@@ -5,6 +5,7 @@ sys.path.insert(0, str(pathlib.Path(__file__).resolve().parents[1]))
 import numpy as np
 import sequencealigner_amd as sa
 from tests.oracle_binding import Oracle
+from tests import extremal
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -23,8 +24,12 @@ while time.time() - t0 < budget:
         gaps = dict(gap_pen=int(rng.choice([0, 1, 2, 3, 4, 5, 8, 12, 20, 40, 57, 60, 100])))
     else:
         gaps = dict(gap_open=int(rng.choice([0, 1, 2, 5, 10, 11, 12, 16, 25, 60, 120])), gap_extend=int(rng.choice([0, 1, 2, 3, 5, 10, 20])))
+    try:
+        sc = sa.Scoring.from_names(method, matrix, **gaps)
+    except Exception:
+        continue
     n = int(rng.integers(2, 400))
-    regime = int(rng.integers(0, 8))
+    regime = int(rng.integers(0, 9))
     if regime == 0:
         lens = rng.integers(1, 10, n)
     elif regime == 1:
@@ -42,16 +47,17 @@ while time.time() - t0 < budget:
         m = int(rng.choice([2, 3, 5, 8, 14, 15, 16, 31, 63]))
         nn = min(n, 150)
         lens = np.where(rng.random(nn) < 0.5, m + rng.integers(0, 3, nn), rng.integers(150, 660, nn))
-    else:
+    elif regime == 5:
         lens = np.where(rng.random(min(n, 80)) < 0.1, rng.integers(1000, 2300, min(n, 80)), rng.integers(1, 150, min(n, 80)))
     alpha = NT if dna else AA
-    seqs = [alpha[rng.integers(0, len(alpha), int(l))].tobytes() for l in lens]
+    if regime == 8:
+        # the edges of the value ranges (tests/extremal.py): homopolymers and two-letter sequences of the scoring's best
+        # residue and worst pair, half of them of a shortest length m or m + 1 -- frame shifts in flight at full gain
+        seqs = extremal.low_complexity(sc, rng, min(n, 160), int(rng.choice(extremal.SHORTEST)))
+    else:
+        seqs = [alpha[rng.integers(0, len(alpha), int(l))].tobytes() for l in lens]
     if rng.random() < 0.15:  # near-duplicates and exact duplicates
         seqs = [seqs[int(rng.integers(0, len(seqs)))] if rng.random() < 0.5 else s for s in seqs]
-    try:
-        sc = sa.Scoring.from_names(method, matrix, **gaps)
-    except Exception:
-        continue
     store = sa.SequenceStore.from_sequences(seqs)
     want = o.align(store, sc, triangular=True)
     got = sa.hip_align(store, sc, triangular=True)
