@@ -738,6 +738,67 @@ int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int
 	return rc;
 }
 
+/* The alignments of the N x k neighbour pairs (include/seqalign_hip.h: sa_hip_alignments), added to the finished file:
+ * /neighbor_alignment_records N x k x 8 I32LE, /neighbor_cigar_offsets N k + 1 I64LE, /neighbor_cigars U32LE. */
+int sa_host_write_alignments(const char *path, const struct sa_host_store *s, int32_t k, const struct sa_aln *records,
+			     const uint32_t *cigar, int64_t runs)
+{
+	if (!path || !s || !records || runs < 0 || (runs > 0 && !cigar))
+		return fail("Alignment data missing");
+	const size_t dim = (size_t)s->in.num;
+	if (k < 1 || k > SA_HIP_NEIGHBORS_MAX || dim < 2 || (size_t)k > dim - 1)
+		return fail("Neighbor count must be between 1 and %d and below the number of sequences", SA_HIP_NEIGHBORS_MAX);
+	const size_t np = dim * (size_t)k;
+	int32_t *fields = malloc(sizeof(int32_t) * 8 * np);
+	int64_t *offs = malloc(sizeof(int64_t) * (np + 1));
+	if (!fields || !offs) {
+		free(fields);
+		free(offs);
+		return fail("Out of memory allocating alignment records");
+	}
+	for (size_t t = 0; t < np; t++) {
+		const struct sa_aln *r = records + t;
+		const int32_t f[8] = { r->score, r->a_begin, r->a_end, r->b_begin, r->b_end, r->columns, r->identities, r->cigar_len };
+		memcpy(fields + 8 * t, f, sizeof(f));
+		offs[t] = r->cigar_off;
+	}
+	offs[np] = runs;
+	hid_t fapl = H5Pcreate(H5P_FILE_ACCESS), file;
+	H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
+	H5Pset_alignment(fapl, 4096, 4096);
+	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
+	H5Pclose(fapl);
+	if (file < 0) {
+		free(fields);
+		free(offs);
+		return fail("Failed to open HDF5 file: %s", path);
+	}
+	const uint32_t none = 0;
+	const struct {
+		const char *name;
+		int rank;
+		hsize_t dims[3];
+		hid_t file_type, mem_type;
+		const void *data;
+	} sets[3] = { { "/neighbor_alignment_records", 3, { dim, (hsize_t)k, 8 }, H5T_STD_I32LE, H5T_NATIVE_INT32, fields },
+		      { "/neighbor_cigar_offsets", 1, { np + 1, 0, 0 }, H5T_STD_I64LE, H5T_NATIVE_INT64, offs },
+		      { "/neighbor_cigars", 1, { (hsize_t)runs, 0, 0 }, H5T_STD_U32LE, H5T_NATIVE_UINT32, runs ? (const void *)cigar : &none } };
+	int rc = 0;
+	for (int d = 0; d < 3 && !rc; d++) {
+		hid_t space = H5Screate_simple(sets[d].rank, sets[d].dims, NULL);
+		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || (sets[d].dims[0] && H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
+			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
+		if (set >= 0)
+			H5Dclose(set);
+		H5Sclose(space);
+	}
+	H5Fclose(file);
+	free(fields);
+	free(offs);
+	return rc;
+}
+
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder
  * when `compression` > 0, the raw tiles when 0.  Same file, dataset, chunk shape and filter pipeline as sa_host_write_hdf5 --
  * the tiles go to H5Dwrite_chunk as they are, tile row after tile row. */

@@ -78,6 +78,11 @@ int sa_host_write_hdf5_streams(const char *path, const struct sa_host_store *s, 
  * file with /sequences and the two, no /similarity_matrix (--neighbors-only). */
 int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int32_t k, const int32_t *index, const int32_t *score,
 			    int create);
+/* --alignments: /neighbor_alignment_records (N x k x 8 int32: the fields of struct sa_aln up to cigar_len),
+ * /neighbor_cigar_offsets (N k + 1 int64: entry t = cigar_off of record t, row-major; the last = `runs`) and
+ * /neighbor_cigars (`runs` uint32), added to the file at `path` (which sa_host_write_neighbors has written to). */
+int sa_host_write_alignments(const char *path, const struct sa_host_store *s, int32_t k, const struct sa_aln *records,
+			     const uint32_t *cigar, int64_t runs);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,8 @@
  *   added     --column N  --no-header   (non-interactive answers to the reference's DSV column prompt)
  *             -k/--neighbors K  --neighbors-only   (the K best partners of every sequence, selected on the device:
  *             /neighbor_indices and /neighbor_scores; with --neighbors-only no /similarity_matrix at all)
- * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> -B report.
+ *             --alignments   (with -k: the N x K pairs (r, neighbor) traced back on the device, records and CIGARs)
+ * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
 #define _GNU_SOURCE
@@ -94,6 +95,7 @@ struct options {
 	int dsv_column, dsv_has_header;
 	int neighbors; /* -k: 0 = not given */
 	bool neighbors_only;
+	bool alignments; /* --alignments: the N x K neighbour pairs traced back */
 };
 
 static void usage(const char *argv0)
@@ -123,6 +125,11 @@ static void usage(const char *argv0)
 	       "  -k, --neighbors K        Also write the K best partners of every sequence [1-64]:\n"
 	       "                           /neighbor_indices and /neighbor_scores (score descending, index ascending)\n"
 	       "      --neighbors-only     With -k: no /similarity_matrix, the matrix never leaves the device\n"
+	       "      --alignments         With -k: align every sequence with its K neighbors on the device and write\n"
+	       "                           /neighbor_alignment_records (N x K x 8: score, a_begin, a_end, b_begin, b_end,\n"
+	       "                           columns, identities, cigar_len; a = the sequence, b = its neighbor),\n"
+	       "                           /neighbor_cigar_offsets (N*K + 1) and /neighbor_cigars (runs: length << 4 | op,\n"
+	       "                           op 0 = M a residue of each, 1 = I of a only, 2 = D of b only)\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -154,7 +161,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "no-write", 'W', false }, { "no-progress", 'P', false }, { "no-detail", 'D', false },
 		     { "force-proceed", 'F', false }, { "quiet", 'Q', false }, { "verbose", 'V', false },
 		     { "help", 'h', false }, { "column", 1, true }, { "no-header", 2, false },
-		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { NULL, 0, false } };
+		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { "alignments", 4, false }, { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -262,6 +269,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 				o->neighbors = (int)v;
 				break;
 			case 3: o->neighbors_only = true; break;
+			case 4: o->alignments = true; break;
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -340,6 +348,8 @@ int main(int argc, char **argv)
 		ok = (err("Missing required option: -o, --output"), false);
 	if (ok && o.neighbors_only && !o.neighbors)
 		ok = (err("Option --neighbors-only requires -k, --neighbors"), false);
+	if (ok && o.alignments && !o.neighbors)
+		ok = (err("Option --alignments requires -k, --neighbors"), false);
 	if (ok && sa_matrix_load(o.matrix, sc.lut, sc.sub))
 		ok = (err("Invalid substitution matrix name"), false);
 	if (ok && (sc.method = sa_method_parse(o.align)) < 0)
@@ -627,6 +637,40 @@ int main(int argc, char **argv)
 		t_out += now() - t0;
 		stamp("neighbors written");
 	}
+	double t_trace = 0.0;
+	long long trace_runs = 0;
+	if (o.alignments) {
+		/* the N x K pairs (r, neighbor_indices[r][t]), row-major: traced back on the device (include/seqalign_hip.h) */
+		const size_t np = (size_t)store.in.num * (size_t)o.neighbors;
+		int32_t *pa = malloc(sizeof(int32_t) * np);
+		if (!pa) {
+			err("Out of memory allocating alignment pairs");
+			return 1;
+		}
+		for (size_t t = 0; t < np; t++)
+			pa[t] = (int32_t)(t / (size_t)o.neighbors);
+		sa_alns *alns = sa_hip_alignments(store.in, &sc, pa, nb_index, (int64_t)np);
+		free(pa);
+		if (!alns) {
+			err("%s", sa_last_error());
+			return 1;
+		}
+		t_trace = sa_hip_last_alignments_seconds(); /* (reported by itself: the Alignment phase stays the all-vs-all scores) */
+		stamp("sa_hip_alignments returned");
+		int64_t runs = 0;
+		const uint32_t *cigar = sa_alns_cigar(alns, &runs);
+		trace_runs = (long long)runs;
+		if (!o.no_write) {
+			t0 = now();
+			if (sa_host_write_alignments(o.output, &store, o.neighbors, sa_alns_records(alns), cigar, runs)) {
+				err("%s", sa_host_error());
+				return 1;
+			}
+			t_out += now() - t0;
+			stamp("alignments written");
+		}
+		sa_alns_destroy(alns);
+	}
 	if (o.benchmark) { /* -B: src/util/benchmark.c:50-64 */
 		const double total = t_in + t_filter + t_align + t_out;
 		printf("Timing breakdown:\n  Input: %.3f sec\n  Filter: %.3f sec\n  Alignment: %.3f sec\n  Output: %.3f sec\n"
@@ -642,6 +686,9 @@ int main(int argc, char **argv)
 		if (o.neighbors)
 			printf("  (neighbor selection on the device, K = %d: %.6f sec%s)\n", o.neighbors, t_select,
 			       nb_second_pass ? ", after a second alignment pass into device memory" : "");
+		if (o.alignments)
+			printf("  (alignments of the %lld neighbor pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
+			       (long long)store.in.num * o.neighbors, t_trace, trace_runs);
 		printf("Alignments per second: %.2f\n", t_align > 0 ? (double)pairs / t_align : 0.0);
 	}
 	if (pinned)

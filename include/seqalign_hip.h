@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors and *_alignments calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -262,6 +262,70 @@ bool sa_hip_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k
 int sa_zjob_neighbors(sa_zjob *job, int32_t k, int32_t *index, int32_t *score);
 /* device time (seconds) of the selection kernel in the last successful sa_hip_neighbors / sa_zjob_neighbors call */
 double sa_hip_last_neighbors_seconds(void);
+
+/* ---- alignments for chosen pairs: traceback on the device, run-length CIGARs ----------------------------------------
+ * No reference counterpart: the reference keeps scores only.  For an explicit list of pairs (a[t], b[t]) of one store,
+ * a != b, any order, duplicates allowed (the natural list: the N x k neighbours), the device repeats the exact s32 sweep of
+ * the pair, records every cell's decision in scratch memory, walks the decisions back and returns one record and one CIGAR
+ * per pair.
+ *
+ * CIGAR: uint32 runs, BAM style, len << 4 | op; SA_ALN_M: a residue of each sequence, SA_ALN_I: a residue of a only,
+ * SA_ALN_D: a residue of b only.  Runs go from the start of the alignment to its end; adjacent runs differ in op.
+ *
+ * Orientation: the library computes in the reference's orientation -- lo = min(a, b) is the row sequence, hi = max(a, b) the
+ * column sequence, the substitution matrix indexed as the score kernels index it -- so `score` equals the similarity-matrix
+ * entry of the pair even for a matrix that is not symmetric.  For a > b the result is mirrored on output: I <-> D, spans
+ * swapped.
+ *
+ * Tie rule (part of the contract; the same input gives the same bytes), canonical orientation: r indexes rows (lo),
+ * c columns (hi); H / M, X (gap_x: from the left, consumes a residue of hi) and Y (gap_y: from above, consumes a residue
+ * of lo) are the reference's tables, border cells included with the values src/bio/method/nw.c:14-20, ga.c:23-38 and
+ * sw.c:18-30 give them.
+ *   NW     start at (m, n).  At (r, c): r > 0 && c > 0 && H[r][c] == H[r-1][c-1] + S: diagonal; else r > 0 &&
+ *          H[r][c] == H[r-1][c] + g: up; else left.  Stop at (0, 0).
+ *   Gotoh  three states, start in M at (m, n).  M, not at the origin: r > 0 && c > 0 && M[r][c] == M[r-1][c-1] + S: diagonal;
+ *          else M[r][c] == X[r][c]: enter state X at this cell; else enter state Y.  X at (r, c): emit a left step; then
+ *          X[r][c] == M[r][c-1] + open: state M at (r, c-1) (open wins ties), else state X at (r, c-1).  Y: the same, upwards.
+ *   SW     end cell: the cell with M == best of smallest r, then smallest c.  best == 0: the alignment is empty (cigar_len
+ *          0, columns 0, all four span fields 0).  Otherwise walk as Gotoh, but in state M the first test is M[r][c] == 0:
+ *          stop.  The spans are where the walk started and stopped.
+ * (For every scoring a context accepts the border values leave no choice: along row 0 the walk goes left, along column 0
+ * up; SW stops on a border.)
+ *
+ * What "the alignment has this score" means: the sum of S over the M columns plus, per gap run of length L, NW: L g;
+ * Gotoh and SW: open + (L - 1) max(open, extend) -- the reference's recurrence lets a gap be re-opened from `match`, and
+ * scorings with |open| < |extend| are accepted.  Adjacent I and D runs each pay their own open.
+ *
+ * Device memory: a pair needs one byte per cell of len_lo x 64 ceil(len_hi / 64) for the decisions; a call sorts its pairs
+ * by that size and runs them in batches sized from the free device memory (SA_HIP_TRACE_BATCH_BYTES caps a batch).  Any
+ * lengths the store accepts work.  A context runs one such call at a time, and not beside sa_ctx_align_range of the same
+ * context (they share its strip-boundary scratch). */
+enum { SA_ALN_M = 0, SA_ALN_I = 1, SA_ALN_D = 2 };
+struct sa_aln {
+	int32_t score;                  /* == the similarity-matrix entry of (a, b), always */
+	int32_t a_begin, a_end;         /* half-open residue span of a covered by the alignment */
+	int32_t b_begin, b_end;         /* same for b; NW / Gotoh: whole sequences */
+	int32_t columns;                /* alignment length = sum of all run lengths */
+	int32_t identities;             /* M columns whose two residue CODES (0..23) are equal */
+	int32_t cigar_len;              /* number of runs */
+	int64_t cigar_off;              /* first run in the flat cigar array: the sum of cigar_len of the pairs before this one */
+};
+typedef struct sa_alns sa_alns;   /* owns records + flat cigar in host memory */
+/* on a context: host index arrays in, host result out.  NULL + sa_last_error for a == b, an index out of range,
+ * npairs < 0; npairs == 0 gives a valid empty result. */
+sa_alns *sa_ctx_alignments(sa_ctx *ctx, const int32_t *a, const int32_t *b, int64_t npairs);
+/* one call: sa_ctx_create on the first device + sa_ctx_alignments.  NULL as well for a scoring the context refuses and
+ * when there is no device. */
+sa_alns *sa_hip_alignments(struct sa_input in, const struct sa_scoring *sc, const int32_t *a, const int32_t *b, int64_t npairs);
+const struct sa_aln *sa_alns_records(const sa_alns *alns);          /* npairs records, in the caller's pair order */
+const uint32_t *sa_alns_cigar(const sa_alns *alns, int64_t *runs);  /* flat runs; *runs (may be NULL) = their number */
+int64_t sa_alns_count(const sa_alns *alns);                         /* npairs */
+void sa_alns_destroy(sa_alns *alns);
+/* device time (seconds) of the last successful sa_ctx_alignments / sa_hip_alignments call of this process: fill + walk */
+double sa_hip_last_alignments_seconds(void);
+/* ... and its parts: seconds of the fill kernels, of the walk (walk, scan of cigar_len, compaction), the DP cells filled
+ * and the number of batches the call was cut into.  Any pointer may be NULL. */
+void sa_hip_last_alignments_breakdown(double *fill_seconds, double *walk_seconds, int64_t *cells, int32_t *batches);
 
 /* ---- pair-space planning (host only, no device needed) -------------------
  * DP cells (sum of len_i*len_j) of the packed pair range [start, start+count),

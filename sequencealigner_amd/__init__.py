@@ -19,6 +19,7 @@ Python/CPU fallback: a missing library or device raises.
 """
 from .binding import (  # noqa: F401
     AlignError,
+    Alignments,
     Context,
     DeflateJob,
     PinnedMatrix,
@@ -30,6 +31,9 @@ from .binding import (  # noqa: F401
     last_align_path,
     last_align_seconds,
     hip_align,
+    hip_alignments,
+    last_alignments_breakdown,
+    last_alignments_seconds,
     hip_filter,
     hip_memory,
     hip_neighbors,
@@ -44,5 +48,5 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "AlignError", "Context", "PinnedMatrix", "Scoring", "SequenceStore", "device_count", "device_name", "last_align_breakdown", "last_align_path", "last_align_seconds", "hip_align", "hip_filter",
-    "hip_memory", "hip_neighbors", "last_neighbors_seconds", "library_path", "load_library", "matrix_names", "method_names", "pair_count", "set_progress",
+    "hip_memory", "hip_neighbors", "Alignments", "hip_alignments", "last_alignments_seconds", "last_alignments_breakdown", "last_neighbors_seconds", "library_path", "load_library", "matrix_names", "method_names", "pair_count", "set_progress",
 ]

@@ -56,6 +56,8 @@ ABI_SYMBOLS = (
     "sa_hip_last_align_path",
     "sa_zjob_create", "sa_zjob_destroy", "sa_zjob_tiles_per_row", "sa_zjob_tile_row", "sa_zjob_stats", "sa_zjob_next", "sa_zjob_align_seconds", "sa_hip_tiles_begin",
     "sa_ctx_neighbors", "sa_hip_neighbors", "sa_zjob_neighbors", "sa_hip_last_neighbors_seconds",
+    "sa_ctx_alignments", "sa_hip_alignments", "sa_alns_records", "sa_alns_cigar", "sa_alns_count", "sa_alns_destroy",
+    "sa_hip_last_alignments_seconds", "sa_hip_last_alignments_breakdown",
 )
 
 
@@ -185,6 +187,21 @@ def load_library() -> C.CDLL:
     lib.sa_zjob_neighbors.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.sa_zjob_neighbors.restype = C.c_int
     lib.sa_hip_last_neighbors_seconds.restype = C.c_double
+    lib.sa_ctx_alignments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sa_ctx_alignments.restype = C.c_void_p
+    lib.sa_hip_alignments.argtypes = [_Input, C.POINTER(_Scoring), C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sa_hip_alignments.restype = C.c_void_p
+    lib.sa_alns_records.argtypes = [C.c_void_p]
+    lib.sa_alns_records.restype = C.c_void_p
+    lib.sa_alns_cigar.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.sa_alns_cigar.restype = C.c_void_p
+    lib.sa_alns_count.argtypes = [C.c_void_p]
+    lib.sa_alns_count.restype = C.c_int64
+    lib.sa_alns_destroy.argtypes = [C.c_void_p]
+    lib.sa_alns_destroy.restype = None
+    lib.sa_hip_last_alignments_seconds.restype = C.c_double
+    lib.sa_hip_last_alignments_breakdown.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.sa_hip_last_alignments_breakdown.restype = None
     _lib = lib
     return lib
 
@@ -422,6 +439,85 @@ def last_neighbors_seconds() -> float:
     return float(load_library().sa_hip_last_neighbors_seconds())
 
 
+#: struct sa_aln
+ALN_DTYPE = np.dtype([("score", "<i4"), ("a_begin", "<i4"), ("a_end", "<i4"), ("b_begin", "<i4"), ("b_end", "<i4"),
+                      ("columns", "<i4"), ("identities", "<i4"), ("cigar_len", "<i4"), ("cigar_off", "<i8")])
+CIGAR_OPS = "MID"  # SA_ALN_M: a residue of each, SA_ALN_I: of a only, SA_ALN_D: of b only
+
+
+@dataclass
+class Alignments:
+    """What sa_ctx_alignments / sa_hip_alignments return: one record per pair, in the caller's order, and the flat
+    run-length CIGARs (uint32 runs, len << 4 | op; record t owns cigar[cigar_off : cigar_off + cigar_len])."""
+    pairs: np.ndarray    # int32 [P, 2] = (a, b)
+    records: np.ndarray  # ALN_DTYPE [P]
+    cigar: np.ndarray    # uint32, flat
+
+    def runs(self, t: int) -> list[tuple[int, str]]:
+        r = self.records[t]
+        return [(int(w) >> 4, CIGAR_OPS[int(w) & 15]) for w in self.cigar[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["cigar_len"])]]
+
+    def cigar_string(self, t: int) -> str:
+        """e.g. "37M2D61M" ("" for the empty alignment of a Smith-Waterman pair whose best score is 0)"""
+        return "".join(f"{n}{op}" for n, op in self.runs(t))
+
+    def aligned(self, t: int, store: "SequenceStore") -> tuple[str, str]:
+        """the two gapped strings of pair t: the covered residues of a and of b, '-' where the other sequence has one alone"""
+        r = self.records[t]
+        sa, sb = store.sequence(int(self.pairs[t, 0])).decode(), store.sequence(int(self.pairs[t, 1])).decode()
+        i, j, ga, gb = int(r["a_begin"]), int(r["b_begin"]), [], []
+        for n, op in self.runs(t):
+            ga.append(sa[i:i + n] if op != "D" else "-" * n)
+            gb.append(sb[j:j + n] if op != "I" else "-" * n)
+            i += n if op != "D" else 0
+            j += n if op != "I" else 0
+        return "".join(ga), "".join(gb)
+
+
+def _pairs_array(pairs) -> np.ndarray:
+    arr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2) if len(pairs) else np.zeros((0, 2), np.int64)
+    if arr.size and (arr.min() < -2**31 or arr.max() >= 2**31):
+        raise AlignError("pair indices must be int32")
+    return np.ascontiguousarray(arr.astype(np.int32))
+
+
+def _take_alignments(lib, handle, pairs: np.ndarray) -> Alignments:
+    if not handle:
+        raise AlignError(_err())
+    try:
+        n = int(lib.sa_alns_count(handle))
+        runs = C.c_int64(0)
+        cig = lib.sa_alns_cigar(handle, C.byref(runs))
+        rec = lib.sa_alns_records(handle)
+        records = np.frombuffer(C.string_at(rec, n * ALN_DTYPE.itemsize), dtype=ALN_DTYPE).copy() if n else np.zeros(0, ALN_DTYPE)
+        cigar = np.frombuffer(C.string_at(cig, 4 * runs.value), dtype=np.uint32).copy() if runs.value else np.zeros(0, np.uint32)
+    finally:
+        lib.sa_alns_destroy(handle)
+    return Alignments(pairs=pairs, records=records, cigar=cigar)
+
+
+def hip_alignments(store: SequenceStore, scoring: Scoring, pairs) -> Alignments:
+    """sa_hip_alignments: the alignments of the listed pairs (a, b), a != b, any order, duplicates allowed -- traced back
+    on the device.  The contract (orientation, tie rule, what a CIGAR scores) is in include/seqalign_hip.h."""
+    lib = load_library()
+    arr = _pairs_array(pairs)
+    a, b = np.ascontiguousarray(arr[:, 0]), np.ascontiguousarray(arr[:, 1])
+    sc = scoring._as_c()
+    return _take_alignments(lib, lib.sa_hip_alignments(store._as_c(), C.byref(sc), a.ctypes.data, b.ctypes.data, len(arr)), arr)
+
+
+def last_alignments_seconds() -> float:
+    """device time (fill + walk) of the last hip_alignments / Context.alignments call"""
+    return float(load_library().sa_hip_last_alignments_seconds())
+
+
+def last_alignments_breakdown() -> dict:
+    """... and its parts: fill_seconds, walk_seconds, the DP cells filled and the number of batches"""
+    f, w, c, b = C.c_double(0), C.c_double(0), C.c_int64(0), C.c_int32(0)
+    load_library().sa_hip_last_alignments_breakdown(C.byref(f), C.byref(w), C.byref(c), C.byref(b))
+    return {"fill_seconds": f.value, "walk_seconds": w.value, "cells": c.value, "batches": b.value}
+
+
 class PinnedMatrix:
     """A host result matrix page-locked once (what a C host does in output_load with sa_hip_host_register), so that
     repeated deliveries into it are pure DMA / direct stores.  `.array` is the flat int32 numpy view.
@@ -578,6 +674,12 @@ class Context:
         if self._lib.sa_ctx_neighbors(self._h, C.c_void_p(d_packed_ptr), int(k), C.c_void_p(d_index_ptr), C.c_void_p(d_score_ptr),
                                       C.c_void_p(stream)):
             raise AlignError(_err())
+
+    def alignments(self, pairs) -> Alignments:
+        """sa_ctx_alignments: the alignments of the listed pairs of this context's store (see hip_alignments)"""
+        arr = _pairs_array(pairs)
+        a, b = np.ascontiguousarray(arr[:, 0]), np.ascontiguousarray(arr[:, 1])
+        return _take_alignments(self._lib, self._lib.sa_ctx_alignments(self._h, a.ctypes.data, b.ctypes.data, len(arr)), arr)
 
     def timing(self, enable: bool) -> None:
         self._lib.sa_ctx_timing(self._h, int(enable))

@@ -24,6 +24,8 @@ struct SaEnv {
 	int split = 0;   /* SA_HIP_SPLIT=n   : n slices even when fewer devices are visible (testing aid)                */
 	int gather = -1; /* SA_HIP_GATHER=0/1: multi-device path through dense shares + RCCL all-gather (-1: default)    */
 	int tiles_split = 0; /* SA_HIP_TILES_SPLIT=n: sa_hip_tiles_begin deals the column blocks over n jobs on device 0 (testing aid) */
+	/* traceback (sa_traceback.hip) */
+	long long trace_batch_bytes = 0; /* SA_HIP_TRACE_BATCH_BYTES=n : cap on the decision scratch of one batch of pairs (0: from the free device memory) */
 	/* diagnostics */
 	bool verbose = false;             /* SA_HIP_VERBOSE                                                               */
 	bool stamps = false;              /* SA_HIP_STAMPS : per-tile clocks of every launch (synchronous)                */
