@@ -799,6 +799,64 @@ int sa_host_write_alignments(const char *path, const struct sa_host_store *s, in
 	return rc;
 }
 
+/* The score graph as CSR (include/seqalign_hip.h: sa_hip_edges): /edge_offsets N + 1 I64LE, /edge_indices and /edge_scores
+ * E = offsets[N] I32LE each (extent 0 when there is no edge), contiguous.  create = 0: added to the finished file at `path`, whose
+ * other datasets stay as they are; create = 1: a new file with /sequences and these three, no /similarity_matrix.  The arrays
+ * are checked before anything is opened: offsets[0] == 0, offsets non-decreasing, every index in [0, N). */
+int sa_host_write_edges(const char *path, const struct sa_host_store *s, const int64_t *offsets, const int32_t *index, const int32_t *score,
+			int create)
+{
+	if (!path || !s || !offsets)
+		return fail("Edge data missing");
+	const size_t dim = (size_t)s->in.num;
+	if (offsets[0] != 0)
+		return fail("Edge offsets must start at 0");
+	for (size_t r = 0; r < dim; r++)
+		if (offsets[r + 1] < offsets[r])
+			return fail("Edge offsets decrease at row %zu", r);
+	const int64_t count = offsets[dim];
+	if (count > 0 && (!index || !score))
+		return fail("Edge data missing");
+	for (int64_t t = 0; t < count; t++)
+		if (index[t] < 0 || (size_t)index[t] >= dim)
+			return fail("Edge index %d at position %lld is outside the %zu sequences", index[t], (long long)t, dim);
+	hid_t file;
+	if (create) {
+		if (create_with_sequences(path, s, &file))
+			return 1;
+	} else {
+		hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
+		H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
+		H5Pset_alignment(fapl, 4096, 4096);
+		H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
+		H5Pclose(fapl);
+		if (file < 0)
+			return fail("Failed to open HDF5 file: %s", path);
+	}
+	const struct {
+		const char *name;
+		hsize_t extent;
+		hid_t file_type, mem_type;
+		const void *data;
+	} sets[3] = { { "/edge_offsets", (hsize_t)dim + 1, H5T_STD_I64LE, H5T_NATIVE_INT64, offsets },
+		      { "/edge_indices", (hsize_t)count, H5T_STD_I32LE, H5T_NATIVE_INT32, index },
+		      { "/edge_scores", (hsize_t)count, H5T_STD_I32LE, H5T_NATIVE_INT32, score } };
+	int rc = 0;
+	for (int d = 0; d < 3 && !rc; d++) {
+		hid_t space = H5Screate_simple(1, &sets[d].extent, NULL);
+		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || (sets[d].extent && H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
+			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
+		if (set >= 0)
+			H5Dclose(set);
+		H5Sclose(space);
+	}
+	H5Fclose(file);
+	if (rc && create)
+		remove(path);
+	return rc;
+}
+
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder
  * when `compression` > 0, the raw tiles when 0.  Same file, dataset, chunk shape and filter pipeline as sa_host_write_hdf5 --
  * the tiles go to H5Dwrite_chunk as they are, tile row after tile row. */

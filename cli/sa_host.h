@@ -83,6 +83,12 @@ int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int
  * /neighbor_cigars (`runs` uint32), added to the file at `path` (which sa_host_write_neighbors has written to). */
 int sa_host_write_alignments(const char *path, const struct sa_host_store *s, int32_t k, const struct sa_aln *records,
 			     const uint32_t *cigar, int64_t runs);
+/* --min-score: /edge_offsets (N + 1 I64LE), /edge_indices and /edge_scores (E = offsets[N] I32LE each; extent 0 when E = 0),
+ * the CSR arrays of sa_hip_edges / sa_zjob_edges.  `create` as in sa_host_write_neighbors: 0 adds the three datasets to the
+ * finished file at `path`, 1 writes a new file with /sequences and the three (--edges-only).  offsets[0] != 0, decreasing
+ * offsets or an index outside [0, N) give an error, and no file when `create` is set. */
+int sa_host_write_edges(const char *path, const struct sa_host_store *s, const int64_t *offsets, const int32_t *index, const int32_t *score,
+			int create);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,9 @@
  *             -k/--neighbors K  --neighbors-only   (the K best partners of every sequence, selected on the device:
  *             /neighbor_indices and /neighbor_scores; with --neighbors-only no /similarity_matrix at all)
  *             --alignments   (with -k: the N x K pairs (r, neighbor) traced back on the device, records and CIGARs)
- * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> -B report.
+ *             --min-score T  --edges-only   (the score graph: every pair that scores at least T as CSR, built on the device:
+ *             /edge_offsets, /edge_indices and /edge_scores; with --edges-only no /similarity_matrix at all)
+ * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> score graph -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
 #define _GNU_SOURCE
@@ -96,6 +98,8 @@ struct options {
 	int neighbors; /* -k: 0 = not given */
 	bool neighbors_only;
 	bool alignments; /* --alignments: the N x K neighbour pairs traced back */
+	bool has_min_score, edges_only; /* --min-score T: the score graph; --edges-only: nothing else */
+	int32_t min_score;
 };
 
 static void usage(const char *argv0)
@@ -130,6 +134,12 @@ static void usage(const char *argv0)
 	       "                           columns, identities, cigar_len; a = the sequence, b = its neighbor),\n"
 	       "                           /neighbor_cigar_offsets (N*K + 1) and /neighbor_cigars (runs: length << 4 | op,\n"
 	       "                           op 0 = M a residue of each, 1 = I of a only, 2 = D of b only)\n"
+	       "      --min-score T        Also write the score graph, every pair that scores at least T (any 32-bit integer,\n"
+	       "                           negative values included), as CSR over the sequences as written:\n"
+	       "                           /edge_offsets (N + 1), /edge_indices and /edge_scores (row r: the entries\n"
+	       "                           offsets[r] .. offsets[r + 1], columns ascending)\n"
+	       "      --edges-only         With --min-score: no /similarity_matrix, the matrix never leaves the device\n"
+	       "                           (not together with -k)\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -161,7 +171,8 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "no-write", 'W', false }, { "no-progress", 'P', false }, { "no-detail", 'D', false },
 		     { "force-proceed", 'F', false }, { "quiet", 'Q', false }, { "verbose", 'V', false },
 		     { "help", 'h', false }, { "column", 1, true }, { "no-header", 2, false },
-		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { "alignments", 4, false }, { NULL, 0, false } };
+		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { "alignments", 4, false },
+		     { "min-score", 5, true }, { "edges-only", 6, false }, { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -270,6 +281,15 @@ static int parse_args(int argc, char **argv, struct options *o)
 				break;
 			case 3: o->neighbors_only = true; break;
 			case 4: o->alignments = true; break;
+			case 5:
+				if (!parse_long(val, INT32_MIN, INT32_MAX, &v)) {
+					err("Minimum score must be an integer between %d and %d", INT32_MIN, INT32_MAX);
+					return 1;
+				}
+				o->has_min_score = true;
+				o->min_score = (int32_t)v;
+				break;
+			case 6: o->edges_only = true; break;
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -350,6 +370,10 @@ int main(int argc, char **argv)
 		ok = (err("Option --neighbors-only requires -k, --neighbors"), false);
 	if (ok && o.alignments && !o.neighbors)
 		ok = (err("Option --alignments requires -k, --neighbors"), false);
+	if (ok && o.edges_only && !o.has_min_score)
+		ok = (err("Option --edges-only requires --min-score"), false);
+	if (ok && o.edges_only && o.neighbors)
+		ok = (err("Options --edges-only and -k, --neighbors conflict: the neighbors need a pass of their own (use --min-score without --edges-only)"), false);
 	if (ok && sa_matrix_load(o.matrix, sc.lut, sc.sub))
 		ok = (err("Invalid substitution matrix name"), false);
 	if (ok && (sc.method = sa_method_parse(o.align)) < 0)
@@ -410,8 +434,10 @@ int main(int argc, char **argv)
 		info("Filter threshold: %.1f%%", (double)o.filter * 100.0);
 	if (o.neighbors)
 		info("Neighbors: %d per sequence%s", o.neighbors, o.neighbors_only ? " (no similarity matrix)" : "");
+	if (o.has_min_score)
+		info("Score graph: pairs that score at least %d%s", o.min_score, o.edges_only ? " (no similarity matrix)" : "");
 
-	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t0;
+	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t_edges = 0, t0;
 	stamp("options parsed");
 	struct sa_host_store store;
 	t0 = now();
@@ -448,6 +474,8 @@ int main(int argc, char **argv)
 	}
 	int32_t *nb_index = NULL, *nb_score = NULL;
 	bool nb_done = false, nb_second_pass = false;
+	sa_edges *edges = NULL;
+	bool eg_second_pass = false;
 	if (o.neighbors) {
 		nb_index = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
 		nb_score = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
@@ -468,7 +496,8 @@ int main(int argc, char **argv)
 	 * SA_HOST_CPU_DEFLATE=1 keeps zlib at exactly the level asked for (all cores, sa_host_write_hdf5). */
 	const long long npairs = (long long)n * ((long long)n - 1) / 2;
 	const size_t zchunk = sa_host_hdf5_chunk_dim(n);
-	bool device_deflate = !o.no_write && !o.neighbors_only && n > 256 && !getenv("SA_HOST_MATRIX") &&
+	const bool no_matrix = o.neighbors_only || o.edges_only; /* the matrix never leaves the device */
+	bool device_deflate = !o.no_write && !no_matrix && n > 256 && !getenv("SA_HOST_MATRIX") &&
 			      (o.compression > 0 ? !getenv("SA_HOST_CPU_DEFLATE") && !getenv("SA_HOST_SERIAL_DEFLATE")
 						 /* without -z the same walk returns the tiles as they are: H5Dwrite_chunk instead of H5Dwrite's
 						  * gather of every tile out of N-wide rows.  On several devices the plain path stays with sa_hip_align
@@ -483,7 +512,7 @@ int main(int argc, char **argv)
 					       (o.compression >= SA_HIP_Z_PAIR_LEVEL ? row_raw / 2 : 0));
 		stamp("device memory probed (runtime up)");
 	}
-	if (!o.no_write && !device_deflate && !o.neighbors_only) {
+	if (!o.no_write && !device_deflate && !no_matrix) {
 		const size_t full_bytes = sizeof(int32_t) * n * n;
 		const bool tmpf = sa_host_matrix_needs_file(n);
 		out.triangular = tmpf || !sa_hip_memory(full_bytes);
@@ -566,8 +595,36 @@ int main(int argc, char **argv)
 				verb("Neighbors: %s", sa_last_error());
 			}
 		}
+		if (o.has_min_score) {
+			edges = sa_zjob_edges(job, o.min_score);
+			if (edges) {
+				t_edges = sa_hip_last_edges_seconds();
+				verb("Score graph built from the device's finished matrix (no second alignment)");
+			} else {
+				verb("Score graph: %s", sa_last_error());
+			}
+		}
 		sa_zjob_destroy(job);
 		stamp("HDF5 written");
+	} else if (o.edges_only) {
+		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the graph there, copy back 8 N + 8 E bytes */
+		info("Similarity Matrix stays on the device: the pairs that score at least %d are selected there", o.min_score);
+		t0 = now();
+		edges = sa_hip_edges(store.in, &sc, o.min_score);
+		if (!edges) {
+			err("%s", sa_last_error());
+			return 1;
+		}
+		const double call = now() - t0;
+		stamp("sa_hip_edges returned");
+		if (show_progress) {
+			progress_line(1.0, NULL);
+			fputc('\n', stderr);
+			sa_hip_set_progress(NULL, NULL);
+		}
+		t_align = sa_hip_last_align_seconds();
+		t_edges = sa_hip_last_edges_seconds();
+		t_setup = call > t_align + t_edges ? call - t_align - t_edges : 0.0;
 	} else if (o.neighbors_only) {
 		/* no host matrix, no tiles, no matrix transfer: align into device memory, select there, copy back 2 N K ints */
 		info("Similarity Matrix stays on the device: %d neighbors per sequence are selected there", o.neighbors);
@@ -671,6 +728,34 @@ int main(int argc, char **argv)
 		}
 		sa_alns_destroy(alns);
 	}
+	if (o.has_min_score && !edges) {
+		/* as for the neighbours: the matrix of the first pass is not on one device any more */
+		verb("Score graph: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
+		edges = sa_hip_edges(store.in, &sc, o.min_score);
+		if (!edges) {
+			err("%s", sa_last_error());
+			return 1;
+		}
+		eg_second_pass = true;
+		t_edges = sa_hip_last_edges_seconds();
+		stamp("sa_hip_edges returned");
+	}
+	long long edge_count = 0;
+	if (edges) {
+		int64_t count = 0;
+		const int32_t *eg_index = sa_edges_index(edges, &count);
+		edge_count = (long long)count;
+		if (!o.no_write) {
+			t0 = now();
+			if (sa_host_write_edges(o.output, &store, sa_edges_offsets(edges, NULL), eg_index, sa_edges_score(edges), o.edges_only ? 1 : 0)) {
+				err("%s", sa_host_error());
+				return 1;
+			}
+			t_out += now() - t0;
+			stamp("edges written");
+		}
+		sa_edges_destroy(edges);
+	}
 	if (o.benchmark) { /* -B: src/util/benchmark.c:50-64 */
 		const double total = t_in + t_filter + t_align + t_out;
 		printf("Timing breakdown:\n  Input: %.3f sec\n  Filter: %.3f sec\n  Alignment: %.3f sec\n  Output: %.3f sec\n"
@@ -679,6 +764,7 @@ int main(int argc, char **argv)
 		printf("  (device set-up and upload, outside the phases as in the reference: %.3f sec)\n", t_setup);
 		printf("  (schedule: %s)\n", device_deflate ? (o.compression ? "column blocks into device memory, their tiles deflated on the device and written meanwhile"
 								       : "column blocks into device memory, their tiles delivered as HDF5 chunks meanwhile")
+				       : o.edges_only ? "the packed matrix stays in device memory, only the edges come back"
 				       : o.neighbors_only ? "the packed matrix stays in device memory, only the neighbors come back"
 			       : schedule == 2
 					       ? "tiles dealt over the devices, RCCL all-gather of the dense shares, placement on every device"
@@ -689,6 +775,9 @@ int main(int argc, char **argv)
 		if (o.alignments)
 			printf("  (alignments of the %lld neighbor pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
 			       (long long)store.in.num * o.neighbors, t_trace, trace_runs);
+		if (o.has_min_score)
+			printf("  (score graph on the device, min score = %d: %lld edges, %.6f sec%s)\n", o.min_score, edge_count, t_edges,
+			       eg_second_pass ? ", after a second alignment pass into device memory" : "");
 		printf("Alignments per second: %.2f\n", t_align > 0 ? (double)pairs / t_align : 0.0);
 	}
 	if (pinned)

@@ -327,6 +327,43 @@ double sa_hip_last_alignments_seconds(void);
  * and the number of batches the call was cut into.  Any pointer may be NULL. */
 void sa_hip_last_alignments_breakdown(double *fill_seconds, double *walk_seconds, int64_t *cells, int32_t *batches);
 
+/* ---- score graph: every pair at or above a threshold, as CSR, built on the device -------------------------------------
+ * No reference counterpart: the reference delivers the N x N matrix, and whoever clusters it (MCL, connected components /
+ * single linkage, scipy.sparse.csgraph, networkx, igraph) thresholds every element on the host, usually to keep well under 1 %.
+ * Contract: for a store of N sequences and an int32 min_score, entry (r, c) with c != r is an edge iff
+ * score(r, c) >= min_score, score(r, c) the symmetric similarity-matrix entry; the diagonal is never a candidate; larger is
+ * better for all three methods.  The result is the symmetric adjacency in CSR form:
+ *   offsets  int64[N + 1]; offsets[0] = 0, offsets[r + 1] - offsets[r] = degree of r, offsets[N] = E (even: every undirected
+ *            edge appears in both rows)
+ *   index    int32[E]; row r's columns in ASCENDING c
+ *   score    int32[E]; the score of each index entry
+ * Any int32 threshold is valid: at or below the matrix minimum E = N (N - 1); above the maximum the result is valid and empty
+ * (all offsets 0).  The order is part of the contract: the same store, scoring and threshold give the same bytes run after
+ * run -- no position is decided by which workgroup or wave arrives first.  Offsets and every position computed from them are
+ * 64-bit (N = 10^5 can give E near 10^10). */
+/* device-resident, asynchronous on `stream`: d_packed = whole packed matrix of ctx's store; d_offsets: N + 1 int64 of device
+ * memory.  Count and exclusive scan, no host synchronisation, no scratch memory. */
+int sa_ctx_edge_offsets(sa_ctx *ctx, const int32_t *d_packed, int32_t min_score, int64_t *d_offsets, void *stream);
+/* d_offsets as written by sa_ctx_edge_offsets for the SAME d_packed and min_score; d_index, d_score: offsets[N] int32 each.
+ * The two calls are separate so that a device-resident caller can read offsets[N] and allocate exactly E elements. */
+int sa_ctx_edge_fill(sa_ctx *ctx, const int32_t *d_packed, int32_t min_score, const int64_t *d_offsets,
+		     int32_t *d_index, int32_t *d_score, void *stream);
+typedef struct sa_edges sa_edges;   /* owns offsets / index / score in host memory, like sa_alns */
+/* one call, host in / host out: align into device memory, count, read E (8 bytes), allocate 8 E bytes of device memory, fill,
+ * copy back.  The matrix never leaves the device.  One device (the first).  NULL + sa_last_error (the message names N and E)
+ * when the edges, or the packed matrix itself, do not fit; the process goes on working.  sa_hip_last_align_seconds() then
+ * tells the device time of the alignment inside it. */
+sa_edges *sa_hip_edges(struct sa_input in, const struct sa_scoring *sc, int32_t min_score);
+/* on a tile job whose device holds the finished packed matrix: when sa_zjob_neighbors can answer, and refused in the same
+ * cases (the walk is not finished; the matrix is dealt over several jobs; a d_full job). */
+sa_edges *sa_zjob_edges(sa_zjob *job, int32_t min_score);
+const int64_t *sa_edges_offsets(const sa_edges *e, int32_t *num);    /* num + 1 entries; *num (may be NULL) = N */
+const int32_t *sa_edges_index(const sa_edges *e, int64_t *count);    /* *count (may be NULL) = E */
+const int32_t *sa_edges_score(const sa_edges *e);
+void sa_edges_destroy(sa_edges *e);
+/* device time (seconds) of count + scan + fill in the last successful sa_hip_edges / sa_zjob_edges call */
+double sa_hip_last_edges_seconds(void);
+
 /* ---- pair-space planning (host only, no device needed) -------------------
  * DP cells (sum of len_i*len_j) of the packed pair range [start, start+count),
  * the numerator of GCUPS; -1 on a bad range. */

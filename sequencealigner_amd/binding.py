@@ -58,6 +58,8 @@ ABI_SYMBOLS = (
     "sa_ctx_neighbors", "sa_hip_neighbors", "sa_zjob_neighbors", "sa_hip_last_neighbors_seconds",
     "sa_ctx_alignments", "sa_hip_alignments", "sa_alns_records", "sa_alns_cigar", "sa_alns_count", "sa_alns_destroy",
     "sa_hip_last_alignments_seconds", "sa_hip_last_alignments_breakdown",
+    "sa_ctx_edge_offsets", "sa_ctx_edge_fill", "sa_hip_edges", "sa_zjob_edges", "sa_edges_offsets", "sa_edges_index", "sa_edges_score",
+    "sa_edges_destroy", "sa_hip_last_edges_seconds",
 )
 
 
@@ -202,6 +204,23 @@ def load_library() -> C.CDLL:
     lib.sa_hip_last_alignments_seconds.restype = C.c_double
     lib.sa_hip_last_alignments_breakdown.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.sa_hip_last_alignments_breakdown.restype = None
+    lib.sa_ctx_edge_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_edge_offsets.restype = C.c_int
+    lib.sa_ctx_edge_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_edge_fill.restype = C.c_int
+    lib.sa_hip_edges.argtypes = [_Input, C.POINTER(_Scoring), C.c_int32]
+    lib.sa_hip_edges.restype = C.c_void_p
+    lib.sa_zjob_edges.argtypes = [C.c_void_p, C.c_int32]
+    lib.sa_zjob_edges.restype = C.c_void_p
+    lib.sa_edges_offsets.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.sa_edges_offsets.restype = C.c_void_p
+    lib.sa_edges_index.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.sa_edges_index.restype = C.c_void_p
+    lib.sa_edges_score.argtypes = [C.c_void_p]
+    lib.sa_edges_score.restype = C.c_void_p
+    lib.sa_edges_destroy.argtypes = [C.c_void_p]
+    lib.sa_edges_destroy.restype = None
+    lib.sa_hip_last_edges_seconds.restype = C.c_double
     _lib = lib
     return lib
 
@@ -437,6 +456,45 @@ def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int) -> tuple[np.nd
 def last_neighbors_seconds() -> float:
     """device time of the selection kernel in the last hip_neighbors / DeflateJob.neighbors call"""
     return float(load_library().sa_hip_last_neighbors_seconds())
+
+
+def _min_score(min_score) -> int:
+    t = int(min_score)
+    if not -2**31 <= t < 2**31:
+        raise AlignError(f"min_score = {t} is not an int32")
+    return t
+
+
+def _take_edges(lib, handle) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """copies of the three arrays a sa_edges handle owns; the handle is destroyed"""
+    if not handle:
+        raise AlignError(_err())
+    try:
+        num, count = C.c_int32(0), C.c_int64(0)
+        off = lib.sa_edges_offsets(handle, C.byref(num))
+        idx = lib.sa_edges_index(handle, C.byref(count))
+        sco = lib.sa_edges_score(handle)
+        e = count.value
+        offsets = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_int64)), (num.value + 1,)).copy()
+        index = np.ctypeslib.as_array(C.cast(idx, C.POINTER(C.c_int32)), (e,)).copy() if e else np.zeros(0, np.int32)
+        score = np.ctypeslib.as_array(C.cast(sco, C.POINTER(C.c_int32)), (e,)).copy() if e else np.zeros(0, np.int32)
+    finally:
+        lib.sa_edges_destroy(handle)
+    return offsets, index, score
+
+
+def hip_edges(store: SequenceStore, scoring: Scoring, min_score: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """sa_hip_edges: every pair that scores at least min_score, as the symmetric adjacency in CSR form, built on the device --
+    (offsets int64[N + 1], index int32[E], score int32[E]); row r's columns are index[offsets[r]:offsets[r + 1]], ascending.
+    The matrix never leaves the device.  Any int32 threshold is valid."""
+    lib = load_library()
+    sc = scoring._as_c()
+    return _take_edges(lib, lib.sa_hip_edges(store._as_c(), C.byref(sc), _min_score(min_score)))
+
+
+def last_edges_seconds() -> float:
+    """device time of count + scan + fill in the last hip_edges / DeflateJob.edges call"""
+    return float(load_library().sa_hip_last_edges_seconds())
 
 
 #: struct sa_aln
@@ -675,6 +733,20 @@ class Context:
                                       C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def edge_offsets(self, d_packed_ptr: int, min_score: int, d_offsets_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_edge_offsets: from the whole packed device matrix of this store, the CSR offsets (N + 1 int64, device memory)
+        of the pairs that score at least min_score, asynchronously on `stream`; offsets[N] = E"""
+        if self._lib.sa_ctx_edge_offsets(self._h, C.c_void_p(d_packed_ptr), _min_score(min_score), C.c_void_p(d_offsets_ptr),
+                                         C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def edge_fill(self, d_packed_ptr: int, min_score: int, d_offsets_ptr: int, d_index_ptr: int, d_score_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_edge_fill: with the offsets edge_offsets wrote for the same matrix and threshold, the columns (ascending per
+        row) and scores into the device arrays d_index / d_score (E int32 each), asynchronously on `stream`"""
+        if self._lib.sa_ctx_edge_fill(self._h, C.c_void_p(d_packed_ptr), _min_score(min_score), C.c_void_p(d_offsets_ptr),
+                                      C.c_void_p(d_index_ptr), C.c_void_p(d_score_ptr), C.c_void_p(stream)):
+            raise AlignError(_err())
+
     def alignments(self, pairs) -> Alignments:
         """sa_ctx_alignments: the alignments of the listed pairs of this context's store (see hip_alignments)"""
         arr = _pairs_array(pairs)
@@ -753,6 +825,11 @@ class DeflateJob:
         if self._lib.sa_zjob_neighbors(self._h, k, index.ctypes.data, score.ctypes.data):
             raise AlignError(_err())
         return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k)
+
+    def edges(self, min_score: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """sa_zjob_edges: (offsets, index, score) as hip_edges returns them, from the finished packed matrix this job's device
+        holds -- after next() has returned [] for a begin() job; raises when the matrix is dealt over several jobs"""
+        return _take_edges(self._lib, self._lib.sa_zjob_edges(self._h, _min_score(min_score)))
 
     def stats(self) -> dict:
         e, c, r, o = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()

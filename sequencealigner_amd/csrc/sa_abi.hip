@@ -421,7 +421,65 @@ extern "C" bool sa_hip_align(struct sa_input in, struct sa_output out, const str
 	return sa_guard("sa_hip_align", false, [&] { return align_impl(in, out, sc); });
 }
 
-/* ---- sa_hip_neighbors: align into device memory, select there, return N x k indices and scores ---------------------- */
+/* ---- sa_hip_neighbors, sa_hip_edges: align into device memory, select there, return the selection ------------------------- */
+/* the whole packed matrix of `in` in the first device's memory, aligned on a stream of its own between two events */
+struct DeviceRun { /* (released whatever way the caller is left) */
+	sa_ctx *ctx = nullptr;
+	int32_t *d_packed = nullptr;
+	hipStream_t stream = nullptr;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	~DeviceRun()
+	{
+		if (stream) {
+			(void)hipStreamSynchronize(stream);
+			(void)hipStreamDestroy(stream);
+		}
+		if (e0)
+			(void)hipEventDestroy(e0);
+		if (e1)
+			(void)hipEventDestroy(e1);
+		(void)hipFree(d_packed);
+		if (ctx)
+			sa_ctx_destroy(ctx);
+	}
+	/* the alignment is in order on `stream` when this returns true; `who` names the entry point in messages */
+	bool begin(const char *who, struct sa_input in, const struct sa_scoring *sc)
+	{
+		if (sa_hip_device_count() <= 0) {
+			sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
+			return false;
+		}
+		ctx = sa_ctx_create(0, in, sc);
+		if (!ctx)
+			return false;
+		const int64_t pairs = ctx->pairs;
+		SA_HIP_CHECK(hipSetDevice(0), return false);
+		if (hipMalloc(&d_packed, sizeof(int32_t) * (size_t)pairs) != hipSuccess) {
+			(void)hipGetLastError();
+			d_packed = nullptr;
+			sa_set_error("%s: the packed matrix of %d sequences (%.2f GiB) does not fit the device's memory", who, in.num,
+				     (double)pairs * 4.0 / (double)(1 << 30));
+			return false;
+		}
+		SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), return false);
+		SA_HIP_CHECK(hipEventCreate(&e0), return false);
+		SA_HIP_CHECK(hipEventCreate(&e1), return false);
+		SA_HIP_CHECK(hipEventRecord(e0, stream), return false);
+		if (sa_ctx_align_range(ctx, 0, pairs, d_packed, stream) != 0)
+			return false;
+		SA_HIP_CHECK(hipEventRecord(e1, stream), return false);
+		return true;
+	}
+	/* after the stream has been synchronised: the alignment's device time goes to sa_hip_last_align_seconds */
+	bool finish()
+	{
+		float ms = 0.f;
+		SA_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1), return false);
+		g_last_align_seconds.store((double)ms * 1e-3);
+		return true;
+	}
+};
+
 static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score)
 {
 	if (!sc || !index || !score) {
@@ -434,56 +492,39 @@ static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int3
 	}
 	if (!sa_neighbors_check("sa_hip_neighbors", in.num, k))
 		return false;
-	struct Run { /* (released whatever way the function is left) */
-		sa_ctx *ctx = nullptr;
-		int32_t *d_packed = nullptr;
-		hipStream_t stream = nullptr;
-		hipEvent_t e0 = nullptr, e1 = nullptr;
-		~Run()
-		{
-			if (stream) {
-				(void)hipStreamSynchronize(stream);
-				(void)hipStreamDestroy(stream);
-			}
-			if (e0)
-				(void)hipEventDestroy(e0);
-			if (e1)
-				(void)hipEventDestroy(e1);
-			(void)hipFree(d_packed);
-			if (ctx)
-				sa_ctx_destroy(ctx);
-		}
-	} run;
-	run.ctx = sa_ctx_create(0, in, sc);
-	if (!run.ctx)
+	DeviceRun run;
+	if (!run.begin("sa_hip_neighbors", in, sc))
 		return false;
-	const int64_t pairs = run.ctx->pairs;
-	SA_HIP_CHECK(hipSetDevice(0), return false);
-	if (hipMalloc(&run.d_packed, sizeof(int32_t) * (size_t)pairs) != hipSuccess) {
-		(void)hipGetLastError();
-		run.d_packed = nullptr;
-		sa_set_error("sa_hip_neighbors: the packed matrix of %d sequences (%.2f GiB) does not fit the device's memory", in.num,
-			     (double)pairs * 4.0 / (double)(1 << 30));
-		return false;
-	}
-	SA_HIP_CHECK(hipStreamCreateWithFlags(&run.stream, hipStreamNonBlocking), return false);
-	SA_HIP_CHECK(hipEventCreate(&run.e0), return false);
-	SA_HIP_CHECK(hipEventCreate(&run.e1), return false);
-	SA_HIP_CHECK(hipEventRecord(run.e0, run.stream), return false);
-	if (sa_ctx_align_range(run.ctx, 0, pairs, run.d_packed, run.stream) != 0)
-		return false;
-	SA_HIP_CHECK(hipEventRecord(run.e1, run.stream), return false);
 	if (!sa_neighbors_to_host(run.d_packed, in.num, k, index, score, run.stream))
 		return false;
-	float ms = 0.f;
-	SA_HIP_CHECK(hipEventElapsedTime(&ms, run.e0, run.e1), return false);
-	g_last_align_seconds.store((double)ms * 1e-3);
-	return true;
+	return run.finish();
 }
 
 extern "C" bool sa_hip_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score)
 {
 	return sa_guard("sa_hip_neighbors", false, [&] { return neighbors_impl(in, sc, k, index, score); });
+}
+
+static sa_edges *edges_impl(struct sa_input in, const struct sa_scoring *sc, int32_t min_score)
+{
+	if (!sc) {
+		sa_set_error("sa_hip_edges: null argument");
+		return nullptr;
+	}
+	DeviceRun run;
+	if (!run.begin("sa_hip_edges", in, sc))
+		return nullptr;
+	sa_edges *res = sa_edges_to_host("sa_hip_edges", run.d_packed, in.num, min_score, run.stream);
+	if (res && !run.finish()) {
+		sa_edges_destroy(res);
+		res = nullptr;
+	}
+	return res;
+}
+
+extern "C" sa_edges *sa_hip_edges(struct sa_input in, const struct sa_scoring *sc, int32_t min_score)
+{
+	return sa_guard("sa_hip_edges", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score); });
 }
 
 extern "C" int sa_hip_last_align_path(void) { return g_last_align_path.load(); }

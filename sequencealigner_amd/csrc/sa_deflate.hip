@@ -1284,6 +1284,32 @@ extern "C" int sa_zjob_neighbors(sa_zjob *z, int32_t k, int32_t *index, int32_t 
 	});
 }
 
+/* The score graph of the job's packed matrix (sa_edges.hip), in order behind whatever the job has on its stream.  Refuses what
+ * sa_zjob_neighbors refuses, for the same reasons. */
+extern "C" sa_edges *sa_zjob_edges(sa_zjob *z, int32_t min_score)
+{
+	return sa_guard("sa_zjob_edges", (sa_edges *)nullptr, [&]() -> sa_edges * {
+		if (!z) {
+			sa_set_error("sa_zjob_edges: null argument");
+			return nullptr;
+		}
+		if (!z->peers.empty()) {
+			sa_set_error("sa_zjob_edges: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+			return nullptr;
+		}
+		if (!z->d_packed) {
+			sa_set_error("sa_zjob_edges: the job walks a full matrix; the selection reads the packed index");
+			return nullptr;
+		}
+		if (z->shells && z->next_batch < zjob_batches(z)) {
+			sa_set_error("sa_zjob_edges: the walk is not finished (sa_zjob_next has not returned 0 yet)");
+			return nullptr;
+		}
+		SA_HIP_CHECK(hipSetDevice(z->device), return nullptr);
+		return sa_edges_to_host("sa_zjob_edges", z->d_packed, z->num, min_score, z->stream);
+	});
+}
+
 /* one device's part of a walk in shells: context, the packed matrix (whole: a block's place in it is its own), a job over
  * the column blocks `first`, `first + step`, ...; the first two of them are on their way when this returns */
 static sa_zjob *zjob_begin_on(int device, struct sa_input in, const struct sa_scoring *sc, size_t chunk_dim, int level, int first, int step)

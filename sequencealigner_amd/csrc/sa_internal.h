@@ -116,4 +116,10 @@ hipError_t sa_launch_neighbors(const int32_t *packed, int32_t num, int32_t k, in
 /* ... into host arrays, in order on `s`, which is synchronised; the kernel's device time goes to sa_hip_last_neighbors_seconds */
 bool sa_neighbors_to_host(const int32_t *d_packed, int32_t num, int32_t k, int32_t *index, int32_t *score, hipStream_t s);
 
+/* score graph (sa_edges.hip): every pair at or above a threshold, as CSR, from a packed device matrix into host memory, in
+ * order on `s`, which is synchronised; the device time of count + scan + fill goes to sa_hip_last_edges_seconds.  `who` names
+ * the entry point in messages.  nullptr + sa_set_error on failure. */
+struct sa_edges;
+sa_edges *sa_edges_to_host(const char *who, const int32_t *d_packed, int32_t num, int32_t min_score, hipStream_t s);
+
 #endif /* SA_INTERNAL_H */
