@@ -22,6 +22,20 @@
  * The 32-bit add / sub act on both halves because the halves are UNSIGNED and never carry or borrow: all values live
  * in [floor, 65535 - S'max], the profile entries S' = S + const are >= 0 (host-checked, else the s32 kernels run).
  *
+ * Two diagonal adds per instruction (NW, SA_PK_PAIRED_ADDS).  The same argument one level up: two neighbouring registers
+ * are four u16 fields of one 64-bit integer, and by the range predicate above no field of Vdiag + S' exceeds 65535, so
+ * nothing carries from a field into the next one -- neither inside a register nor from the high half of a register into
+ * the low half of its neighbour.  One v_lshl_add_u64 (shift 0; operands are even-aligned VGPR pairs) therefore makes the
+ * diagonal adds of the columns q, q + 1 of a lane: NW keeps its left neighbour's value in the register below column 0
+ * (X[0] = the value moved in from the previous lane, X[q + 1] = V[q]), the pairs are (X[q], X[q + 1]) for even q against
+ * components 0/1 or 2/3 of a 16-byte profile part, and odd K keeps one plain add for its last column.  The adds of a
+ * step run before its DPP move, while X[0] still holds the previous step's left value -- the diagonal input of column
+ * 0 -- so the two alternating left-neighbour registers of the other methods are one here.  (Bubble rows may wrap as
+ * before; a carry out of such a field lands in a cell of the same bubble row of the same lane, which is never stored.)
+ * The instruction's issue cost on this chip is NOT on record yet: tools/microbench/valu_rates.hip (row v_lshl_add_u64)
+ * and max3_f16.hip (paired chains of 8 and 7 registers) are the measurement, DESIGN.md 4.1 / 4.2 say what is known.
+ * Gotoh and SW make their diagonal adds just in time inside the chain and keep the 32-bit add.
+ *
  * Three-way maxima in one instruction (8-lane groups).  gfx950 has v_pk_maximum3_f16, and on the bit patterns
  * 0x0000..0x7c00 the f16 order is the unsigned order: with all values <= SA_PK_F16_MAX = 0x7bff the instruction is a
  * packed max3_u16 (bit-exact, checked exhaustively by tools/microbench/max3_f16.hip; same issue cost as v_pk_max_u16):
@@ -85,6 +99,9 @@
 #ifndef SA_PK_OPAQUE_TOKEN
 #define SA_PK_OPAQUE_TOKEN 1
 #endif
+#ifndef SA_PK_PAIRED_ADDS
+#define SA_PK_PAIRED_ADDS 1 /* NW: one v_lshl_add_u64 for the diagonal adds of two neighbouring columns (0: two v_add_u32) */
+#endif
 #ifndef SA_PK_QUIET_BLOCKS
 #define SA_PK_QUIET_BLOCKS 0 /* measured slower, see do_block */
 #endif
@@ -95,6 +112,7 @@ extern __shared__ __attribute__((aligned(256))) uint8_t sa_pk_lds[];
 
 constexpr int CH = SA_SYS_CHUNK;
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t pkmax(uint32_t a, uint32_t b)
 {
@@ -116,6 +134,17 @@ template <bool F16> __device__ __forceinline__ uint32_t pkmax3(uint32_t a, uint3
 		return d;
 	}
 	return pkmax(pkmax(a, b), c);
+}
+/* Two diagonal adds in one instruction: (hi:lo) + (phi:plo) as ONE 64-bit integer add (v_lshl_add_u64, shift 0) on
+ * even-aligned register pairs.  Exact for the same reason the 32-bit add is (see the header): no u16 field of a live
+ * value carries, so nothing crosses from a register's high half into its neighbour's low half either. */
+__device__ __forceinline__ void pkadd2(uint32_t lo, uint32_t hi, uint32_t plo, uint32_t phi, uint32_t &dlo, uint32_t &dhi)
+{
+	const uint64_t x = ((uint64_t)hi << 32) | lo, p = ((uint64_t)phi << 32) | plo;
+	uint64_t d;
+	asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(d) : "v"(x), "v"(p));
+	dlo = (uint32_t)d;
+	dhi = (uint32_t)(d >> 32);
 }
 __device__ __forceinline__ uint32_t pk2(uint32_t v) { return (v & 0xffffu) | (v << 16); }
 __device__ __forceinline__ uint32_t comp(const uint4 &w, int k) { return k == 0 ? w.x : k == 1 ? w.y : k == 2 ? w.z : w.w; }
@@ -392,7 +421,16 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 	const uint32_t q2 = pk2((uint32_t)-A.q); /* GA: |q| */
 	const uint32_t cmask2 = (pad[0] == 0 ? 0xffffu : 0u) | (pad[1] == 0 ? 0xffff0000u : 0u); /* halves whose column 0 is real */
 	uint32_t V[K], Y[K];
-	uint32_t vl[2];   /* left-neighbour shift registers of even / odd steps; the first lane's copies hold what it injects */
+	uint32_t vl[2];   /* left-neighbour shift registers of even / odd steps (NW with paired adds: vl[0] alone, vl[1] is
+	                   * never read); the first lane's copies hold what it injects */
+	/* NW with paired adds keeps ONE left-neighbour register, vl[0] = X[0] of the header's X[K + 1]: the adds of a step run
+	 * before its DPP move, when the register still holds the previous step's left value, and the move then overwrites it
+	 * (the first lane has no source lane and keeps what it injects, which NW never changes).  X[] is not an array in the
+	 * source: pkadd2's 64-bit operand (vl[0], V[0]) makes the register allocator put vl[0] in the even register below
+	 * V[0], and (V[q - 1], V[q]) pins the rest of V[] pairwise.  Nothing but that operand constraint asks for it; what
+	 * shows a compiler that builds the pairs with copies instead is the v_mov_b32 count of tools/dev/codegen_check.py
+	 * (nw 8 9: no more of them than with SA_PK_PAIRED_ADDS=0). */
+	constexpr bool PAIRED = SA_PK_PAIRED_ADDS && METHOD == SA_METHOD_NW;
 	uint32_t xout = 0; /* GA: X of the column right of V[K-1], current row */
 	uint32_t vbase;    /* GA: the plain boundary value (first lane) */
 	/* SW (row-shifted domain of sa_systolic_kernel.inc: with p the stream position of the row a lane is processing it
@@ -507,7 +545,7 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 		 * flight -- 92 -> 128 VGPRs for NW K <= 16, 163 / 165 for Gotoh / SW (a wave per SIMD less) -- and doubles the loop's
 		 * code: cfg 2 14.50 -> 15.18 ms, U[65,128] 33.3 -> 32.2 TCUPS.  The per-step branch costs nothing measurable. */
 		auto step = [&](auto has_events, const int s) __attribute__((always_inline)) {
-			uint32_t &vcur = vl[s & 1];
+			uint32_t &vcur = vl[PAIRED ? 0 : s & 1];
 			if (METHOD == SA_METHOD_SW)
 				carry = pkmax(shift_in<G>(0u, carry), best);
 			if (decltype(has_events)::value && __builtin_expect((ev >> s) & 1u, 0)) { /* wave-uniform, rare */
@@ -533,7 +571,8 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 					}
 					if (!leader) {
 						vl[0] = pksubsat(vl[0], delta2);
-						vl[1] = pksubsat(vl[1], delta2);
+						if (!PAIRED)
+							vl[1] = pksubsat(vl[1], delta2);
 					}
 					frame++;
 				}
@@ -566,7 +605,7 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			/* token two steps ahead (positions 16, 17 belong to the next block, already in the ring).  Loaded BEHIND the event
 			 * branch: load and the step's end then sit in one basic block (see SA_PK_OPAQUE_TOKEN below) */
 			const uint32_t tk_far = rbase[s + 2];
-			const uint32_t vprev = vl[(s + 1) & 1];
+			const uint32_t vprev = vl[PAIRED ? 0 : (s + 1) & 1];
 			/* Diagonal adds are made just in time (column q + 1's from the still-old V[q]), and a 16-byte part of the
 			 * profile row is re-loaded for the NEXT step as soon as its four columns have been consumed -- no d[] array,
 			 * no second profile buffer.  A packed op that reads the result of the packed op right before it costs a
@@ -583,15 +622,29 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			};
 			uint32_t dnw[K];
 			if (METHOD == SA_METHOD_NW) {
-				dnw[0] = vprev + comp(P[0], 0);
+				if (PAIRED) {
+					/* columns q, q + 1 for even q: (X[q], X[q + 1]) + (S'[q], S'[q + 1]), the profile pair being components
+					 * 0/1 or 2/3 of a ds_read_b128; odd K keeps a plain add for its last column */
 #pragma unroll
-				for (int q = 1; q < K; q++)
-					dnw[q] = V[q - 1] + comp(P[q >> 2], q & 3);
+					for (int q = 0; q + 1 < K; q += 2)
+						pkadd2(q ? V[q - 1] : vprev, V[q], comp(P[q >> 2], q & 3), comp(P[q >> 2], (q & 3) + 1), dnw[q], dnw[q + 1]);
+					if (K & 1)
+						dnw[K - 1] = (K > 1 ? V[K > 1 ? K - 2 : 0] : vprev) + comp(P[(K - 1) >> 2], (K - 1) & 3);
+				} else {
+					dnw[0] = vprev + comp(P[0], 0);
+#pragma unroll
+					for (int q = 1; q < K; q++)
+						dnw[q] = V[q - 1] + comp(P[q >> 2], q & 3);
+				}
 #pragma unroll
 				for (int p = 0; p < PARTS; p++) /* the profile row of the next step, into the registers the adds released */
 					P[p] = *reinterpret_cast<const uint4 *>(row_next + p * PARTSTRIDE);
-				if ((K & 3) != 0) /* (keeps the partly used last part one ds_read_b128, see reload) */
-					asm volatile("" ::"v"(P[PARTS - 1].y), "v"(P[PARTS - 1].z), "v"(P[PARTS - 1].w));
+				if ((K & 3) != 0) { /* (keeps the partly used last part one ds_read_b128, see reload) */
+					if (PAIRED) /* (as ONE operand: with a 64-bit use beside 32-bit ones the load is split into a ds_read2_b64) */
+						asm volatile("" ::"v"(__builtin_bit_cast(u32x4, P[PARTS - 1])));
+					else
+						asm volatile("" ::"v"(P[PARTS - 1].y), "v"(P[PARTS - 1].z), "v"(P[PARTS - 1].w));
+				}
 				__builtin_amdgcn_sched_barrier(0);
 			}
 			if (METHOD == SA_METHOD_SW)

@@ -18,7 +18,7 @@ c = collections.Counter(ops)
 print(name)
 print("instructions", len(ops))
 for k in ("flat_load_ubyte", "flat_load_dword", "global_load_ubyte", "global_load_dword", "s_load_dword", "v_readlane_b32", "v_writelane_b32",
-          "v_readfirstlane_b32", "v_pk_maximum3_f16", "v_pk_max_u16", "v_add_u32_e32", "v_sub_u32_e32", "v_mov_b32_e32", "v_mov_b32_dpp",
+          "v_readfirstlane_b32", "v_pk_maximum3_f16", "v_pk_max_u16", "v_add_u32_e32", "v_lshl_add_u64", "v_sub_u32_e32", "v_mov_b32_e32", "v_mov_b32_dpp",
           "ds_read_b128", "ds_read_u16", "s_nop", "s_waitcnt", "s_setprio"):
     print(f"  {k:22s} {c.get(k, 0)}")
 flat = sum(v for k, v in c.items() if k.startswith("flat_"))

@@ -74,7 +74,42 @@ template <int MODE> __global__ __launch_bounds__(256) void rate(uint32_t *out, i
 	out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 
-template <int MODE> int run(const char *name, double per)
+/* The hoisted shape again with the register count as a parameter, and with the adds paired: two neighbouring registers
+ * hold four u16 fields that never carry (the packing invariant), so one v_lshl_add_u64 with shift 0 on the even-aligned
+ * pair does both adds. Odd NR keeps one plain add for the last register. PAIRED adds read v[q] where the plain rows read
+ * v[q-1] (a pair has to be two neighbours); both are hoisted in front of the chain, so the issue stream is the same. */
+template <int NR, bool PAIRED> __global__ __launch_bounds__(256) void rate_chain(uint32_t *out, int seed)
+{
+	uint32_t v[NR], d[NR], w = threadIdx.x * 0x00010001u + seed;
+	for (int q = 0; q < NR; q++) v[q] = (threadIdx.x + q * seed) & 0x3fff3fffu, d[q] = v[q] ^ 0x11;
+	const uint64_t ww = ((uint64_t)(w ^ 0x5) << 32) | w;
+	for (int r = 0; r < REP; r++) {
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+			if (PAIRED) {
+#pragma unroll
+				for (int q = 0; q + 1 < NR; q += 2) {
+					uint64_t s, x = ((uint64_t)v[q + 1] << 32) | v[q];
+					asm volatile("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(s) : "v"(x), "v"(ww));
+					d[q] = (uint32_t)s, d[q + 1] = (uint32_t)(s >> 32);
+				}
+				if (NR & 1) asm volatile("v_add_u32_e32 %0, %1, %2" : "=v"(d[NR - 1]) : "v"(w), "v"(v[NR - 1]));
+			} else {
+#pragma unroll
+				for (int q = 0; q < NR; q++)
+					asm volatile("v_add_u32_e32 %0, %1, %2" : "=v"(d[q]) : "v"(w), "v"(v[(q + NR - 1) % NR]));
+			}
+#pragma unroll
+			for (int q = 0; q < NR; q++)
+				asm volatile("v_pk_maximum3_f16 %0, %1, %0, %2" : "+v"(v[q]) : "v"(d[q]), "v"(v[(q + NR - 1) % NR]));
+		}
+	}
+	uint32_t s = 0;
+	for (int q = 0; q < NR; q++) s += v[q] + d[q];
+	out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
+template <int MODE, int NR = 8, bool PAIRED = false> int run(const char *name, double per)
 {
 	uint32_t *out;
 	CHECK(hipMalloc(&out, 4 * 256 * 8 * 256));
@@ -82,9 +117,11 @@ template <int MODE> int run(const char *name, double per)
 	for (int bpc : { 1, 2, 4, 8 }) {
 		hipEvent_t e0, e1;
 		CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
-		hipLaunchKernelGGL(rate<MODE>, dim3(256 * bpc), dim3(256), 0, 0, out, 3);
+		void (*kern)(uint32_t *, int);
+		if constexpr (MODE < 6) kern = rate<MODE>; else kern = rate_chain<NR, PAIRED>;
+		hipLaunchKernelGGL(kern, dim3(256 * bpc), dim3(256), 0, 0, out, 3);
 		CHECK(hipEventRecord(e0, 0));
-		hipLaunchKernelGGL(rate<MODE>, dim3(256 * bpc), dim3(256), 0, 0, out, 3);
+		hipLaunchKernelGGL(kern, dim3(256 * bpc), dim3(256), 0, 0, out, 3);
 		CHECK(hipEventRecord(e1, 0));
 		CHECK(hipDeviceSynchronize());
 		float ms = 0.f;
@@ -113,5 +150,9 @@ int main()
 	run<3>("NW register step: add + 2 v_pk_max_u16", 1);
 	run<4>("NW register step: add + v_pk_maximum3_f16", 1);
 	run<5>("NW register step: adds hoisted, max3 chain", 1);
+	run<6, 8, false>("  the same, 8 registers (parametrised)", 1);
+	run<6, 8, true>("  8 registers, 4 v_lshl_add_u64", 1);
+	run<6, 7, false>("  the same, 7 registers", 7.0 / 8);
+	run<6, 7, true>("  7 registers, 3 v_lshl_add_u64 + 1 add", 7.0 / 8);
 	return h != 0;
 }

@@ -15,6 +15,11 @@ template <int MODE> __global__ __launch_bounds__(256) void k(int *out, unsigned 
 {
 	int v[8], w = threadIdx.x * 0x01010101 + seed, acc = seed, z = seed * 3;
 	for (int q = 0; q < 8; q++) v[q] = threadIdx.x + q * seed;
+	unsigned long long v2[8] = {}, w2 = 0; /* MODE 40 only: 64-bit operands, even-aligned VGPR pairs */
+	if (MODE == 40) {
+		w2 = ((unsigned long long)w << 32) | (unsigned)z;
+		for (int q = 0; q < 8; q++) v2[q] = (unsigned long long)v[q] * 0x100000001ull;
+	}
 	unsigned long long t0 = __builtin_amdgcn_s_memtime();
 	unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
 	for (int r = 0; r < REP; r++) {
@@ -59,12 +64,17 @@ template <int MODE> __global__ __launch_bounds__(256) void k(int *out, unsigned 
 			if (MODE == 37) OP8("v_cmp_lt_i32_e64 s[20:21], %1, %0\n\tv_cndmask_b32_e64 %0, %1, %0, s[20:21]", "v"(w) : "s20", "s21");
 			if (MODE == 38) OP8("v_cmp_lt_i32_e32 vcc, %1, %0", "v"(w) : "vcc");
 			if (MODE == 39) OP8("v_sub_u32_e32 %0, %1, %0\n\tv_ashrrev_i32_e32 %0, 31, %0\n\tv_and_b32_e32 %0, %1, %0\n\tv_max_u32_e32 %0, %1, %0", "v"(w));
+			if (MODE == 40) {
+#pragma unroll
+				for (int q = 0; q < 8; q++) asm volatile("v_lshl_add_u64 %0, %1, 0, %0" : "+v"(v2[q]) : "v"(w2));
+			}
 		}
 	}
 	unsigned long long t1 = __builtin_amdgcn_s_memtime();
 	unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
 	int s = z;
 	for (int q = 0; q < 8; q++) s += v[q];
+	if (MODE == 40) for (int q = 0; q < 8; q++) s += (int)v2[q] + (int)(v2[q] >> 32);
 	out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 	if ((threadIdx.x & 63) == 0) {
 		cyc[blockIdx.x * 4 + threadIdx.x / 64] = t1 - t0;
@@ -122,7 +132,7 @@ int main()
 	ROW(2, "v_max3_i32"); ROW(7, "v_max3_f32"); ROW(15, "v_med3_i32"); ROW(13, "v_add3_u32"); ROW(12, "v_lshl_add_u32"); ROW(14, "v_mad_i32_i24");
 	ROW(1, "v_add_u32_sdwa"); ROW(18, "v_add_u32_dpp"); ROW(3, "v_mov_b32_dpp"); ROW(11, "v_cndmask_b32");
 	ROW(16, "v_pk_add_i16"); ROW(17, "v_pk_max_i16"); ROW(32, "v_pk_max_f16"); ROW(19, "v_cvt_f32_ubyte1"); ROW(20, "v_dot4c_i32_i8");
-	ROW(34, "v_bfe_i32"); ROW(35, "v_perm_b32");
+	ROW(34, "v_bfe_i32"); ROW(35, "v_perm_b32"); ROW(40, "v_lshl_add_u64 (shift 0)");
 	ROW(36, "v_cmp + v_cndmask (vcc), per PAIR"); ROW(37, "v_cmp + v_cndmask (sgpr pair), per PAIR"); ROW(38, "v_cmp_lt_i32 alone");
 	ROW(39, "sub+ashr+and+max select, per FOUR");
 	printf("\n\ncalibration over all launches above: s_memtime %.1f ticks/us of s_memrealtime (100 MHz) = %.0f MHz;  "
