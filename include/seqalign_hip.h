@@ -134,6 +134,12 @@ int64_t sa_ctx_pairs(const sa_ctx *ctx);
  * (a hipStream_t, NULL = default stream). 0 on success. */
 int sa_ctx_align_range(sa_ctx *ctx, int64_t start, int64_t count, int32_t *d_scores, void *stream);
 
+/* Diagnostics: how the packed tiles of the context's LAST launch (range, share or host delivery batch) got their row tokens --
+ * *lean from the token streams built beside the arranged copies of the store, *legacy derived from the code bytes in the
+ * kernel (partial tiles, store-order tiles, everything with SA_HIP_NO_TOKENS=1).  Counted on the host from the launch plan
+ * with the kernel's own rule.  0 on success. */
+int sa_ctx_token_tiles(const sa_ctx *ctx, int64_t *lean, int64_t *legacy);
+
 /* The launch/copy loop of cuda_align (src/interface/seqalign_cuda.c:182-292) on a ready context: scores of the
  * packed range [start, start+count) delivered into the HOST matrix `out` (the WHOLE matrix: packed element p
  * at out.matrix[p], or full dim x dim; out.matrix == NULL computes and copies nothing, the reference's -W).

@@ -47,7 +47,7 @@ class _Scoring(C.Structure):  # struct sa_scoring
 #: every symbol include/seqalign_hip.h declares (tests check the .so exports exactly these)
 ABI_SYMBOLS = (
     "sa_hip_memory", "sa_hip_align", "sa_hip_filter", "sa_ctx_create", "sa_ctx_destroy", "sa_ctx_pairs", "sa_pairs_cells",
-    "sa_ctx_align_range", "sa_ctx_align_range16", "sa_ctx_scores_fit16", "sa_hip_widen16", "sa_ctx_expand_full", "sa_pairs_partition", "sa_ctx_timing", "sa_ctx_timing_read",
+    "sa_ctx_align_range", "sa_ctx_align_range16", "sa_ctx_token_tiles", "sa_ctx_scores_fit16", "sa_hip_widen16", "sa_ctx_expand_full", "sa_pairs_partition", "sa_ctx_timing", "sa_ctx_timing_read",
     "sa_matrix_load", "sa_matrix_count", "sa_matrix_name", "sa_matrix_is_nucleotide", "sa_method_parse",
     "sa_method_name", "sa_method_gap_kind", "sa_hip_device_count", "sa_hip_device_name", "sa_last_error",
     "sa_abi_version",
@@ -113,6 +113,8 @@ def load_library() -> C.CDLL:
     lib.sa_pairs_cells.restype = C.c_int64
     lib.sa_ctx_align_range.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sa_ctx_align_range.restype = C.c_int
+    lib.sa_ctx_token_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.sa_ctx_token_tiles.restype = C.c_int
     lib.sa_ctx_align_range16.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sa_ctx_align_range16.restype = C.c_int
     lib.sa_ctx_scores_fit16.argtypes = [C.c_void_p]
@@ -668,6 +670,14 @@ class Context:
     def align_range(self, start: int, count: int, d_scores_ptr: int, stream: int = 0) -> None:
         if self._lib.sa_ctx_align_range(self._h, start, count, C.c_void_p(d_scores_ptr), C.c_void_p(stream)):
             raise AlignError(_err())
+
+    def token_tiles(self) -> tuple[int, int]:
+        """packed tiles of the last launch as (lean, legacy): streaming the token streams built beside the arranged copies /
+        deriving their tokens from the code bytes in the kernel (partial and store-order tiles, SA_HIP_NO_TOKENS=1)"""
+        lean, legacy = C.c_int64(0), C.c_int64(0)
+        if self._lib.sa_ctx_token_tiles(self._h, C.byref(lean), C.byref(legacy)):
+            raise AlignError(_err())
+        return int(lean.value), int(legacy.value)
 
     @property
     def scores_fit16(self) -> bool:

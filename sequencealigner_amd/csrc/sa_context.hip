@@ -144,6 +144,7 @@ SaPlanInputs sa_plan_inputs(const sa_ctx *ctx)
 	in.persistent_wgs = ctx->persistent_wgs;
 	in.env_chunk = ctx->env.chunk;
 	in.no_sort = ctx->env.no_sort;
+	in.no_tokens = ctx->env.no_tokens;
 	return in;
 }
 
@@ -297,6 +298,10 @@ extern "C" void sa_ctx_destroy(sa_ctx *ctx)
 		(void)hipFree(ar.d_off);
 		(void)hipFree(ar.d_rowmap);
 		(void)hipFree(ar.d_posmap);
+		(void)hipFree(ar.d_tok);
+		(void)hipFree(ar.d_tok_off);
+		(void)hipFree(ar.d_mine);
+		(void)hipFree(ar.d_any);
 	}
 	(void)hipFree(ctx->d_codes);
 	(void)hipFree(ctx->d_meta);
@@ -344,10 +349,23 @@ bool sa_arranged_store(sa_ctx *ctx, const SaArrKey &key, const sa_ctx::Arranged 
 		memcpy(codes_s.data() + off_s[(size_t)p], ctx->codes.data() + ctx->off[(size_t)i], (size_t)n);
 		off_s[(size_t)p + 1] = off_s[(size_t)p] + n;
 	}
+	SaTokenStreams ts; /* (one more linear pass over the copy; nothing with SA_HIP_NO_TOKENS) */
+	if (!ctx->env.no_tokens && !sa_build_tokens(codes_s.data(), off_s.data(), num, key, ts))
+		return false;
 	sa_ctx::Arranged ar;
 	ar.key = key;
 	bool ok = false;
 	do {
+		if (!ts.tok.empty()) {
+			SA_HIP_CHECK(hipMalloc(&ar.d_tok, sizeof(uint16_t) * ts.tok.size()), break);
+			SA_HIP_CHECK(hipMalloc(&ar.d_tok_off, sizeof(int32_t) * ts.tok_off.size()), break);
+			SA_HIP_CHECK(hipMalloc(&ar.d_mine, sizeof(uint16_t) * ts.mine.size()), break);
+			SA_HIP_CHECK(hipMalloc(&ar.d_any, sizeof(uint16_t) * ts.any.size()), break);
+			SA_HIP_CHECK(hipMemcpy(ar.d_tok, ts.tok.data(), sizeof(uint16_t) * ts.tok.size(), hipMemcpyHostToDevice), break);
+			SA_HIP_CHECK(hipMemcpy(ar.d_tok_off, ts.tok_off.data(), sizeof(int32_t) * ts.tok_off.size(), hipMemcpyHostToDevice), break);
+			SA_HIP_CHECK(hipMemcpy(ar.d_mine, ts.mine.data(), sizeof(uint16_t) * ts.mine.size(), hipMemcpyHostToDevice), break);
+			SA_HIP_CHECK(hipMemcpy(ar.d_any, ts.any.data(), sizeof(uint16_t) * ts.any.size(), hipMemcpyHostToDevice), break);
+		}
 		SA_HIP_CHECK(hipMalloc(&ar.d_codes, codes_s.size()), break);
 		SA_HIP_CHECK(hipMalloc(&ar.d_off, sizeof(int32_t) * off_s.size()), break);
 		SA_HIP_CHECK(hipMalloc(&ar.d_rowmap, sizeof(int32_t) * rowmap.size()), break);
@@ -364,6 +382,10 @@ bool sa_arranged_store(sa_ctx *ctx, const SaArrKey &key, const sa_ctx::Arranged 
 		(void)hipFree(ar.d_off);
 		(void)hipFree(ar.d_rowmap);
 		(void)hipFree(ar.d_posmap);
+		(void)hipFree(ar.d_tok);
+		(void)hipFree(ar.d_tok_off);
+		(void)hipFree(ar.d_mine);
+		(void)hipFree(ar.d_any);
 		return false;
 	}
 	*out = &ctx->arranged.back();

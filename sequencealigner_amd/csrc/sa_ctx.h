@@ -72,8 +72,12 @@ struct sa_ctx {
 		SaArrKey key;
 		uint8_t *d_codes = nullptr;
 		int32_t *d_off = nullptr, *d_rowmap = nullptr, *d_posmap = nullptr;
+		/* its token streams (sa_plan.h: SaTokenStreams); nullptr with SA_HIP_NO_TOKENS */
+		uint16_t *d_tok = nullptr, *d_mine = nullptr, *d_any = nullptr;
+		int32_t *d_tok_off = nullptr;
 	};
 	std::deque<Arranged> arranged;
+	int64_t tok_lean = 0, tok_legacy = 0; /* packed tiles of the last launch: streaming pre-built tokens / deriving them (sa_ctx_token_tiles) */
 	bool out_is_host = false; /* the range being launched stores straight into host memory (sa_ctx_align_host) */
 	/* launch plans of recently used packed ranges (callers loop over the same few ranges): the host plan (sa_plan.h) and
 	 * its device copies */

@@ -59,7 +59,7 @@ static bool resolve_levels(sa_ctx *ctx, const SaArrKey (&keys)[SA_PK_SORT_LEVELS
 		if (!sa_arranged_store(ctx, keys[l], &ar))
 			return false;
 		if (ar)
-			lv[l] = { ar->d_codes, ar->d_off, ar->d_rowmap, ar->d_posmap, ar->key.block };
+			lv[l] = { ar->d_codes, ar->d_off, ar->d_rowmap, ar->d_posmap, ar->key.block, ar->d_tok, ar->d_tok_off, ar->d_mine, ar->d_any };
 	}
 	return true;
 }
@@ -502,9 +502,12 @@ static int align_range_launches(sa_ctx *ctx, int64_t start, int64_t count, int32
 	 * 30.8 -> 29.7 ms, three bundles of a mixed-length store 12.35 -> 11.54 ms
 	 * (profiles/r04_bundles_side_by_side_vs_serial.txt). */
 	ctx->prog_items.clear();
+	ctx->tok_lean = ctx->tok_legacy = 0;
 	for (size_t bi = 0; bi < pl.h.bundles.size(); bi++) {
 		if (pl.h.bundles[bi].nlocal[(size_t)rk] <= 0)
 			continue;
+		ctx->tok_lean += pl.h.bundles[bi].tok_lean[(size_t)rk];
+		ctx->tok_legacy += pl.h.bundles[bi].tok_legacy[(size_t)rk];
 		Launch L = pk_launch(ctx, pl, bi, rk, share, counters, common);
 		if (!run_launch(ctx, L, s))
 			return 1;
@@ -564,6 +567,19 @@ int sa_align_range_impl(sa_ctx *ctx, int64_t start, int64_t count, int32_t *d_sc
 	} mark{ ctx, slot, &rc };
 	rc = align_range_launches(ctx, start, count, d_scores, s, out16, world, rank, host_out, slot);
 	return rc;
+}
+
+extern "C" int sa_ctx_token_tiles(const sa_ctx *ctx, int64_t *lean, int64_t *legacy)
+{
+	return sa_guard("sa_ctx_token_tiles", 1, [&] {
+		if (!ctx || !lean || !legacy) {
+			sa_set_error("sa_ctx_token_tiles: null argument");
+			return 1;
+		}
+		*lean = ctx->tok_lean;
+		*legacy = ctx->tok_legacy;
+		return 0;
+	});
 }
 
 extern "C" int sa_ctx_align_range(sa_ctx *ctx, int64_t start, int64_t count, int32_t *d_scores, void *stream)

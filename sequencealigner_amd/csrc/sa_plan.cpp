@@ -148,6 +148,54 @@ void sa_arrange_rows(const sa_meta *meta, int32_t num, const SaArrKey &key, std:
 	}
 }
 
+bool sa_build_tokens(const uint8_t *codes, const int32_t *off, int32_t num, const SaArrKey &key, SaTokenStreams &ts)
+{
+	ts = SaTokenStreams();
+	if (!sa_arranged_exists(num, key))
+		return true;
+	const int ng = key.ng, ch = key.ch, g = 64 / ng;
+	const int32_t streams = num / key.block * (key.block / ch), slots = streams / ng; /* (a block is whole wave slots) */
+	ts.streams = streams;
+	ts.tok_off.resize((size_t)streams + 1);
+	int64_t total = 0;
+	for (int32_t w = 0; w < slots; w++) {
+		int32_t smax = 0;
+		for (int s = w * ng; s < (w + 1) * ng; s++)
+			smax = std::max(smax, off[(size_t)(s + 1) * ch] - off[(size_t)s * ch]);
+		/* the kernel runs nblk blocks and its last one prefetches block nblk + 1 (pk_tile: load_block(blk + 2)) */
+		const int32_t nblk = (smax + g - 1 + 15) >> 4, padded = 16 * sa_token_blocks(smax, g);
+		if (padded < 16 * (nblk + 1) + 16 || padded != (smax + g - 1 + 15) / 16 * 16 + 32) {
+			sa_set_error("token streams: padded length %d does not cover the lookahead of %d blocks", padded, nblk);
+			return false;
+		}
+		for (int s = w * ng; s < (w + 1) * ng; s++) {
+			ts.tok_off[(size_t)s] = (int32_t)total;
+			total += padded;
+		}
+		if (total > (int64_t)1 << 30) {
+			sa_set_error("token streams: store too large for 32-bit stream offsets");
+			return false;
+		}
+	}
+	ts.tok_off[(size_t)streams] = (int32_t)total;
+	ts.tok.assign((size_t)total, (uint16_t)SA_CODE_NOP);
+	ts.mine.assign((size_t)(total / 16), 0);
+	ts.any.assign((size_t)(total / 16 / ng), 0);
+	for (int32_t s = 0; s < streams; s++) {
+		const int32_t b = off[(size_t)s * ch], n = off[(size_t)(s + 1) * ch] - b, at = ts.tok_off[(size_t)s];
+		const int32_t any_at = ts.tok_off[(size_t)(s / ng * ng)] / 16 / ng;
+		for (int32_t p = 0; p < n; p++) {
+			const uint8_t c = codes[(size_t)b + (size_t)p];
+			ts.tok[(size_t)at + (size_t)p] = c;
+			if (c == SA_CODE_SEP) {
+				ts.mine[(size_t)(at / 16 + p / 16)] |= (uint16_t)(1u << (p & 15));
+				ts.any[(size_t)(any_at + p / 16)] |= (uint16_t)(1u << (p & 15));
+			}
+		}
+	}
+	return true;
+}
+
 static const char *const TOO_LARGE = "packed range too large for one launch; split it into smaller ranges";
 
 bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int world, bool share_host, SaHostPlan &plan)
@@ -521,6 +569,8 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 		b.nlocal.assign((size_t)nranks, 0);
 		b.pairs.assign((size_t)nranks, 0);
 		b.cells.assign((size_t)nranks, 0);
+		b.tok_lean.assign((size_t)nranks, 0);
+		b.tok_legacy.assign((size_t)nranks, 0);
 		struct Part {
 			int64_t work;
 			uint32_t code, pair;
@@ -535,6 +585,9 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 				const int32_t npairs = (cl.ncols + 1) / 2;
 				const bool small = sa_pk_decode(cl.cls).small;
 				const int64_t full_rows = (int64_t)sa_pk_wpb(in.method, b.g, sa_pk_decode(cl.cls).k) * (64 / b.g) * cl.chunk;
+				const auto &rw = rows_of[(size_t)cl.cls];
+				const int32_t lvrows[SA_PK_SORT_LEVELS] = { b.args[x].lv[0].block, b.args[x].lv[1].block, b.args[x].lv[2].block,
+									    b.args[x].lv[3].block };
 				int32_t pair_of_full = 0; /* (tiles ascend: the pair index only moves forward) */
 				for (int32_t t = 0; t < cl.ntiles; t++) {
 					uint32_t pair;
@@ -547,6 +600,14 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 					}
 					if (world >= 1 && cl.owner[(size_t)t] != r)
 						continue;
+					{ /* which way the tile gets its tokens: pk_tile's rule -- an arranged level picked, hence a full tile */
+						const size_t c0 = (size_t)2 * pair, c1 = c0 + 1 < rw.size() ? c0 + 1 : c0;
+						const int32_t ra = std::min(rw[c0].first, rw[c1].first), rb = std::max(rw[c0].second, rw[c1].second);
+						const int32_t chunk = t < nfull ? t - T[(size_t)pair] : T[(size_t)pair + 1] - T[(size_t)pair];
+						const int32_t i_begin = ra + chunk * (int32_t)full_rows;
+						const bool lean = !in.no_tokens && sa_pk_pick_level(lvrows, ra, rb, i_begin, (int32_t)full_rows) >= 0;
+						(lean ? b.tok_lean : b.tok_legacy)[(size_t)r]++;
+					}
 					const uint32_t code = ((uint32_t)x << SA_PK_UTILE_BITS) | (uint32_t)t;
 					if (t < nfull && !small) {
 						ul.push_back(code);

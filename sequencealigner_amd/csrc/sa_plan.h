@@ -60,6 +60,7 @@ struct SaPlanInputs {
 	/* development switches (sa_env.h) */
 	int env_chunk = 0;
 	bool no_sort = false;
+	bool no_tokens = false;
 };
 
 /* Which kernel families reproduce the reference exactly for a scoring and a store's length range, and their constants
@@ -94,6 +95,27 @@ bool sa_arranged_exists(int32_t num, const SaArrKey &key);
 int sa_pk_arranged_keys(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chunk_pk, bool host_out, SaArrKey (&lv)[SA_PK_SORT_LEVELS]);
 /* The permutation of one arranged copy: rowmap[position] = row (DESIGN 4.2 "arranged row streams") */
 void sa_arrange_rows(const sa_meta *meta, int32_t num, const SaArrKey &key, std::vector<int32_t> &rowmap);
+
+/* Token streams of one arranged copy (DESIGN 4.2 "token streams"): what the block work of the packed kernels derives from
+ * the code bytes -- the profile row of every stream position, NOP past the end of a stream, the terminator masks of every
+ * 16-position block -- made once, beside the copy.  A full tile of shape {ng, ch} streams positions [i_begin, +rows) with
+ * i_begin a multiple of ch, so the streams are a fixed partition of the copy: stream = position / ch, wave slot =
+ * stream / ng.  Only the arranged blocks are covered (positions below num / block * block).
+ *   tok      u16 per stream position: the residue code, SA_CODE_SEP behind every sequence, SA_CODE_NOP from the stream's end
+ *            to the padded length of its wave slot, 16 (roundup((smax + G - 1) / 16) + 2) positions with smax the longest
+ *            stream of the slot and G = 64 / ng: the kernel's prefetch of block nblk + 1 reads without a clamp
+ *   tok_off  [streams + 1] start of every stream in tok, in positions: a multiple of 16, so that
+ *   mine     u16 per 16-position block of a stream, at tok_off[stream] / 16 + blk: bit p = position 16 blk + p is a terminator
+ *   any      u16 per block of a wave slot, at tok_off[slot * ng] / 16 / ng + blk: the OR of the slot's ng `mine` */
+struct SaTokenStreams {
+	int32_t streams = 0;
+	std::vector<uint16_t> tok, mine, any;
+	std::vector<int32_t> tok_off;
+};
+/* blocks (16 positions) a wave slot's streams are padded to: smax = positions of its longest stream, g = lanes per group */
+inline int32_t sa_token_blocks(int32_t smax, int g) { return ((smax + g - 1 + 15) >> 4) + 2; }
+/* codes / off: the ARRANGED copy (position order, terminators included); false + sa_set_error when it does not fit 32-bit offsets */
+bool sa_build_tokens(const uint8_t *codes, const int32_t *off, int32_t num, const SaArrKey &key, SaTokenStreams &ts);
 
 struct SaHostClass {
 	int cls = 0;
@@ -133,6 +155,9 @@ struct SaHostBundle {
 	std::vector<int64_t> ufirst;     /* max(world, 1) + 1 offsets into ulist                            */
 	std::vector<int32_t> nlocal;     /* tiles of the launch, per rank (one entry when world == 0)       */
 	std::vector<int64_t> pairs, cells;
+	/* per rank: tiles of the launch that stream pre-built tokens (full tiles of an arranged level, tokens not switched
+	 * off) and tiles that derive them in the kernel -- the rule of pk_tile (sa_systolic_pk.inc), counted here */
+	std::vector<int64_t> tok_lean, tok_legacy;
 };
 
 struct SaGenericShare {

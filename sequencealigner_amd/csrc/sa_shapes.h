@@ -113,6 +113,11 @@ struct SaArranged { /* one arranged copy of the row store (sa_plan.cpp: sa_arran
 	const int32_t *rowmap; /* position -> row                      */
 	const int32_t *posmap; /* row -> position                      */
 	int32_t rows;          /* sequences per arranged block         */
+	/* token streams of the copy (sa_plan.h: SaTokenStreams), or tok = nullptr: none were built (SA_HIP_NO_TOKENS) */
+	const uint16_t *tok;     /* code / SEP / NOP per stream position    */
+	const int32_t *tok_off;  /* stream -> start in tok (a multiple of 16) */
+	const uint16_t *mine;    /* terminator mask per block of a stream   */
+	const uint16_t *any;     /* ... OR-ed over the streams of a wave slot */
 };
 struct SaPkClassArgs { /* one class of a bundle launch, in device memory */
 	const int32_t *jlist;     /* columns (ascending) of the class                                        */

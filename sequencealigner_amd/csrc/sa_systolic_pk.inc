@@ -276,6 +276,9 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 	const uint8_t *rcodes = A.codes;
 	const int32_t *roff = A.off, *rowmap = nullptr, *posmap = nullptr;
 	int32_t sort_rows = 0;
+	/* token streams of the level the tile streams (sa_plan.h: SaTokenStreams), or none: see the row streams below */
+	const uint16_t *tk_tok = nullptr, *tk_mine = nullptr, *tk_any = nullptr;
+	const int32_t *tk_off = nullptr;
 	{
 		const int32_t lvrows[SA_PK_SORT_LEVELS] = { uload(&A.lvp[0].rows), uload(&A.lvp[1].rows), uload(&A.lvp[2].rows),
 							    uload(&A.lvp[3].rows) };
@@ -287,6 +290,10 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			roff = uniform_ptr(L.off);
 			rowmap = uniform_ptr(L.rowmap);
 			posmap = uniform_ptr(L.posmap);
+			tk_tok = uniform_ptr(L.tok);
+			tk_off = uniform_ptr(L.tok_off);
+			tk_mine = uniform_ptr(L.mine);
+			tk_any = uniform_ptr(L.any);
 			sort_rows = lvrows[0]; /* (then the level's own, without a dynamic register index) */
 #pragma unroll
 			for (int k = 1; k < SA_PK_SORT_LEVELS; k++)
@@ -371,18 +378,23 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 	/* tokens a lane feeds per block: G = 8 two consecutive ones of its own group (positions 2k, 2k+1, k = r16 / 2),
 	 * G = 16 the one at position r16 */
 	constexpr int TPL = G == 8 ? 2 : 1;
+	typedef typename std::conditional<G == 8, uint32_t, uint16_t>::type tok_t; /* ... as one LDS / global access */
 	auto fpos = [&](int u) -> int { return G == 8 ? (r16 & ~1) + u : r16; };
 	/* (32-bit offsets from the uniform base of the store: a scalar-base load, no 64-bit address arithmetic per token) */
-	const uint32_t ulast = (uint32_t)(sbeg + last);
+	/* The three per-lane values the block work keeps across the main loop, one register each for BOTH ways to the tokens
+	 * (below: the lean way): this one's are the offset of the lane's first position in the store, that of the stream's last
+	 * position, and the stream's length.  (Separate variables per way are separate registers: the bundle kernels sit at
+	 * their occupancy limits.) */
+	uint32_t bw_a = (uint32_t)(sbeg + fpos(0)), bw_b = (uint32_t)(sbeg + last), bw_c = (uint32_t)slen;
 	auto load_block = [&](int32_t blk, int u) -> int {
-		const uint32_t at = (uint32_t)(sbeg + fpos(u)) + (uint32_t)(blk << 4);
-		return (int)rcodes[at < ulast ? at : ulast];
+		const uint32_t at = bw_a + (uint32_t)u + (uint32_t)(blk << 4);
+		return (int)rcodes[at < bw_b ? at : bw_b];
 	};
 	constexpr uint32_t SEPWORD = (uint32_t)SA_CODE_SEP * TUNIT;
 	constexpr uint32_t NOPWORD = (uint32_t)SA_CODE_NOP * TUNIT;
 	auto block_word = [&](int32_t blk, int raw, int u) -> uint32_t { /* token -> profile row offset */
 		const int32_t pos = (blk << 4) + fpos(u);
-		return pos < slen ? (uint32_t)raw * TUNIT : NOPWORD;
+		return pos < (int32_t)bw_c ? (uint32_t)raw * TUNIT : NOPWORD;
 	};
 	uint16_t *ring = s_ring + grp * GSTRIDE;
 	auto ring_write = [&](int32_t blk, uint32_t word, int u) {
@@ -413,6 +425,53 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			mine |= ((uint32_t)(m >> ((lane & 48) + (lane & 1))) & 0x5555u) << u;
 		}
 		return any;
+	};
+
+	/* The LEAN way to the same four things (next block's ring entries, gmask_next, evn, the prefetch for block + 2): a tile
+	 * that streams an arranged level is a full tile whose streams are streams of the level's token copy (stream = position /
+	 * chunk; host: sa_build_tokens) -- codes as u16 with NOP from the stream's end and padded past the lookahead, so a lane's
+	 * two positions are ONE aligned dword at a constant offset from a base that moves 32 bytes per block (no clamp, no
+	 * end-of-stream select), one multiply scales both, and the terminator masks are loaded instead of balloted.  One
+	 * wave-uniform branch per block picks the way; the sixteen steps exist once. */
+	/* (an integer in a scalar register: as a bool it lives in a lane mask and every block pays a v_cndmask + v_cmp to test it) */
+	const int32_t lean = __builtin_amdgcn_readfirstlane(tk_tok != nullptr ? 1 : 0);
+	/* its three: bw_a = byte offset of this lane's tokens of block 0 in the token copy, bw_b = that of its stream's masks,
+	 * bw_c = LDS byte offset at which it writes its tokens of a block 0 mod 4 (first ring copy) */
+	const uint16_t *tk_any_w = nullptr;
+	if (lean) {
+		const int32_t s0 = i_begin / ch_full + gw; /* the wave's first stream (i_begin is a multiple of the chunk) */
+		const uint32_t o_w = (uint32_t)uload(tk_off + s0), o_g = (uint32_t)tk_off[s0 + grp];
+		bw_a = 2u * o_g + (G == 8 ? 4u * (uint32_t)(r16 >> 1) : 2u * (uint32_t)r16);
+		bw_b = o_g >> 3; /* u16 per block: 2 (o_g / 16) bytes */
+		tk_any_w = tk_any + (o_w >> 4) / NG;
+		/* (with the offset of the rings folded in: derived from the ring READ base the write address is two instructions per
+		 * block instead of one) */
+		bw_c = (uint32_t)(WPB * OUT_HALFS * 2 + 2 * (wv * (NG * GSTRIDE) + grp * GSTRIDE + fpos(0)));
+	}
+	/* The loads take the address form (uniform base in scalar registers + 32-bit lane offset): the base moves with the block
+	 * in scalar arithmetic and the lane offset never changes.  The empty statement makes the offset a new value (in place)
+	 * every block; loop-invariant, the compiler adds it to the base ONCE and then moves a 64-bit pointer per lane along
+	 * (two registers and a 64-bit vector add per load). */
+	auto lean_load = [&](int32_t blk) -> uint32_t {
+		const uint8_t *const b = reinterpret_cast<const uint8_t *>(tk_tok) + (size_t)(uint32_t)(blk << 5);
+		asm volatile("" : "+v"(bw_a));
+		return *reinterpret_cast<const tok_t *>(b + bw_a);
+	};
+	auto lean_mine = [&](int32_t blk) -> uint32_t {
+		const uint8_t *const b = reinterpret_cast<const uint8_t *>(tk_mine) + (size_t)(uint32_t)(blk << 1);
+		asm volatile("" : "+v"(bw_b));
+		return *reinterpret_cast<const uint16_t *>(b + bw_b);
+	};
+	/* (every lane loads the wave's mask; it becomes scalar -- lean_any_s -- a block later: right behind the load the
+	 * readfirstlane would wait for it) */
+	auto lean_any = [&](int32_t blk) -> uint32_t { return (uint32_t)tk_any_w[blk]; };
+	auto lean_any_s = [&](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+	/* both tokens of the dword scaled at once: code < 64 and code * TUNIT < 65536, nothing carries into the upper half */
+	auto lean_ring = [&](int32_t blk, uint32_t raw) {
+		const uint32_t w = __umul24(raw, TUNIT);
+		tok_t *const at = reinterpret_cast<tok_t *>(sa_pk_lds + bw_c + ((blk & 3) << 5));
+		at[0] = (tok_t)w;
+		at[RING * 2 / sizeof(tok_t)] = (tok_t)w;
 	};
 
 	/* ---- DP state (u16 pairs, see header) ---- */
@@ -478,11 +537,18 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 		s_ring[k] = (uint16_t)NOPWORD;
 	__syncthreads(); /* profile complete (all waves), ring cleared */
 	/* Gotoh: the first sequence starts like after a terminator at stream position -1 */
-	unsigned long long ev_lo = METHOD == SA_METHOD_GA ? 1ull << 63 : 0ull, ev_hi;
+	/* ev_hi: positions of the current block at which some group of the wave has a terminator (16 bits); ev_lo: the same
+	 * for the previous block (all 32-bit scalar arithmetic: as 64-bit history the funnel shifts went through the VALU) */
+	uint32_t ev_lo = METHOD == SA_METHOD_GA ? 0x8000u : 0u, ev_hi;
 	/* gm: bit s + 2 = my group's token at position s of the current block is a terminator; bits 1, 0 = positions 15, 14
 	 * of the previous block */
 	uint32_t gm, gmask;
-	{
+	if (lean) {
+		lean_ring(0, lean_load(0));
+		gmask = lean_mine(0);
+		ev_hi = lean_any_s(lean_any(0));
+		gm = (gmask << 2) | (METHOD == SA_METHOD_GA ? 2u : 0u);
+	} else {
 		uint32_t w0[TPL];
 #pragma unroll
 		for (int u = 0; u < TPL; u++) {
@@ -492,10 +558,23 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 		ev_hi = block_events(w0, gmask);
 		gm = (gmask << 2) | (METHOD == SA_METHOD_GA ? 2u : 0u);
 	}
+	/* What is in flight across a block.  The derived way: the code bytes of the block after the next.  The lean way:
+	 * raw_next[0] = the lane's token dword of that block, mask_next = its stream's terminator mask and any_next the wave's,
+	 * both of the NEXT block -- loaded a block before they are used, like the tokens.  With 8-lane groups mask_next IS
+	 * raw_next[1]: both ways then load both registers in every block and the two unrolled blocks can swap them; a register
+	 * that only one way loads costs that way a copy of the value just loaded, and a wait for it, where the ways join. */
 	int raw_next[TPL];
+	uint32_t mask_pf = 0, any_next = 0;
+	uint32_t &mask_next = TPL == 2 ? reinterpret_cast<uint32_t &>(raw_next[TPL - 1]) : mask_pf;
+	if (lean) {
+		raw_next[0] = (int)lean_load(1);
+		mask_next = lean_mine(1);
+		any_next = lean_any(1);
+	} else {
 #pragma unroll
-	for (int u = 0; u < TPL; u++)
-		raw_next[u] = load_block(1, u);
+		for (int u = 0; u < TPL; u++)
+			raw_next[u] = load_block(1, u);
+	}
 	const uint8_t *const lane_prof = s_prof + copy * (NSLOT * 16) + lig * 16;
 	/* this lane's token of stream position 16 blk + s - lig sits at rbase[s] */
 	auto ring_base = [&](int32_t blk) -> const uint16_t * { return ring + (((blk << 4) - lig) & (RING - 1)); };
@@ -521,20 +600,36 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 		}
 		/* steps of this block at which a terminator enters the first lane of some group (+ Gotoh: the restore steps)
 		 * or the last lane of some group meets one */
-		const unsigned long long ev_in =
-			METHOD == SA_METHOD_GA ? (ev_hi | (ev_hi << 1) | (ev_hi << 2) | (ev_lo >> 63) | (ev_lo >> 62)) : ev_hi;
-		const uint32_t ev = (uint32_t)(((ev_lo >> (64 - (G - 1))) | (ev_hi << (G - 1)) | ev_in) & 0xffffu);
+		const uint32_t ev_in =
+			METHOD == SA_METHOD_GA ? (ev_hi | (ev_hi << 1) | (ev_hi << 2) | (ev_lo >> 15) | (ev_lo >> 14)) : ev_hi;
+		const uint32_t ev = ((ev_lo >> (16 - (G - 1))) | (ev_hi << (G - 1)) | ev_in) & 0xffffu;
 		/* next block's tokens go into the ring while this block computes */
-		uint32_t wn[TPL], gmask_next;
+		uint32_t gm_next, evn; /* gm and ev_hi of the next block */
+		/* (everything in flight was loaded a block ago and is used now: said once, here, the wait costs nothing, and the
+		 * compiler's bookkeeping of the two ways' loads does not end in a wait for the NEW loads further down) */
+		__builtin_amdgcn_s_waitcnt(0x0f70); /* vmcnt(0) */
+		if (lean) {
+			lean_ring(blk + 1, (uint32_t)raw_next[0]);
+			gm_next = (mask_next << 2) | (gm >> 16);
+			evn = lean_any_s(any_next);
+			asm volatile("" ::: "memory"); /* (what was in flight is consumed before its registers are loaded again) */
+			raw_next[0] = (int)lean_load(blk + 2);
+			mask_next = lean_mine(blk + 2);
+			any_next = lean_any(blk + 2);
+		} else {
+			uint32_t gmask_next;
+			uint32_t wn[TPL];
 #pragma unroll
-		for (int u = 0; u < TPL; u++) {
-			wn[u] = block_word(blk + 1, raw_next[u], u);
-			ring_write(blk + 1, wn[u], u);
+			for (int u = 0; u < TPL; u++) {
+				wn[u] = block_word(blk + 1, raw_next[u], u);
+				ring_write(blk + 1, wn[u], u);
+			}
+			evn = block_events(wn, gmask_next);
+			gm_next = (gmask_next << 2) | (gm >> 16);
+#pragma unroll
+			for (int u = 0; u < TPL; u++)
+				raw_next[u] = load_block(blk + 2, u);
 		}
-		const uint32_t evn = block_events(wn, gmask_next);
-#pragma unroll
-		for (int u = 0; u < TPL; u++)
-			raw_next[u] = load_block(blk + 2, u);
 		const uint16_t *rbase = ring_base(blk);
 
 		/* One step of the block.  has_events = false is the same step without the event test: a block in which no
@@ -798,8 +893,8 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			for (int s = 0; s < 16; s++)
 				step(std::true_type{}, s);
 		}
-		gm = (gmask_next << 2) | (gm >> 16);
-		ev_lo = (ev_lo >> 16) | (ev_hi << 48);
+		gm = gm_next;
+		ev_lo = ev_hi;
 		ev_hi = evn;
 	};
 	const unsigned long long ph1 = A.stamps ? __builtin_amdgcn_s_memtime() : 0ull; /* diagnostics: end of the prologue */
