@@ -6,10 +6,15 @@
  * every pair of the range is covered by exactly one tile, tile lists and dense-share layouts stay inside their
  * buffers, placement segments cover the range once, arranged copies are permutations that stay inside their blocks.
  *
- *   plan_check <lens.i32> <method> <matrix> <gap_pen> <gap_open> <gap_ext> <CUs> <start> <count> <world> <share_host> ...
+ *   plan_check [--tokens <chunk>] <lens.i32> <method> <matrix> <gap_pen> <gap_open> <gap_ext> <CUs> <start> <count> <world> <share_host> ...
  *
  * (start, count, world, share_host) may repeat; count = -1 means "to the end", start/count accept k*2^30 style via
- * plain integers only.  Prints one line per plan; exit status 0 = every check held. */
+ * plain integers only.  Prints one line per plan; exit status 0 = every check held.
+ *
+ * --tokens <chunk>: plan with SA_HIP_CHUNK = chunk (0: the planner's own choice) and print, behind every plan, one line per
+ * packed class saying WHICH arranged level its tiles stream pre-built tokens from -- what sa_ctx_token_tiles only counts:
+ *   tokens: G <g> K <k> f16 <0|1> small <0|1> wpb <waves> rows <rows of a full tile> lean <block>:<tiles> ... legacy <tiles>
+ * derived from the class's own lists with sa_pk_pick_level, as sa_plan_host counts tok_lean (the two must agree). */
 #include <algorithm>
 #include <cinttypes>
 #include <cstdio>
@@ -269,6 +274,52 @@ static void check_plan(const SaPlanInputs &in, const SaHostPlan &pl)
 	       pl.chunk_pk_small, pl.segs.size(), pl.share_elems, generic_pairs);
 }
 
+/* per packed class: lean tiles per arranged level and legacy tiles -- the rule of pk_tile (an arranged level picked: the
+ * tile streams that level's tokens), applied to the tiles as tile_geo derives them */
+static void print_tokens(const SaPlanInputs &in, const SaHostPlan &pl)
+{
+	int64_t lean_all = 0, legacy_all = 0, lean_plan = 0, legacy_plan = 0;
+	for (const auto &b : pl.bundles) {
+		for (size_t x = 0; x < b.cls.size(); x++) {
+			const auto &cl = pl.classes[(size_t)b.cls[x]];
+			const SaPkCls pc = sa_pk_decode(cl.cls);
+			const auto &lv = b.args[x].lv;
+			const int32_t lvrows[SA_PK_SORT_LEVELS] = { lv[0].block, lv[1].block, lv[2].block, lv[3].block };
+			const int wpb = sa_pk_wpb(g_method, pc.g, pc.k);
+			int32_t rows = 0; /* of a full tile, as the tile lists have it (0: the class has none) */
+			int64_t lean[SA_PK_SORT_LEVELS] = { 0, 0, 0, 0 }, legacy = 0;
+			for (int32_t t = 0; t < cl.ntiles; t++) {
+				const TileGeo g = tile_geo(pl, cl, t);
+				if (t < cl.ntiles - cl.npart) {
+					CHECK(rows == 0 || rows == g.i_count, "class %d: full tiles of %d and %d rows", cl.cls, rows, g.i_count);
+					rows = g.i_count;
+				}
+				const int32_t ra = std::min(g.ia[0], g.ia[1]), rb = std::max(g.ib[0], g.ib[1]);
+				const int l = in.no_tokens ? -1 : sa_pk_pick_level(lvrows, ra, rb, g.i_begin, wpb * (64 / pc.g) * cl.chunk);
+				if (l >= 0) {
+					CHECK(t < cl.ntiles - cl.npart, "class %d tile %d: a partial tile picked an arranged level", cl.cls, t);
+					lean[l]++;
+					lean_all++;
+				} else {
+					legacy++;
+					legacy_all++;
+				}
+			}
+			printf("tokens: G %d K %d f16 %d small %d wpb %d rows %d lean", pc.g, pc.k, b.f16, (int)pc.small, wpb, rows);
+			for (int l = 0; l < SA_PK_SORT_LEVELS; l++)
+				if (lvrows[l] > 0)
+					printf(" %d:%" PRId64, lvrows[l], lean[l]);
+			printf(" legacy %" PRId64 "\n", legacy);
+		}
+		for (size_t r = 0; r < b.tok_lean.size(); r++) {
+			lean_plan += b.tok_lean[r];
+			legacy_plan += b.tok_legacy[r];
+		}
+	}
+	CHECK(lean_all == lean_plan && legacy_all == legacy_plan, "token tiles: %" PRId64 " lean / %" PRId64 " legacy here, the plan counts %" PRId64 " / %" PRId64,
+	      lean_all, legacy_all, lean_plan, legacy_plan);
+}
+
 static void check_arranged(const SaPlanInputs &in, const SaHostPlan &pl)
 {
 	std::vector<SaArrKey> keys;
@@ -294,8 +345,16 @@ static void check_arranged(const SaPlanInputs &in, const SaHostPlan &pl)
 
 int main(int argc, char **argv)
 {
+	bool tokens = false;
+	int env_chunk = 0;
+	if (argc >= 3 && !strcmp(argv[1], "--tokens")) {
+		tokens = true;
+		env_chunk = atoi(argv[2]);
+		argv += 2;
+		argc -= 2;
+	}
 	if (argc < 12 || (argc - 8) % 4 != 0) {
-		fprintf(stderr, "usage: plan_check lens.i32 method matrix gap_pen gap_open gap_ext CUs (start count world share_host)...\n");
+		fprintf(stderr, "usage: plan_check [--tokens chunk] lens.i32 method matrix gap_pen gap_open gap_ext CUs (start count world share_host)...\n");
 		return 2;
 	}
 	FILE *f = fopen(argv[1], "rb");
@@ -348,6 +407,7 @@ int main(int argc, char **argv)
 	in.pk_gain = L.pk_gain;
 	in.pk_slack = L.pk_slack;
 	in.persistent_wgs = cus * 32;
+	in.env_chunk = env_chunk;
 	printf("store: %d sequences, lengths %d..%d; limits: sys_ok %d pk_kmax %d pk16_kmax %d (f16 up to %d) chunk cap %d\n", num, min_len,
 	       max_len, (int)L.sys_ok, L.pk_kmax, L.pk16_kmax, L.pk16_f16_kmax, L.pk_chunk_cap);
 	const int64_t pairs = (int64_t)num * (num - 1) / 2;
@@ -366,6 +426,8 @@ int main(int argc, char **argv)
 		}
 		check_plan(in, pl);
 		check_arranged(in, pl);
+		if (tokens)
+			print_tokens(in, pl);
 	}
 	if (g_fail) {
 		fprintf(stderr, "%d checks failed\n", g_fail);

@@ -143,3 +143,57 @@ def test_host_delivery(short2100, sa, monkeypatch):
         assert np.array_equal(got[True], got[False])
     finally:
         dest.close()
+
+
+def placed_shares(ctx, pairs, world, elem16, host=None):
+    """align_share of every rank of `world` over the whole range, then place_shares: (placed vector, lean, legacy summed over
+    the ranks); guard words behind the shares and behind the placed vector"""
+    import torch
+    to_host = host is not None
+    e = ctx.share_elems(0, pairs, world, to_host)
+    shares = torch.full((world * e + 8,), -77, dtype=torch.int16 if elem16 else torch.int32, device="cuda")
+    packed = torch.full((pairs + 8,), -77, dtype=torch.int32, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    lean = legacy = 0
+    for r in range(world):
+        ctx.align_share(0, pairs, world, r, shares.data_ptr() + (2 if elem16 else 4) * r * e, elem16, st, host.ptr if to_host else 0)
+        a, b = ctx.token_tiles()
+        lean, legacy = lean + a, legacy + b
+    ctx.place_shares(0, pairs, world, shares.data_ptr(), elem16, packed.data_ptr(), st, to_host)
+    torch.cuda.synchronize()
+    out = packed.cpu().numpy()
+    assert (out[pairs:] == -77).all() and (shares[world * e:].cpu().numpy() == -77).all(), "wrote past the range"
+    return out[:pairs], lean, legacy
+
+
+@pytest.mark.parametrize("world", [2, 8])
+def test_shares_of_two_tile_sizes(world, short2100, sa, monkeypatch):
+    """the multi-rank path without SA_HIP_CHUNK: the planner cuts a rank's share into two tile sizes (chunk_pk and
+    chunk_pk_small, each with arranged copies and token streams of its own: tests/test_plan_host.py has the plan); int16 and
+    s32 elements, and for world 8 also with the scores going straight into a page-locked host matrix, where a block is one tile"""
+    store, scoring, want = short2100
+    monkeypatch.delenv("SA_HIP_CHUNK", raising=False)
+    host = sa.PinnedMatrix(store.pairs) if world == 8 else None
+    try:
+        got = {}
+        for no_tokens in (False, True):
+            if no_tokens:
+                monkeypatch.setenv("SA_HIP_NO_TOKENS", "1")
+            else:
+                monkeypatch.delenv("SA_HIP_NO_TOKENS", raising=False)
+            with sa.Context(store, scoring, 0) as ctx:
+                assert ctx.scores_fit16
+                for elem16 in (True, False):
+                    for dest in [None] + ([host] if host else []):
+                        if dest:
+                            dest.array[:] = -77
+                        key = (elem16, dest is not None)
+                        got[no_tokens, key], lean, legacy = placed_shares(ctx, store.pairs, world, elem16, dest)
+                        assert (lean == 0 and legacy >= 1) if no_tokens else (lean >= 1), (no_tokens, key, lean, legacy)
+                        assert not dest or np.array_equal(dest.array, want), f"world {world} {key} no_tokens {no_tokens}: host matrix differs from the oracle"
+        for (no_tokens, key), v in got.items():
+            assert np.array_equal(v, want), f"world {world} (int16, to_host) {key} no_tokens {no_tokens}: placed vector differs from the oracle"
+            assert np.array_equal(v, got[False, key])
+    finally:
+        if host:
+            host.close()

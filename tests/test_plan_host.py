@@ -9,12 +9,16 @@ cfg 5 is the geometry of the one abort this project has on record (round 3, test
 ranges [k 2^30, +2^30) of the 89 994-sequence post-filter store)."""
 import json
 import pathlib
+import re
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests.synth import make_config
+from tests import token_classes as tc
+from tests.limits_line import parse_limits
+from tests.planner_limits import PK16_F16_KMAX, class_of, form_of
+from tests.synth import make_config, make_protein_set
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 HARNESS = ROOT / "tests" / "plan_host"
@@ -50,9 +54,11 @@ def config_lens(name: str) -> tuple[np.ndarray, dict]:
     return lens, cfg
 
 
-def run(exe, lens_path, method, matrix, gaps, plans, cus=256, timeout=900):
-    argv = [str(exe), str(lens_path), method, matrix, str(gaps.get("gap_pen", 0)), str(gaps.get("gap_open", 0)),
-            str(gaps.get("gap_extend", 0)), str(cus)]
+def run(exe, lens_path, method, matrix, gaps, plans, cus=256, timeout=900, tokens=None):
+    """tokens: SA_HIP_CHUNK of the plans (0: none), and a `tokens:` line per packed class behind every plan"""
+    argv = [str(exe)] + ([] if tokens is None else ["--tokens", str(tokens)])
+    argv += [str(lens_path), method, matrix, str(gaps.get("gap_pen", 0)), str(gaps.get("gap_open", 0)),
+             str(gaps.get("gap_extend", 0)), str(cus)]
     for p in plans:
         argv += [str(int(v)) for v in p]
     res = subprocess.run(argv, capture_output=True, text=True, timeout=timeout)
@@ -128,3 +134,93 @@ def test_oversized_range_is_refused_not_crashed(plan_check, tmp_path):
     out = run(plan_check, lens_file(tmp_path, "huge", lens), "nw", "blosum62", dict(gap_pen=4), [(0, -1, 0, 0), (0, G30, 0, 0)])
     assert "refused: packed range too large for one launch" in out
     assert out.count("plan [") == 2 and out.count("refused") == 1  # the 2^30-pair sub-range plans fine
+
+
+# ---- the stores of tests/test_gpu_token_classes.py: which arranged level every tile of every class streams ----
+TOKENS_LINE = re.compile(r"tokens: G (\d+) K (\d+) f16 (\d) small (\d) wpb (\d+) rows (\d+) lean((?: \d+:\d+)*) legacy (\d+)")
+
+
+def token_plans(out):
+    """per `plan [` line of plan_check --tokens: {(G, K): dict(f16, wpb, rows, lean = {block: tiles}, legacy)}"""
+    plans = []
+    for line in out.splitlines():
+        if line.startswith("plan ["):
+            plans.append({})
+        m = TOKENS_LINE.match(line)
+        if m:
+            assert m[4] == "0", line  # (SA_HIP_CHUNK: one tile size)
+            lean = {int(b): int(n) for b, n in (x.split(":") for x in m[7].split())}
+            plans[-1][int(m[1]), int(m[2])] = dict(f16=m[3] == "1", wpb=int(m[5]), rows=int(m[6]), lean=lean, legacy=int(m[8]))
+    return plans
+
+
+def check_class_tiles(c, g, k, method, tag):
+    """the three kinds of tile the store is built for, in the tile shape the class is meant to have"""
+    waves = 8 if (g == 16 and k >= 45) or (method == "nw" and g == 8 and k >= 17) else 4  # sa_shapes.h: sa_pk_wpb
+    assert c["wpb"] == waves and c["rows"] == waves * (64 // g) * tc.CHUNK, f"{tag}: {c}"
+    assert any(n >= 1 for b, n in c["lean"].items() if b > c["rows"]), f"{tag}: no lean tile inside a larger arranged block: {c}"
+    assert c["lean"].get(c["rows"], 0) >= 1, f"{tag}: no lean tile that is its own block: {c}"
+    assert c["legacy"] >= 1, f"{tag}: no tile that derives its tokens: {c}"
+
+
+@pytest.mark.parametrize("g,klo", tc.BUNDLES, ids=[f"g{g}-klo{klo}" for g, klo in tc.BUNDLES])
+def test_token_class_stores_aim_where_they_claim(g, klo, plan_check, tmp_path):
+    """every class of the bundle is admitted on the form the limits give (nothing goes to the s32 kernels), and -- in the
+    whole range and in the range of its three columns alone -- has lean tiles inside the 256-row arranged block, lean
+    tiles that are their own block, tiles that derive their tokens, and four or eight waves per workgroup as listed"""
+    lens = tc.store_lengths(g, klo)
+    f = lens_file(tmp_path, f"tc_{g}_{klo}", lens)
+    classes = tc.bundle_classes(g, klo)
+    ranges = [(0, -1, 0, 0)]
+    for k in classes:
+        j = tc.first_column(g, klo, k)
+        assert [lens[j + c] for c in range(3)] == tc.column_lengths(g, k)
+        ranges.append((j * (j - 1) // 2, 3 * j + 3, 0, 0))  # tri(j) through the end of column j + 2
+    for method, gaps in tc.METHODS:
+        out = run(plan_check, f, method, tc.MATRIX, gaps, ranges, tokens=tc.CHUNK)
+        lim = parse_limits(out)
+        plans = token_plans(out)
+        assert len(plans) == len(ranges) and "refused" not in out
+        for n, k in enumerate(classes):
+            tag = f"{method} G {g} K {k}"
+            assert class_of(g * k, lim) == (g, k) == class_of(g * k - (g - 1), lim), f"{tag} is not a packed class under {lim}"
+            assert set(plans[1 + n]) == {(g, k)}, f"{tag}: its three columns alone plan {sorted(plans[1 + n])}"
+            for c in (plans[0][g, k], plans[1 + n][g, k]):
+                assert c["f16"] == form_of(g, k, lim)[1], f"{tag}: {c} under {lim}"
+                check_class_tiles(c, g, k, method, tag)
+        if g == 16:  # what these stores count on: the three-way form wherever it exists, the two-way form only beyond
+            assert [k for k in classes if not plans[0][g, k]["f16"]] == [k for k in classes if k > PK16_F16_KMAX], (method, lim)
+
+
+@pytest.mark.parametrize("g,klo", tc.LOW_K_TWO_WAY, ids=[f"g{g}-klo{klo}" for g, klo in tc.LOW_K_TWO_WAY])
+def test_token_class_stores_with_a_one_residue_row(g, klo, plan_check, tmp_path):
+    """a one-residue row in front: the limits move the low 16-lane classes to the two-way u16 form (NW: all of them), and
+    every class they still admit keeps its three kinds of tile"""
+    lens = tc.store_lengths(g, klo, short_row=True)
+    assert lens[0] == 1 and min(lens[1:]) == tc.ROW_MIN
+    f = lens_file(tmp_path, f"tc1_{g}_{klo}", lens)
+    for method, gaps in tc.METHODS:
+        out = run(plan_check, f, method, tc.MATRIX, gaps, [(0, -1, 0, 0)], tokens=tc.CHUNK)
+        lim = parse_limits(out)
+        plan, = token_plans(out)
+        admitted = [k for k in tc.bundle_classes(g, klo) if k <= lim["pk16"]]
+        assert [k for gg, k in sorted(plan) if gg == 16] == admitted and (admitted or klo > 13), (method, lim, sorted(plan))
+        two_way = [k for k in admitted if not plan[g, k]["f16"]]
+        assert two_way == [k for k in admitted if k > lim["f16"]] and (two_way or klo > 13), (method, lim, two_way)
+        for k in admitted:
+            check_class_tiles(plan[g, k], g, k, method, f"{method} G {g} K {k} with a one-residue row")
+
+
+def test_short2100_shares_have_lean_tiles_of_both_sizes(plan_check, tmp_path):
+    """the store of tests/test_gpu_token_streams.py::test_shares_of_two_tile_sizes: world 2 and 8 cut it into two tile sizes
+    (chunk_pk / chunk_pk_small), and both have tiles that stream tokens, host delivery included"""
+    lens = [len(s) for s in make_protein_set(2100, 5, 20, 49)]
+    out = run(plan_check, lens_file(tmp_path, "short2100", lens), "nw", "blosum62", dict(gap_pen=4),
+              [(0, -1, 2, 0), (0, -1, 8, 0), (0, -1, 8, 1)], tokens=0)
+    assert out.count("plan [") == 3 and "refused" not in out
+    blocks = out.split("plan [")[1:]
+    for b in blocks:
+        sizes = {m[4]: 0 for m in TOKENS_LINE.finditer(b)}
+        for m in TOKENS_LINE.finditer(b):
+            sizes[m[4]] += sum(int(x.split(":")[1]) for x in m[7].split())
+        assert set(sizes) == {"0", "1"} and all(sizes.values()), f"plan [{b}"
