@@ -73,7 +73,14 @@ enum sa_gap_kind { SA_GAP_LINEAR = 0, SA_GAP_AFFINE = 1 };
 
 /* Replaces the globals read by cuda_align (src/interface/seqalign_cuda.c:115-123,170).
  * Gap values are the STORED form, i.e. already negated (src/bio/align.c:127-128):
- * `-p 4` -> gap_pen = -4; `-s 10 -e 1` -> gap_opn = -10, gap_ext = -1. */
+ * `-p 4` -> gap_pen = -4; `-s 10 -e 1` -> gap_opn = -10, gap_ext = -1.
+ *
+ * `sub` is data: any 24 x 24 table may be given, symmetric or not (every named matrix is symmetric).  For the pair
+ * (i, j), i < j, j the column sequence, the cell of residue x of i and residue y of j reads, as the reference does
+ * (src/bio/method/nw.c:23,29; ga.c:46; sw.c:39):
+ *     NW           sub[lut[x] * SA_SUB_DIM + lut[y]]      [code of i][code of j]
+ *     Gotoh, SW    sub[lut[y] * SA_SUB_DIM + lut[x]]      [code of j][code of i]
+ * Every kernel family and the traceback keep this order. */
 struct sa_scoring {
 	int32_t method;                        /* enum sa_method                   (ALIGN)    */
 	int32_t gap_pen;                       /* linear gap, used by NW           (GAP_PEN)  */

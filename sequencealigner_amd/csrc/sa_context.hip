@@ -213,9 +213,15 @@ static sa_ctx *ctx_create_impl(int device, struct sa_input in, const struct sa_s
 		ctx->pk_slack = L.pk_slack;
 		ctx->pk_extra = L.pk_extra;
 	}
+	/* the s8 table the systolic profile builders read as sub8[row residue][column residue] (sa_systolic_kernel.inc,
+	 * sa_systolic_pk.inc), the row sequence being the earlier one, i.  `sub` is indexed [i][j] by NW and [j][i] by Gotoh and
+	 * SW (include/seqalign_hip.h; reference nw.c:23,29, ga.c:46, sw.c:39), so for those two the staged copy is the
+	 * transpose.  Every named matrix is symmetric: for them nothing changes. */
+	const bool col_major = sc->method != SA_METHOD_NW;
 	int8_t sub8[SA_SUB_DIM * SA_SUB_DIM];
-	for (int k = 0; k < SA_SUB_DIM * SA_SUB_DIM; k++)
-		sub8[k] = (int8_t)std::max(-128, std::min(127, sc->sub[k]));
+	for (int a = 0; a < SA_SUB_DIM; a++)
+		for (int b = 0; b < SA_SUB_DIM; b++)
+			sub8[a * SA_SUB_DIM + b] = (int8_t)std::max(-128, std::min(127, sc->sub[col_major ? b * SA_SUB_DIM + a : a * SA_SUB_DIM + b]));
 
 	bool ok = false;
 	do {

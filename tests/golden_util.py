@@ -10,7 +10,7 @@ GOLDEN_DIR = pathlib.Path(__file__).resolve().parent / "golden"
 
 
 def golden_cases() -> list[str]:
-    return sorted(p.stem for p in GOLDEN_DIR.glob("*.npz") if not p.stem.startswith(("filter_", "digest_", "stripes_", "oracle_vs_ref")))
+    return sorted(p.stem for p in GOLDEN_DIR.glob("*.npz") if not p.stem.startswith(("filter_", "digest_", "stripes_", "oracle_vs_ref", "tables_vs_ref")))
 
 
 def load_case(name: str):

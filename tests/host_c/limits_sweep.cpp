@@ -8,6 +8,9 @@
  *   limits_sweep <matrix>...                  the grid: methods x gaps 0..60 x shortest 1..32 x longest 8..5000
  *   limits_sweep --print <method> <matrix> <gap_pen> <gap_open> <gap_ext> <max_len> <min_len>     one `limits:` line and the
  *                                                                                         `shapes:` line (sa_shapes.h)
+ *   limits_sweep --print <method> <matrix> ... <min_len> --sub FILE      the same for a table given as data: FILE holds 576
+ *                                                                       integers, used in place of the named matrix's table
+ *                                                                       (<matrix> may then be "-")
  *
  * Exit status 0 = every property held. */
 #include <algorithm>
@@ -114,9 +117,24 @@ int main(int argc, char **argv)
 	if (argc >= 9 && !strcmp(argv[1], "--print")) {
 		sa_scoring sc{};
 		sc.method = sa_method_parse(argv[2]);
-		if (sc.method < 0 || sa_matrix_load(argv[3], sc.lut, sc.sub)) {
+		const bool own_table = argc >= 11 && !strcmp(argv[9], "--sub");
+		if (sc.method < 0 || (!(own_table && !strcmp(argv[3], "-")) && sa_matrix_load(argv[3], sc.lut, sc.sub))) {
 			fprintf(stderr, "%s\n", sa_last_error());
 			return 2;
+		}
+		if (own_table) {
+			FILE *f = fopen(argv[10], "r");
+			int got = 0;
+			long long v;
+			while (f && got < SA_SUB_DIM * SA_SUB_DIM && fscanf(f, "%lld", &v) == 1 && v >= INT32_MIN && v <= INT32_MAX)
+				sc.sub[got++] = (int32_t)v;
+			const bool more = f && fscanf(f, "%lld", &v) == 1;
+			if (f)
+				fclose(f);
+			if (got != SA_SUB_DIM * SA_SUB_DIM || more) {
+				fprintf(stderr, "limits_sweep --sub %s: %d int32 values read, %d expected and no more\n", argv[10], got, SA_SUB_DIM * SA_SUB_DIM);
+				return 2;
+			}
 		}
 		sc.gap_pen = -atoi(argv[4]);
 		sc.gap_opn = -atoi(argv[5]);
@@ -130,7 +148,7 @@ int main(int argc, char **argv)
 		return 0;
 	}
 	if (argc < 2) {
-		fprintf(stderr, "usage: limits_sweep <matrix>... | --print method matrix gap_pen gap_open gap_ext max_len min_len\n");
+		fprintf(stderr, "usage: limits_sweep <matrix>... | --print method matrix gap_pen gap_open gap_ext max_len min_len [--sub FILE]\n");
 		return 2;
 	}
 	static const int EXT[] = { 0, 1, 2, 3, 4, 5, 8, 11, 16, 30, 60 };

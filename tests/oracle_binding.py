@@ -145,6 +145,16 @@ class RefLib:
         return dict(gap_pen=gp.value, gap_opn=go.value, gap_ext=ge.value, affine=bool(aff.value),
                     lut=np.array(lut, np.int32), sub=np.array(sub, np.int32), method=name.value.decode())
 
+    def set_tables(self, lut, sub) -> None:
+        """Overwrites the lut and the substitution table this instance's reference code reads (its exported SEQ_LUT /
+        SUB_MAT data, src/bio/matrices.c:12-13, filled from the named matrix by ref_configure) with a caller's: data
+        written at run time into this instance's private copy of the library, other instances keep theirs."""
+        lut = np.ascontiguousarray(lut, np.int32).reshape(-1)
+        sub = np.ascontiguousarray(sub, np.int32).reshape(-1)
+        assert lut.size == 128 and sub.size == 576
+        C.memmove(C.addressof((C.c_int32 * 128).in_dll(self.lib, "SEQ_LUT")), lut.ctypes.data, 512)
+        C.memmove(C.addressof((C.c_int32 * 576).in_dll(self.lib, "SUB_MAT")), sub.ctypes.data, 2304)
+
     def pair(self, seq1: bytes, seq2: bytes) -> int:
         return int(self.lib.ref_pair(seq1, len(seq1), seq2, len(seq2)))
 

@@ -24,16 +24,22 @@ BUNDLE = re.compile(r"sa_k_systolic_pk_bundle<\w+,(\d+),(\d+),(true|false)>\[K(\
 @pytest.fixture(scope="module")
 def planner(tmp_path_factory):
     """limits(scoring, max_len, min_len) -> the planner's `limits:` line as a dict: the product's sa_kernel_limits, built
-    from the tree with plain g++ (tests/test_limits_host.py runs the same harness under the sanitizers)"""
-    exe = tmp_path_factory.mktemp("limits") / "limits_sweep"
+    from the tree with plain g++ (tests/test_limits_host.py runs the same harness under the sanitizers).  A scoring without
+    a matrix name hands its table over as data (--sub FILE)."""
+    tmp = tmp_path_factory.mktemp("limits")
+    exe = tmp / "limits_sweep"
     srcs = [ROOT / "tests" / "host_c" / "limits_sweep.cpp", CSRC / "sa_plan.cpp", CSRC / "sa_limits.cpp", CSRC / "sa_tables.cpp"]
     subprocess.check_call(["g++", "-std=c++17", "-O1", *map(str, srcs), "-o", str(exe)])
     out = subprocess.run([str(exe), "--print", "nw", "blosum62", "4", "0", "0", "1024", "1"], capture_output=True, text=True, check=True).stdout
     assert parse_shapes(out) == SHAPES, "the class geometry of sa_shapes.h changed: tests/extremal.py and the constants above aim at the wrong lengths"
 
     def limits(scoring, max_len, min_len):
-        argv = [str(exe), "--print", scoring.method_name, scoring.matrix_name, str(-scoring.gap_pen), str(-scoring.gap_opn),
+        argv = [str(exe), "--print", scoring.method_name, scoring.matrix_name or "-", str(-scoring.gap_pen), str(-scoring.gap_opn),
                 str(-scoring.gap_ext), str(int(max_len)), str(int(min_len))]
+        if scoring.matrix_name == "":
+            table = tmp / "sub.txt"
+            table.write_text(" ".join(str(int(v)) for v in scoring.sub))
+            argv += ["--sub", str(table)]
         out = subprocess.run(argv, capture_output=True, text=True, timeout=60, check=True).stdout
         return parse_limits(out)
 
@@ -62,3 +68,21 @@ def form_of(g, k, lim):
         if lanes == g and k <= last:
             return name, name != "pk16-u16"
     return None, None
+
+
+PACKED_FORMS = ("pk8", "pk16-f16", "pk16-u16")
+
+
+def columns_by_form(lens, lim):
+    """{form name or "s32": the columns j >= 1 of a store with these lengths that the limits send there}"""
+    out = {}
+    for j in range(1, len(lens)):
+        cls = class_of(lens[j], lim)
+        out.setdefault(form_of(*cls, lim)[0] if cls else "s32", []).append(j)
+    return out
+
+
+def unreached_forms(lens, lim):
+    """(name, lanes, last admitted K) of the forms the limits admit that no column of the store runs on"""
+    by_form = columns_by_form(lens, lim)
+    return [(name, g, k) for name, g, k, _ in forms(lim) if k and not (name == "pk16-u16" and k <= lim["f16"]) and not by_form.get(name)]

@@ -18,6 +18,7 @@ import pathlib
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 from tests.limits_line import parse_limits, parse_shapes
@@ -79,3 +80,34 @@ def test_limits_line_of_the_boundaries_the_gpu_cases_rely_on(limits_sweep):
     assert line("sw", "blosum62", 0, 12, 3, 1024, 3) == (1, 24, 60, 21, 4)     # SW: chunk cap 4 at 1024 residues
     assert line("sw", "blosum62", 0, 2, 16700, 1000, 1000)[0] == 1             # the last extend the s32 kernels admit ...
     assert line("sw", "blosum62", 0, 2, 16800, 1000, 1000)[0] == 0             # ... and the first they do not
+
+
+def test_limits_of_a_table_given_as_data(limits_sweep, tmp_path, sa):
+    """--print --sub FILE under the sanitizers: a named matrix's own table handed over as data gives the named matrix's line,
+    a malformed file is refused, and the line follows the table's entries -- with gaps of 0 the s32 family ends between the
+    entries 127 and 128, -127 and -128 (the s8 profile, -128 reserved for padding)"""
+    from tests import tables as tb
+
+    def line(method, sub, pen, o, e, longest, shortest, matrix="-", check=True):
+        table = tmp_path / "sub.txt"
+        table.write_text("\n".join(str(int(v)) for v in np.asarray(sub, dtype=np.int64).reshape(-1)))
+        res = subprocess.run([str(limits_sweep), "--print", method, matrix, str(pen), str(o), str(e), str(longest), str(shortest), "--sub", str(table)],
+                             capture_output=True, text=True)
+        assert "ERROR: AddressSanitizer" not in res.stderr and "runtime error" not in res.stderr, res.stderr[-6000:]
+        if not check:
+            return res
+        assert res.returncode == 0, res.stderr[-2000:]
+        return parse_limits(res.stdout)
+
+    for method, matrix, pen, o, e in (("nw", "blosum62", 4, 0, 0), ("ga", "pam250", 0, 30, 2), ("sw", "nuc44", 0, 10, 1)):
+        named = subprocess.run([str(limits_sweep), "--print", method, matrix, str(pen), str(o), str(e), "1024", "3"], capture_output=True, text=True, check=True).stdout
+        gaps = dict(gap_pen=pen) if method == "nw" else dict(gap_open=o, gap_extend=e)
+        assert line(method, sa.Scoring.from_names(method, matrix, **gaps).sub, pen, o, e, 1024, 3) == parse_limits(named)
+    base = tb.asymmetric(1, -4, 11)
+    for method in ("nw", "sw"):
+        assert line(method, tb.with_extremes(base, -127, 127), 0, 0, 0, 1024, 1)["sys_ok"] == 1
+        assert line(method, tb.with_extremes(base, -127, 128), 0, 0, 0, 1024, 1)["sys_ok"] == 0
+        assert line(method, tb.with_extremes(base, -128, 127), 0, 0, 0, 1024, 1)["sys_ok"] == 0
+    assert line("nw", base[:575], 4, 0, 0, 1024, 1, check=False).returncode == 2
+    assert line("nw", list(base) + [1], 4, 0, 0, 1024, 1, check=False).returncode == 2
+    assert line("nw", [2 ** 31] + list(base[1:]), 4, 0, 0, 1024, 1, check=False).returncode == 2

@@ -117,6 +117,7 @@ def main():
     print(f"filter_f0.9: {len(fs)} -> {len(kept)} kept")
 
     oracle_vs_ref()
+    tables_vs_ref()
 
 
 def oracle_vs_ref():
@@ -130,5 +131,19 @@ def oracle_vs_ref():
     print(f"oracle_vs_ref: {len(data)} arrays")
 
 
+def tables_vs_ref():
+    """tests/test_tables_oracle.py's calls to the reference library with tables written into it as data, and its answers"""
+    from tests.test_tables_oracle import live_reference, stored_calls
+    data = {}
+    for key, method, gaps, lut, sub, store in stored_calls(sa):
+        data.update({f"{key}/{k}": v for k, v in live_reference(method, gaps, lut, sub, store).items()})
+        data[f"{key}/gaps"] = np.array(json.dumps(gaps))
+    np.savez_compressed(OUT / "tables_vs_ref.npz", **data)
+    print(f"tables_vs_ref: {len(data)} arrays")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["tables_vs_ref"]:  # this fixture alone: the others stay as they are
+        tables_vs_ref()
+    else:
+        main()
