@@ -857,6 +857,69 @@ int sa_host_write_edges(const char *path, const struct sa_host_store *s, const i
 	return rc;
 }
 
+/* The single-linkage tree (include/seqalign_hip.h: sa_hip_linkage): /linkage_pairs (N - 1) x 2 I32LE and /linkage_scores N - 1
+ * I32LE, contiguous; with `labels` also /cluster_labels N I32LE (--clusters T).  create = 0: added to the finished file at `path`,
+ * whose other datasets stay as they are; create = 1: a new file with /sequences and these, no /similarity_matrix.  The pairs are
+ * checked before anything is opened: every index in [0, N), lo < hi. */
+int sa_host_write_linkage(const char *path, const struct sa_host_store *s, const int32_t *pairs, const int32_t *score, const int32_t *labels,
+			  int create)
+{
+	if (!path || !s)
+		return fail("Linkage data missing");
+	const size_t dim = (size_t)s->in.num;
+	if (dim < 1)
+		return fail("Linkage data missing");
+	const size_t merges = dim - 1;
+	if (merges > 0 && (!pairs || !score))
+		return fail("Linkage data missing");
+	for (size_t t = 0; t < merges; t++) {
+		const int32_t lo = pairs[2 * t], hi = pairs[2 * t + 1];
+		if (lo < 0 || hi < 0 || (size_t)lo >= dim || (size_t)hi >= dim)
+			return fail("Linkage pair %zu (%d, %d) is outside the %zu sequences", t, lo, hi, dim);
+		if (lo >= hi)
+			return fail("Linkage pair %zu (%d, %d) does not have lo < hi", t, lo, hi);
+	}
+	if (labels)
+		for (size_t r = 0; r < dim; r++)
+			if (labels[r] < 0 || (size_t)labels[r] > r)
+				return fail("Cluster label %d of sequence %zu is not the smallest index of a cluster", labels[r], r);
+	hid_t file;
+	if (create) {
+		if (create_with_sequences(path, s, &file))
+			return 1;
+	} else {
+		hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
+		H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
+		H5Pset_alignment(fapl, 4096, 4096);
+		H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
+		H5Pclose(fapl);
+		if (file < 0)
+			return fail("Failed to open HDF5 file: %s", path);
+	}
+	const struct {
+		const char *name;
+		int rank;
+		hsize_t dims[2];
+		const int32_t *data;
+	} sets[3] = { { "/linkage_pairs", 2, { (hsize_t)merges, 2 }, pairs },
+		      { "/linkage_scores", 1, { (hsize_t)merges, 0 }, score },
+		      { "/cluster_labels", 1, { (hsize_t)dim, 0 }, labels } };
+	int rc = 0;
+	for (int d = 0; d < (labels ? 3 : 2) && !rc; d++) {
+		hid_t space = H5Screate_simple(sets[d].rank, sets[d].dims, NULL);
+		hid_t set = H5Dcreate2(file, sets[d].name, H5T_STD_I32LE, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || (sets[d].dims[0] && H5Dwrite(set, H5T_NATIVE_INT32, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
+			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
+		if (set >= 0)
+			H5Dclose(set);
+		H5Sclose(space);
+	}
+	H5Fclose(file);
+	if (rc && create)
+		remove(path);
+	return rc;
+}
+
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder
  * when `compression` > 0, the raw tiles when 0.  Same file, dataset, chunk shape and filter pipeline as sa_host_write_hdf5 --
  * the tiles go to H5Dwrite_chunk as they are, tile row after tile row. */

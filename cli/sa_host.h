@@ -89,6 +89,12 @@ int sa_host_write_alignments(const char *path, const struct sa_host_store *s, in
  * offsets or an index outside [0, N) give an error, and no file when `create` is set. */
 int sa_host_write_edges(const char *path, const struct sa_host_store *s, const int64_t *offsets, const int32_t *index, const int32_t *score,
 			int create);
+/* --linkage / --clusters: /linkage_pairs ((N - 1) x 2 I32LE) and /linkage_scores (N - 1 I32LE), the tree of sa_hip_linkage /
+ * sa_zjob_linkage; with `labels` (or NULL) also /cluster_labels (N I32LE).  `create` as in sa_host_write_edges: 1 writes a new
+ * file with /sequences and these (--linkage-only).  An index outside [0, N), lo >= hi or a label above its own index give an
+ * error, and no file when `create` is set. */
+int sa_host_write_linkage(const char *path, const struct sa_host_store *s, const int32_t *pairs, const int32_t *score, const int32_t *labels,
+			  int create);
 
 #ifdef __cplusplus
 }

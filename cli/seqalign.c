@@ -13,7 +13,10 @@
  *             --alignments   (with -k: the N x K pairs (r, neighbor) traced back on the device, records and CIGARs)
  *             --min-score T  --edges-only   (the score graph: every pair that scores at least T as CSR, built on the device:
  *             /edge_offsets, /edge_indices and /edge_scores; with --edges-only no /similarity_matrix at all)
- * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> score graph -> -B report.
+ *             --linkage  --clusters T  --linkage-only   (the single-linkage tree, built on the device: /linkage_pairs and
+ *             /linkage_scores; with --clusters also /cluster_labels, the connected components of the pairs that score at least T;
+ *             with --linkage-only no /similarity_matrix at all)
+ * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> score graph -> linkage -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
 #define _GNU_SOURCE
@@ -100,6 +103,8 @@ struct options {
 	bool alignments; /* --alignments: the N x K neighbour pairs traced back */
 	bool has_min_score, edges_only; /* --min-score T: the score graph; --edges-only: nothing else */
 	int32_t min_score;
+	bool linkage, linkage_only, has_clusters; /* --linkage: the single-linkage tree; --clusters T: its labels at T as well */
+	int32_t clusters_at;
 };
 
 static void usage(const char *argv0)
@@ -140,6 +145,13 @@ static void usage(const char *argv0)
 	       "                           offsets[r] .. offsets[r + 1], columns ascending)\n"
 	       "      --edges-only         With --min-score: no /similarity_matrix, the matrix never leaves the device\n"
 	       "                           (not together with -k)\n"
+	       "      --linkage            Also write the single-linkage tree (the maximum spanning tree of the scores, built\n"
+	       "                           on the device): /linkage_pairs ((N - 1) x 2, lo < hi) and /linkage_scores (N - 1),\n"
+	       "                           in the order single linkage joins clusters (score descending)\n"
+	       "      --clusters T         The tree, and /cluster_labels (N): the smallest index in each sequence's connected\n"
+	       "                           component of the pairs that score at least T (any 32-bit integer)\n"
+	       "      --linkage-only       The tree, and no /similarity_matrix: the matrix never leaves the device\n"
+	       "                           (not together with -k or --min-score)\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -172,7 +184,8 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "force-proceed", 'F', false }, { "quiet", 'Q', false }, { "verbose", 'V', false },
 		     { "help", 'h', false }, { "column", 1, true }, { "no-header", 2, false },
 		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { "alignments", 4, false },
-		     { "min-score", 5, true }, { "edges-only", 6, false }, { NULL, 0, false } };
+		     { "min-score", 5, true }, { "edges-only", 6, false }, { "linkage", 7, false }, { "clusters", 8, true },
+		     { "linkage-only", 9, false }, { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -290,6 +303,16 @@ static int parse_args(int argc, char **argv, struct options *o)
 				o->min_score = (int32_t)v;
 				break;
 			case 6: o->edges_only = true; break;
+			case 7: o->linkage = true; break;
+			case 8:
+				if (!parse_long(val, INT32_MIN, INT32_MAX, &v)) {
+					err("Cluster score must be an integer between %d and %d", INT32_MIN, INT32_MAX);
+					return 1;
+				}
+				o->linkage = o->has_clusters = true;
+				o->clusters_at = (int32_t)v;
+				break;
+			case 9: o->linkage = o->linkage_only = true; break;
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -374,6 +397,10 @@ int main(int argc, char **argv)
 		ok = (err("Option --edges-only requires --min-score"), false);
 	if (ok && o.edges_only && o.neighbors)
 		ok = (err("Options --edges-only and -k, --neighbors conflict: the neighbors need a pass of their own (use --min-score without --edges-only)"), false);
+	if (ok && o.linkage_only && o.neighbors)
+		ok = (err("Options --linkage-only and -k, --neighbors conflict: the neighbors need a pass of their own (use --linkage without --linkage-only)"), false);
+	if (ok && o.linkage_only && o.has_min_score)
+		ok = (err("Options --linkage-only and --min-score conflict: the score graph needs a pass of its own (use --linkage without --linkage-only)"), false);
 	if (ok && sa_matrix_load(o.matrix, sc.lut, sc.sub))
 		ok = (err("Invalid substitution matrix name"), false);
 	if (ok && (sc.method = sa_method_parse(o.align)) < 0)
@@ -437,7 +464,12 @@ int main(int argc, char **argv)
 	if (o.has_min_score)
 		info("Score graph: pairs that score at least %d%s", o.min_score, o.edges_only ? " (no similarity matrix)" : "");
 
-	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t_edges = 0, t0;
+	if (o.linkage)
+		info("Single-linkage tree%s", o.linkage_only ? " (no similarity matrix)" : "");
+	if (o.has_clusters)
+		info("Clusters: connected components of the pairs that score at least %d", o.clusters_at);
+
+	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t_edges = 0, t_linkage = 0, t0;
 	stamp("options parsed");
 	struct sa_host_store store;
 	t0 = now();
@@ -476,6 +508,9 @@ int main(int argc, char **argv)
 	bool nb_done = false, nb_second_pass = false;
 	sa_edges *edges = NULL;
 	bool eg_second_pass = false;
+	sa_linkage *tree = NULL;
+	bool lk_second_pass = false;
+	int lk_rounds = 0;
 	if (o.neighbors) {
 		nb_index = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
 		nb_score = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
@@ -496,7 +531,7 @@ int main(int argc, char **argv)
 	 * SA_HOST_CPU_DEFLATE=1 keeps zlib at exactly the level asked for (all cores, sa_host_write_hdf5). */
 	const long long npairs = (long long)n * ((long long)n - 1) / 2;
 	const size_t zchunk = sa_host_hdf5_chunk_dim(n);
-	const bool no_matrix = o.neighbors_only || o.edges_only; /* the matrix never leaves the device */
+	const bool no_matrix = o.neighbors_only || o.edges_only || o.linkage_only; /* the matrix never leaves the device */
 	bool device_deflate = !o.no_write && !no_matrix && n > 256 && !getenv("SA_HOST_MATRIX") &&
 			      (o.compression > 0 ? !getenv("SA_HOST_CPU_DEFLATE") && !getenv("SA_HOST_SERIAL_DEFLATE")
 						 /* without -z the same walk returns the tiles as they are: H5Dwrite_chunk instead of H5Dwrite's
@@ -604,8 +639,38 @@ int main(int argc, char **argv)
 				verb("Score graph: %s", sa_last_error());
 			}
 		}
+		if (o.linkage) {
+			tree = sa_zjob_linkage(job);
+			if (tree) {
+				t_linkage = sa_hip_last_linkage_seconds();
+				lk_rounds = sa_hip_last_linkage_rounds();
+				verb("Single-linkage tree built from the device's finished matrix (no second alignment)");
+			} else {
+				verb("Single-linkage tree: %s", sa_last_error());
+			}
+		}
 		sa_zjob_destroy(job);
 		stamp("HDF5 written");
+	} else if (o.linkage_only) {
+		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the tree there, copy back 12 (N - 1) bytes */
+		info("Similarity Matrix stays on the device: the single-linkage tree is built there");
+		t0 = now();
+		tree = sa_hip_linkage(store.in, &sc);
+		if (!tree) {
+			err("%s", sa_last_error());
+			return 1;
+		}
+		const double call = now() - t0;
+		stamp("sa_hip_linkage returned");
+		if (show_progress) {
+			progress_line(1.0, NULL);
+			fputc('\n', stderr);
+			sa_hip_set_progress(NULL, NULL);
+		}
+		t_align = sa_hip_last_align_seconds();
+		t_linkage = sa_hip_last_linkage_seconds();
+		lk_rounds = sa_hip_last_linkage_rounds();
+		t_setup = call > t_align + t_linkage ? call - t_align - t_linkage : 0.0;
 	} else if (o.edges_only) {
 		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the graph there, copy back 8 N + 8 E bytes */
 		info("Similarity Matrix stays on the device: the pairs that score at least %d are selected there", o.min_score);
@@ -756,6 +821,48 @@ int main(int argc, char **argv)
 		}
 		sa_edges_destroy(edges);
 	}
+	if (o.linkage && !tree) {
+		/* as for the neighbours: the matrix of the first pass is not on one device any more */
+		verb("Single-linkage tree: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
+		tree = sa_hip_linkage(store.in, &sc);
+		if (!tree) {
+			err("%s", sa_last_error());
+			return 1;
+		}
+		lk_second_pass = true;
+		t_linkage = sa_hip_last_linkage_seconds();
+		lk_rounds = sa_hip_last_linkage_rounds();
+		stamp("sa_hip_linkage returned");
+	}
+	int32_t lk_merges = 0, cluster_count = 0;
+	if (tree) {
+		const int32_t *lk_pairs = sa_linkage_pairs(tree, &lk_merges), *lk_score = sa_linkage_score(tree);
+		int32_t *labels = NULL;
+		if (o.has_clusters) {
+			labels = malloc(sizeof(int32_t) * (size_t)store.in.num);
+			if (!labels) {
+				err("Out of memory allocating cluster labels");
+				return 1;
+			}
+			cluster_count = sa_linkage_labels(lk_pairs, lk_score, store.in.num, o.clusters_at, labels);
+			if (cluster_count < 0) {
+				err("%s", sa_last_error());
+				return 1;
+			}
+			verb("Clusters: %d at score >= %d", cluster_count, o.clusters_at);
+		}
+		if (!o.no_write) {
+			t0 = now();
+			if (sa_host_write_linkage(o.output, &store, lk_pairs, lk_score, labels, o.linkage_only ? 1 : 0)) {
+				err("%s", sa_host_error());
+				return 1;
+			}
+			t_out += now() - t0;
+			stamp("linkage written");
+		}
+		free(labels);
+		sa_linkage_destroy(tree);
+	}
 	if (o.benchmark) { /* -B: src/util/benchmark.c:50-64 */
 		const double total = t_in + t_filter + t_align + t_out;
 		printf("Timing breakdown:\n  Input: %.3f sec\n  Filter: %.3f sec\n  Alignment: %.3f sec\n  Output: %.3f sec\n"
@@ -764,6 +871,7 @@ int main(int argc, char **argv)
 		printf("  (device set-up and upload, outside the phases as in the reference: %.3f sec)\n", t_setup);
 		printf("  (schedule: %s)\n", device_deflate ? (o.compression ? "column blocks into device memory, their tiles deflated on the device and written meanwhile"
 								       : "column blocks into device memory, their tiles delivered as HDF5 chunks meanwhile")
+				       : o.linkage_only ? "the packed matrix stays in device memory, only the single-linkage tree comes back"
 				       : o.edges_only ? "the packed matrix stays in device memory, only the edges come back"
 				       : o.neighbors_only ? "the packed matrix stays in device memory, only the neighbors come back"
 			       : schedule == 2
@@ -778,6 +886,11 @@ int main(int argc, char **argv)
 		if (o.has_min_score)
 			printf("  (score graph on the device, min score = %d: %lld edges, %.6f sec%s)\n", o.min_score, edge_count, t_edges,
 			       eg_second_pass ? ", after a second alignment pass into device memory" : "");
+		if (o.linkage)
+			printf("  (single-linkage tree on the device: %d merges, %d rounds, %.6f sec%s)\n", lk_merges, lk_rounds, t_linkage,
+			       lk_second_pass ? ", after a second alignment pass into device memory" : "");
+		if (o.has_clusters)
+			printf("  (clusters at score >= %d: %d)\n", o.clusters_at, cluster_count);
 		printf("Alignments per second: %.2f\n", t_align > 0 ? (double)pairs / t_align : 0.0);
 	}
 	if (pinned)

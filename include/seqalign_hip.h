@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors and *_alignments calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge* and *_linkage calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -376,6 +376,47 @@ const int32_t *sa_edges_score(const sa_edges *e);
 void sa_edges_destroy(sa_edges *e);
 /* device time (seconds) of count + scan + fill in the last successful sa_hip_edges / sa_zjob_edges call */
 double sa_hip_last_edges_seconds(void);
+
+/* ---- single-linkage clustering: the whole dendrogram from one pass over the device matrix --------------------------------
+ * No reference counterpart.  A CSR graph at one threshold answers one question; the single-linkage hierarchy of a similarity
+ * matrix is its maximum spanning tree, N - 1 pairs, and cutting that tree at ANY score T leaves exactly the connected
+ * components of the graph score >= T.  Built by Boruvka rounds over the device-resident packed triangle (csrc/sa_linkage.hip).
+ * Total order (part of the contract): for pairs i < j with packed index p = j (j - 1) / 2 + i, pair e comes BEFORE pair f iff
+ * score(e) > score(f), or the scores are equal and p(e) < p(f).  Under this strict order the maximum spanning tree of the
+ * complete graph is unique: the same store and scoring give the same bytes run after run, for any matrix -- all scores equal
+ * and the few distinct scores of SW on DNA included.
+ *   pairs  int32[2 (N - 1)]; pairs[2 t] = lo < pairs[2 t + 1] = hi; the N - 1 tree pairs sorted by that order, best first: the
+ *          order in which Kruskal's algorithm, and so single linkage, joins clusters
+ *   score  int32[N - 1]; the score of each pair
+ * Labels at a threshold (host only, from a tree): labels[r] = the smallest index in r's connected component of the graph
+ * score >= T.  Any int32 T is valid: above the maximum labels[r] = r (N clusters), at or below the minimum all 0 (one cluster).
+ * Merge table (host only, from a tree), in the convention of scipy.cluster.hierarchy: merge t joins clusters
+ * left[t] < right[t]; ids below N are sequences, id N + u is the cluster made by merge u; size[t] = sequences in the new
+ * cluster.  Turning scores into heights is left to the caller. */
+size_t sa_linkage_scratch_bytes(int32_t num);          /* host only */
+/* device-resident, asynchronous on `stream`, no host synchronisation, no allocation: d_packed = whole packed matrix of
+ * ctx's store; d_pairs 2 (N - 1) int32, d_score N - 1 int32, d_scratch sa_linkage_scratch_bytes(N) bytes (8-byte aligned),
+ * contents ignored.  ceil(log2 N) rounds are enqueued; the kernels of a round that finds one component return at once. */
+int sa_ctx_linkage(sa_ctx *ctx, const int32_t *d_packed, int32_t *d_pairs, int32_t *d_score, void *d_scratch, void *stream);
+typedef struct sa_linkage sa_linkage;                   /* owns pairs / score in host memory, like sa_edges */
+/* one call, host in / host out: align into device memory, tree, copy back.  The matrix never leaves the device.  One device
+ * (the first).  NULL + sa_last_error when the packed matrix does not fit; the process goes on working. */
+sa_linkage *sa_hip_linkage(struct sa_input in, const struct sa_scoring *sc);
+/* on a tile job whose device holds the finished packed matrix: when sa_zjob_edges can answer; refused in the same cases */
+sa_linkage *sa_zjob_linkage(sa_zjob *job);
+const int32_t *sa_linkage_pairs(const sa_linkage *l, int32_t *merges);   /* *merges (may be NULL) = N - 1 */
+const int32_t *sa_linkage_score(const sa_linkage *l);
+void sa_linkage_destroy(sa_linkage *l);
+/* device time (seconds) of rounds + sort in the last successful sa_hip_linkage / sa_zjob_linkage call */
+double sa_hip_last_linkage_seconds(void);
+/* ... and the rounds of that call that found more than one component (<= ceil(log2 N)) */
+int sa_hip_last_linkage_rounds(void);
+/* host only, no device.  Both fail through sa_last_error with nothing written for a null argument and for a tree that is not
+ * a tree (an index out of range, lo >= hi, a cycle); sa_linkage_labels also for scores that are not in the contract's order. */
+/* returns the number of clusters, < 0 on a bad tree; labels: N int32 */
+int32_t sa_linkage_labels(const int32_t *pairs, const int32_t *score, int32_t num, int32_t min_score, int32_t *labels);
+/* left, right, size: N - 1 int32 each; 0 on success */
+int sa_linkage_merges(const int32_t *pairs, int32_t num, int32_t *left, int32_t *right, int32_t *size);
 
 /* ---- pair-space planning (host only, no device needed) -------------------
  * DP cells (sum of len_i*len_j) of the packed pair range [start, start+count),

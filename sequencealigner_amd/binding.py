@@ -60,6 +60,8 @@ ABI_SYMBOLS = (
     "sa_hip_last_alignments_seconds", "sa_hip_last_alignments_breakdown",
     "sa_ctx_edge_offsets", "sa_ctx_edge_fill", "sa_hip_edges", "sa_zjob_edges", "sa_edges_offsets", "sa_edges_index", "sa_edges_score",
     "sa_edges_destroy", "sa_hip_last_edges_seconds",
+    "sa_linkage_scratch_bytes", "sa_ctx_linkage", "sa_hip_linkage", "sa_zjob_linkage", "sa_linkage_pairs", "sa_linkage_score",
+    "sa_linkage_destroy", "sa_hip_last_linkage_seconds", "sa_hip_last_linkage_rounds", "sa_linkage_labels", "sa_linkage_merges",
 )
 
 
@@ -223,6 +225,26 @@ def load_library() -> C.CDLL:
     lib.sa_edges_destroy.argtypes = [C.c_void_p]
     lib.sa_edges_destroy.restype = None
     lib.sa_hip_last_edges_seconds.restype = C.c_double
+    lib.sa_linkage_scratch_bytes.argtypes = [C.c_int32]
+    lib.sa_linkage_scratch_bytes.restype = C.c_size_t
+    lib.sa_ctx_linkage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_linkage.restype = C.c_int
+    lib.sa_hip_linkage.argtypes = [_Input, C.POINTER(_Scoring)]
+    lib.sa_hip_linkage.restype = C.c_void_p
+    lib.sa_zjob_linkage.argtypes = [C.c_void_p]
+    lib.sa_zjob_linkage.restype = C.c_void_p
+    lib.sa_linkage_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.sa_linkage_pairs.restype = C.c_void_p
+    lib.sa_linkage_score.argtypes = [C.c_void_p]
+    lib.sa_linkage_score.restype = C.c_void_p
+    lib.sa_linkage_destroy.argtypes = [C.c_void_p]
+    lib.sa_linkage_destroy.restype = None
+    lib.sa_hip_last_linkage_seconds.restype = C.c_double
+    lib.sa_hip_last_linkage_rounds.restype = C.c_int
+    lib.sa_linkage_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.sa_linkage_labels.restype = C.c_int32
+    lib.sa_linkage_merges.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_linkage_merges.restype = C.c_int
     _lib = lib
     return lib
 
@@ -499,6 +521,81 @@ def last_edges_seconds() -> float:
     return float(load_library().sa_hip_last_edges_seconds())
 
 
+def _take_linkage(lib, handle) -> tuple[np.ndarray, np.ndarray]:
+    """copies of the two arrays a sa_linkage handle owns; the handle is destroyed"""
+    if not handle:
+        raise AlignError(_err())
+    try:
+        merges = C.c_int32(0)
+        prs = lib.sa_linkage_pairs(handle, C.byref(merges))
+        sco = lib.sa_linkage_score(handle)
+        m = merges.value
+        pairs = np.ctypeslib.as_array(C.cast(prs, C.POINTER(C.c_int32)), (2 * m,)).copy() if m else np.zeros(0, np.int32)
+        score = np.ctypeslib.as_array(C.cast(sco, C.POINTER(C.c_int32)), (m,)).copy() if m else np.zeros(0, np.int32)
+    finally:
+        lib.sa_linkage_destroy(handle)
+    return pairs.reshape(m, 2), score
+
+
+def hip_linkage(store: SequenceStore, scoring: Scoring) -> tuple[np.ndarray, np.ndarray]:
+    """sa_hip_linkage: the single-linkage tree (the maximum spanning tree of the score matrix), built on the device --
+    (pairs int32 (N - 1, 2) with lo < hi, score int32 (N - 1,)), sorted by score descending, then packed index ascending: the
+    order in which single linkage joins clusters.  The matrix never leaves the device."""
+    lib = load_library()
+    sc = scoring._as_c()
+    return _take_linkage(lib, lib.sa_hip_linkage(store._as_c(), C.byref(sc)))
+
+
+def linkage_scratch_bytes(n: int) -> int:
+    """sa_linkage_scratch_bytes: the device scratch memory Context.linkage needs for n sequences"""
+    return int(load_library().sa_linkage_scratch_bytes(int(n)))
+
+
+def last_linkage_seconds() -> float:
+    """device time of rounds + sort in the last hip_linkage / DeflateJob.linkage call"""
+    return float(load_library().sa_hip_last_linkage_seconds())
+
+
+def last_linkage_rounds() -> int:
+    """rounds of the last hip_linkage / DeflateJob.linkage call that found more than one component"""
+    return int(load_library().sa_hip_last_linkage_rounds())
+
+
+def _tree_arrays(pairs, score, n: int):
+    n = int(n)
+    if not 1 <= n < 2**31:
+        raise AlignError(f"n = {n} is not a number of sequences")
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1)
+    if pairs.size != 2 * (n - 1):
+        raise AlignError(f"pairs holds {pairs.size} elements, a tree of {n} sequences has {2 * (n - 1)}")
+    if score is not None:
+        score = np.ascontiguousarray(score, np.int32).reshape(-1)
+        if score.size != n - 1:
+            raise AlignError(f"score holds {score.size} elements, a tree of {n} sequences has {n - 1}")
+    return n, pairs, score
+
+
+def linkage_labels(pairs, score, n: int, min_score: int) -> tuple[np.ndarray, int]:
+    """sa_linkage_labels (host only): (labels int32 (N,), clusters) -- labels[r] is the smallest index in r's connected
+    component of the graph score >= min_score, from the tree alone.  Any int32 threshold is valid."""
+    n, pairs, score = _tree_arrays(pairs, score, n)
+    labels = np.empty(n, np.int32)
+    clusters = load_library().sa_linkage_labels(pairs.ctypes.data, score.ctypes.data, n, _min_score(min_score), labels.ctypes.data)
+    if clusters < 0:
+        raise AlignError(_err())
+    return labels, int(clusters)
+
+
+def linkage_merges(pairs, n: int) -> np.ndarray:
+    """sa_linkage_merges (host only): int32 (N - 1, 3), rows (left, right, size) in the convention of scipy.cluster.hierarchy:
+    ids below N are sequences, id N + u is the cluster made by merge u"""
+    n, pairs, _ = _tree_arrays(pairs, None, n)
+    out = np.empty((3, max(n - 1, 1)), np.int32)
+    if load_library().sa_linkage_merges(pairs.ctypes.data, n, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data):
+        raise AlignError(_err())
+    return np.ascontiguousarray(out[:, :n - 1].T)
+
+
 #: struct sa_aln
 ALN_DTYPE = np.dtype([("score", "<i4"), ("a_begin", "<i4"), ("a_end", "<i4"), ("b_begin", "<i4"), ("b_end", "<i4"),
                       ("columns", "<i4"), ("identities", "<i4"), ("cigar_len", "<i4"), ("cigar_off", "<i8")])
@@ -757,6 +854,13 @@ class Context:
                                       C.c_void_p(d_index_ptr), C.c_void_p(d_score_ptr), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def linkage(self, d_packed_ptr: int, d_pairs_ptr: int, d_score_ptr: int, d_scratch_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_linkage: from the whole packed device matrix of this store, the single-linkage tree into the device arrays
+        d_pairs (2 (N - 1) int32) / d_score (N - 1 int32), asynchronously on `stream`; d_scratch: linkage_scratch_bytes(N) bytes"""
+        if self._lib.sa_ctx_linkage(self._h, C.c_void_p(d_packed_ptr), C.c_void_p(d_pairs_ptr), C.c_void_p(d_score_ptr),
+                                    C.c_void_p(d_scratch_ptr), C.c_void_p(stream)):
+            raise AlignError(_err())
+
     def alignments(self, pairs) -> Alignments:
         """sa_ctx_alignments: the alignments of the listed pairs of this context's store (see hip_alignments)"""
         arr = _pairs_array(pairs)
@@ -840,6 +944,11 @@ class DeflateJob:
         """sa_zjob_edges: (offsets, index, score) as hip_edges returns them, from the finished packed matrix this job's device
         holds -- after next() has returned [] for a begin() job; raises when the matrix is dealt over several jobs"""
         return _take_edges(self._lib, self._lib.sa_zjob_edges(self._h, _min_score(min_score)))
+
+    def linkage(self) -> tuple[np.ndarray, np.ndarray]:
+        """sa_zjob_linkage: (pairs, score) as hip_linkage returns them, from the finished packed matrix this job's device
+        holds -- after next() has returned [] for a begin() job; raises when the matrix is dealt over several jobs"""
+        return _take_linkage(self._lib, self._lib.sa_zjob_linkage(self._h))
 
     def stats(self) -> dict:
         e, c, r, o = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()

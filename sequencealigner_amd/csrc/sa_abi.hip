@@ -527,6 +527,28 @@ extern "C" sa_edges *sa_hip_edges(struct sa_input in, const struct sa_scoring *s
 	return sa_guard("sa_hip_edges", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score); });
 }
 
+static sa_linkage *linkage_impl(struct sa_input in, const struct sa_scoring *sc)
+{
+	if (!sc) {
+		sa_set_error("sa_hip_linkage: null argument");
+		return nullptr;
+	}
+	DeviceRun run;
+	if (!run.begin("sa_hip_linkage", in, sc))
+		return nullptr;
+	sa_linkage *res = sa_linkage_to_host("sa_hip_linkage", run.d_packed, in.num, run.stream);
+	if (res && !run.finish()) {
+		sa_linkage_destroy(res);
+		res = nullptr;
+	}
+	return res;
+}
+
+extern "C" sa_linkage *sa_hip_linkage(struct sa_input in, const struct sa_scoring *sc)
+{
+	return sa_guard("sa_hip_linkage", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc); });
+}
+
 extern "C" int sa_hip_last_align_path(void) { return g_last_align_path.load(); }
 
 extern "C" int sa_hip_last_align_breakdown(double *ms, int n)

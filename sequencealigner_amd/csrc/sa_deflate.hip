@@ -1310,6 +1310,32 @@ extern "C" sa_edges *sa_zjob_edges(sa_zjob *z, int32_t min_score)
 	});
 }
 
+/* The single-linkage tree of the job's packed matrix (sa_linkage.hip), in order behind whatever the job has on its stream.
+ * Refuses what sa_zjob_edges refuses, for the same reasons. */
+extern "C" sa_linkage *sa_zjob_linkage(sa_zjob *z)
+{
+	return sa_guard("sa_zjob_linkage", (sa_linkage *)nullptr, [&]() -> sa_linkage * {
+		if (!z) {
+			sa_set_error("sa_zjob_linkage: null argument");
+			return nullptr;
+		}
+		if (!z->peers.empty()) {
+			sa_set_error("sa_zjob_linkage: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+			return nullptr;
+		}
+		if (!z->d_packed) {
+			sa_set_error("sa_zjob_linkage: the job walks a full matrix; the tree reads the packed index");
+			return nullptr;
+		}
+		if (z->shells && z->next_batch < zjob_batches(z)) {
+			sa_set_error("sa_zjob_linkage: the walk is not finished (sa_zjob_next has not returned 0 yet)");
+			return nullptr;
+		}
+		SA_HIP_CHECK(hipSetDevice(z->device), return nullptr);
+		return sa_linkage_to_host("sa_zjob_linkage", z->d_packed, z->num, z->stream);
+	});
+}
+
 /* one device's part of a walk in shells: context, the packed matrix (whole: a block's place in it is its own), a job over
  * the column blocks `first`, `first + step`, ...; the first two of them are on their way when this returns */
 static sa_zjob *zjob_begin_on(int device, struct sa_input in, const struct sa_scoring *sc, size_t chunk_dim, int level, int first, int step)

@@ -122,4 +122,9 @@ bool sa_neighbors_to_host(const int32_t *d_packed, int32_t num, int32_t k, int32
 struct sa_edges;
 sa_edges *sa_edges_to_host(const char *who, const int32_t *d_packed, int32_t num, int32_t min_score, hipStream_t s);
 
+/* single-linkage tree (sa_linkage.hip): the maximum spanning tree of a packed device matrix into host memory, in order on `s`,
+ * which is synchronised; the device time of rounds + sort goes to sa_hip_last_linkage_seconds.  nullptr + sa_set_error on failure. */
+struct sa_linkage;
+sa_linkage *sa_linkage_to_host(const char *who, const int32_t *d_packed, int32_t num, hipStream_t s);
+
 #endif /* SA_INTERNAL_H */
