@@ -920,6 +920,66 @@ int sa_host_write_linkage(const char *path, const struct sa_host_store *s, const
 	return rc;
 }
 
+/* Order statistics of the scores (include/seqalign_hip.h: sa_hip_select): /score_quantiles m F64LE (the fractions as given),
+ * /score_quantile_values m I32LE and /score_quantile_below m I64LE, contiguous; with `edge_min` also /edge_min_score 1 I32LE
+ * (--min-quantile), with `cluster_min` also /cluster_min_score 1 I32LE (--clusters-quantile).  create = 0: added to the finished
+ * file at `path`, whose other datasets stay as they are; create = 1: a new file with /sequences and these.  The arrays are checked
+ * before anything is opened: 1 <= m <= 16, every fraction in [0, 1], every count in [0, P). */
+int sa_host_write_quantiles(const char *path, const struct sa_host_store *s, const double *fractions, const int32_t *values,
+			    const int64_t *below, int32_t m, const int32_t *edge_min, const int32_t *cluster_min, int create)
+{
+	if (!path || !s || !fractions || !values || !below)
+		return fail("Quantile data missing");
+	if (m < 1 || m > 16)
+		return fail("Quantile count %d is outside 1-16", m);
+	const int64_t pairs = (int64_t)s->in.num * ((int64_t)s->in.num - 1) / 2;
+	for (int32_t t = 0; t < m; t++) {
+		if (!(fractions[t] >= 0.0 && fractions[t] <= 1.0))
+			return fail("Quantile %d is not a fraction between 0 and 1", t);
+		if (below[t] < 0 || below[t] >= pairs)
+			return fail("Quantile %d has %lld pairs below it, outside the %lld pairs", t, (long long)below[t], (long long)pairs);
+	}
+	hid_t file;
+	if (create) {
+		if (create_with_sequences(path, s, &file))
+			return 1;
+	} else {
+		hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
+		H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
+		H5Pset_alignment(fapl, 4096, 4096);
+		H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
+		H5Pclose(fapl);
+		if (file < 0)
+			return fail("Failed to open HDF5 file: %s", path);
+	}
+	const struct {
+		const char *name;
+		hsize_t extent;
+		hid_t file_type, mem_type;
+		const void *data;
+	} sets[5] = { { "/score_quantiles", (hsize_t)m, H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, fractions },
+		      { "/score_quantile_values", (hsize_t)m, H5T_STD_I32LE, H5T_NATIVE_INT32, values },
+		      { "/score_quantile_below", (hsize_t)m, H5T_STD_I64LE, H5T_NATIVE_INT64, below },
+		      { "/edge_min_score", 1, H5T_STD_I32LE, H5T_NATIVE_INT32, edge_min },
+		      { "/cluster_min_score", 1, H5T_STD_I32LE, H5T_NATIVE_INT32, cluster_min } };
+	int rc = 0;
+	for (int d = 0; d < 5 && !rc; d++) {
+		if (!sets[d].data)
+			continue;
+		hid_t space = H5Screate_simple(1, &sets[d].extent, NULL);
+		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0)
+			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
+		if (set >= 0)
+			H5Dclose(set);
+		H5Sclose(space);
+	}
+	H5Fclose(file);
+	if (rc && create)
+		remove(path);
+	return rc;
+}
+
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder
  * when `compression` > 0, the raw tiles when 0.  Same file, dataset, chunk shape and filter pipeline as sa_host_write_hdf5 --
  * the tiles go to H5Dwrite_chunk as they are, tile row after tile row. */

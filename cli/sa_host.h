@@ -95,6 +95,13 @@ int sa_host_write_edges(const char *path, const struct sa_host_store *s, const i
  * error, and no file when `create` is set. */
 int sa_host_write_linkage(const char *path, const struct sa_host_store *s, const int32_t *pairs, const int32_t *score, const int32_t *labels,
 			  int create);
+/* --min-quantile / --clusters-quantile / --quantiles: /score_quantiles (m F64LE, the fractions as given), /score_quantile_values
+ * (m I32LE) and /score_quantile_below (m I64LE), what sa_hip_select / sa_zjob_select returned for the ranks of the fractions; with
+ * `edge_min` (or NULL) also /edge_min_score (1 I32LE), with `cluster_min` (or NULL) also /cluster_min_score (1 I32LE).  `create` as
+ * in sa_host_write_edges.  An m outside 1-16, a fraction outside [0, 1] or a count outside [0, P) give an error, and no file when
+ * `create` is set. */
+int sa_host_write_quantiles(const char *path, const struct sa_host_store *s, const double *fractions, const int32_t *values,
+			    const int64_t *below, int32_t m, const int32_t *edge_min, const int32_t *cluster_min, int create);
 
 #ifdef __cplusplus
 }

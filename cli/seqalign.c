@@ -16,6 +16,9 @@
  *             --linkage  --clusters T  --linkage-only   (the single-linkage tree, built on the device: /linkage_pairs and
  *             /linkage_scores; with --clusters also /cluster_labels, the connected components of the pairs that score at least T;
  *             with --linkage-only no /similarity_matrix at all)
+ *             --min-quantile Q  --clusters-quantile Q  --quantiles Q1,Q2,...   (the cut as a fraction of the score distribution:
+ *             the score at rank min(P - 1, floor(Q P)) of the P pair scores in ascending order, selected on the device by one
+ *             sa_*_select call for all of them: /score_quantiles, /score_quantile_values, /score_quantile_below)
  * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> score graph -> linkage -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
@@ -105,6 +108,10 @@ struct options {
 	int32_t min_score;
 	bool linkage, linkage_only, has_clusters; /* --linkage: the single-linkage tree; --clusters T: its labels at T as well */
 	int32_t clusters_at;
+	/* --min-quantile Q, --clusters-quantile Q, --quantiles Q1,...: the fractions as given, one select call for all of them;
+	 * min_q / clusters_q: which of them sets min_score / clusters_at (-1: none) */
+	double quantiles[SA_HIP_SELECT_MAX];
+	int nquant, min_q, clusters_q;
 };
 
 static void usage(const char *argv0)
@@ -152,11 +159,24 @@ static void usage(const char *argv0)
 	       "                           component of the pairs that score at least T (any 32-bit integer)\n"
 	       "      --linkage-only       The tree, and no /similarity_matrix: the matrix never leaves the device\n"
 	       "                           (not together with -k or --min-score)\n"
+	       "      --min-quantile Q     --min-score at T = the score at rank min(P - 1, floor(Q P)) of the P pair scores in\n"
+	       "                           ascending order, 0 <= Q <= 1: at least the best (1 - Q) of the pairs (0.99: the best\n"
+	       "                           1 %%).  T is selected on the device and written as /edge_min_score; works with\n"
+	       "                           --edges-only; not together with --min-score\n"
+	       "      --clusters-quantile Q  --clusters at that T, written as /cluster_min_score; works with --linkage-only;\n"
+	       "                           not together with --clusters\n"
+	       "      --quantiles Q1,Q2,...  Also write the scores at these fractions.  All fractions of the three options\n"
+	       "                           (16 at most together) come from one selection: /score_quantiles (the fractions),\n"
+	       "                           /score_quantile_values (the scores) and /score_quantile_below (pairs scoring less)\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
 	       argv0);
 }
+
+/* a fraction in [0, 1] (no NaN, nothing behind it) onto the list of an option set; false + message otherwise */
+struct options;
+static bool add_quantile(struct options *o, const char *s, size_t len, int *at);
 
 static bool parse_long(const char *s, long lo, long hi, long *out)
 {
@@ -166,6 +186,31 @@ static bool parse_long(const char *s, long lo, long hi, long *out)
 	if (errno || end == s || *end || v < lo || v > hi)
 		return false;
 	*out = v;
+	return true;
+}
+
+static bool add_quantile(struct options *o, const char *s, size_t len, int *at)
+{
+	char text[64], *end;
+	if (len == 0 || len >= sizeof(text)) {
+		err("Quantile must be a number between 0 and 1");
+		return false;
+	}
+	memcpy(text, s, len);
+	text[len] = 0;
+	errno = 0;
+	const double q = strtod(text, &end);
+	if (errno || end == text || *end || !(q >= 0.0 && q <= 1.0)) {
+		err("Quantile must be a number between 0 and 1: %s", text);
+		return false;
+	}
+	if (o->nquant >= SA_HIP_SELECT_MAX) {
+		err("At most %d quantiles in all (--min-quantile, --clusters-quantile and --quantiles together)", SA_HIP_SELECT_MAX);
+		return false;
+	}
+	if (at)
+		*at = o->nquant;
+	o->quantiles[o->nquant++] = q;
 	return true;
 }
 
@@ -185,8 +230,9 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "help", 'h', false }, { "column", 1, true }, { "no-header", 2, false },
 		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { "alignments", 4, false },
 		     { "min-score", 5, true }, { "edges-only", 6, false }, { "linkage", 7, false }, { "clusters", 8, true },
-		     { "linkage-only", 9, false }, { NULL, 0, false } };
-	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1 };
+		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
+		     { "quantiles", 12, true }, { NULL, 0, false } };
+	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
 		if (arg[0] != '-' || !arg[1]) {
@@ -313,6 +359,33 @@ static int parse_args(int argc, char **argv, struct options *o)
 				o->clusters_at = (int32_t)v;
 				break;
 			case 9: o->linkage = o->linkage_only = true; break;
+			case 10:
+				if (o->min_q >= 0) {
+					err("Option --min-quantile given twice");
+					return 1;
+				}
+				if (!add_quantile(o, val, strlen(val), &o->min_q))
+					return 1;
+				break;
+			case 11:
+				if (o->clusters_q >= 0) {
+					err("Option --clusters-quantile given twice");
+					return 1;
+				}
+				if (!add_quantile(o, val, strlen(val), &o->clusters_q))
+					return 1;
+				o->linkage = true;
+				break;
+			case 12:
+				for (const char *p = val;;) {
+					const char *comma = strchr(p, ',');
+					if (!add_quantile(o, p, comma ? (size_t)(comma - p) : strlen(p), NULL))
+						return 1;
+					if (!comma)
+						break;
+					p = comma + 1;
+				}
+				break;
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -393,8 +466,16 @@ int main(int argc, char **argv)
 		ok = (err("Option --neighbors-only requires -k, --neighbors"), false);
 	if (ok && o.alignments && !o.neighbors)
 		ok = (err("Option --alignments requires -k, --neighbors"), false);
+	if (ok && o.has_min_score && o.min_q >= 0)
+		ok = (err("Options --min-score and --min-quantile conflict: one threshold for the score graph"), false);
+	if (ok && o.has_clusters && o.clusters_q >= 0)
+		ok = (err("Options --clusters and --clusters-quantile conflict: one threshold for the clusters"), false);
+	if (ok && o.min_q >= 0)
+		o.has_min_score = true; /* (min_score itself follows from the selection) */
+	if (ok && o.clusters_q >= 0)
+		o.has_clusters = true;
 	if (ok && o.edges_only && !o.has_min_score)
-		ok = (err("Option --edges-only requires --min-score"), false);
+		ok = (err("Option --edges-only requires --min-score or --min-quantile"), false);
 	if (ok && o.edges_only && o.neighbors)
 		ok = (err("Options --edges-only and -k, --neighbors conflict: the neighbors need a pass of their own (use --min-score without --edges-only)"), false);
 	if (ok && o.linkage_only && o.neighbors)
@@ -461,13 +542,20 @@ int main(int argc, char **argv)
 		info("Filter threshold: %.1f%%", (double)o.filter * 100.0);
 	if (o.neighbors)
 		info("Neighbors: %d per sequence%s", o.neighbors, o.neighbors_only ? " (no similarity matrix)" : "");
-	if (o.has_min_score)
+	if (o.min_q >= 0)
+		info("Score graph: pairs that score at least the %g quantile of the scores%s", o.quantiles[o.min_q],
+		     o.edges_only ? " (no similarity matrix)" : "");
+	else if (o.has_min_score)
 		info("Score graph: pairs that score at least %d%s", o.min_score, o.edges_only ? " (no similarity matrix)" : "");
 
 	if (o.linkage)
 		info("Single-linkage tree%s", o.linkage_only ? " (no similarity matrix)" : "");
-	if (o.has_clusters)
+	if (o.clusters_q >= 0)
+		info("Clusters: connected components of the pairs that score at least the %g quantile of the scores", o.quantiles[o.clusters_q]);
+	else if (o.has_clusters)
 		info("Clusters: connected components of the pairs that score at least %d", o.clusters_at);
+	if (o.nquant)
+		info("Score quantiles: %d, selected on the device", o.nquant);
 
 	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t_edges = 0, t_linkage = 0, t0;
 	stamp("options parsed");
@@ -503,6 +591,18 @@ int main(int argc, char **argv)
 		err("Neighbor count %d exceeds the %d other sequences", o.neighbors, store.in.num - 1);
 		fprintf(stderr, "Use %s -h, --help for usage information\n", argv[0]);
 		return 1;
+	}
+	/* the ranks of the fractions: P is known now.  One select call answers all of them (q_done), where the matrix is */
+	int64_t q_ranks[SA_HIP_SELECT_MAX], q_below[SA_HIP_SELECT_MAX];
+	int32_t q_values[SA_HIP_SELECT_MAX];
+	bool q_done = false, q_second_pass = false;
+	double t_quant = 0;
+	for (int t = 0; t < o.nquant; t++) {
+		q_ranks[t] = sa_score_rank((int64_t)store.in.num * ((int64_t)store.in.num - 1) / 2, o.quantiles[t]);
+		if (q_ranks[t] < 0) {
+			err("Score quantiles need at least two sequences");
+			return 1;
+		}
 	}
 	int32_t *nb_index = NULL, *nb_score = NULL;
 	bool nb_done = false, nb_second_pass = false;
@@ -630,7 +730,18 @@ int main(int argc, char **argv)
 				verb("Neighbors: %s", sa_last_error());
 			}
 		}
-		if (o.has_min_score) {
+		if (o.nquant) { /* first: the cut of what follows */
+			if (sa_zjob_select(job, q_ranks, o.nquant, q_values, q_below) == 0) {
+				q_done = true;
+				t_quant = sa_hip_last_select_seconds();
+				if (o.min_q >= 0)
+					o.min_score = q_values[o.min_q];
+				verb("Score quantiles selected from the device's finished matrix (no second alignment)");
+			} else {
+				verb("Score quantiles: %s", sa_last_error());
+			}
+		}
+		if (o.has_min_score && (o.min_q < 0 || q_done)) {
 			edges = sa_zjob_edges(job, o.min_score);
 			if (edges) {
 				t_edges = sa_hip_last_edges_seconds();
@@ -655,10 +766,14 @@ int main(int argc, char **argv)
 		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the tree there, copy back 12 (N - 1) bytes */
 		info("Similarity Matrix stays on the device: the single-linkage tree is built there");
 		t0 = now();
-		tree = sa_hip_linkage(store.in, &sc);
+		tree = o.nquant ? sa_hip_linkage_with_ranks(store.in, &sc, q_ranks, o.nquant, q_values, q_below) : sa_hip_linkage(store.in, &sc);
 		if (!tree) {
 			err("%s", sa_last_error());
 			return 1;
+		}
+		if (o.nquant) {
+			q_done = true;
+			t_quant = sa_hip_last_select_seconds();
 		}
 		const double call = now() - t0;
 		stamp("sa_hip_linkage returned");
@@ -673,9 +788,31 @@ int main(int argc, char **argv)
 		t_setup = call > t_align + t_linkage ? call - t_align - t_linkage : 0.0;
 	} else if (o.edges_only) {
 		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the graph there, copy back 8 N + 8 E bytes */
-		info("Similarity Matrix stays on the device: the pairs that score at least %d are selected there", o.min_score);
+		if (o.min_q >= 0)
+			info("Similarity Matrix stays on the device: the cut and the pairs at or above it are selected there");
+		else
+			info("Similarity Matrix stays on the device: the pairs that score at least %d are selected there", o.min_score);
 		t0 = now();
-		edges = sa_hip_edges(store.in, &sc, o.min_score);
+		if (o.min_q >= 0 && o.nquant == 1) { /* one alignment: the cut and the graph from the same device matrix */
+			edges = sa_hip_edges_at_rank(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0]);
+		} else {
+			if (o.nquant) { /* further fractions: one select call for all of them, in a pass of its own */
+				if (!sa_hip_select(store.in, &sc, q_ranks, o.nquant, q_values, q_below)) {
+					err("%s", sa_last_error());
+					return 1;
+				}
+				q_second_pass = true;
+			}
+			if (o.min_q >= 0)
+				o.min_score = q_values[o.min_q];
+			edges = sa_hip_edges(store.in, &sc, o.min_score);
+		}
+		if (edges && o.nquant) {
+			q_done = true;
+			t_quant = sa_hip_last_select_seconds();
+			if (o.min_q >= 0)
+				o.min_score = q_values[o.min_q];
+		}
 		if (!edges) {
 			err("%s", sa_last_error());
 			return 1;
@@ -793,6 +930,49 @@ int main(int argc, char **argv)
 		}
 		sa_alns_destroy(alns);
 	}
+	if (o.nquant && !q_done) {
+		/* as for the neighbours: the matrix of the first pass is not on one device any more.  With what the cut feeds where one
+		 * alignment can serve both, by itself otherwise */
+		verb("Score quantiles: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
+		bool got;
+		if (o.min_q >= 0 && o.nquant == 1 && !edges) {
+			edges = sa_hip_edges_at_rank(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0]);
+			got = edges != NULL;
+			if (got) {
+				eg_second_pass = true;
+				t_edges = sa_hip_last_edges_seconds();
+			}
+		} else if (o.linkage && !tree) {
+			tree = sa_hip_linkage_with_ranks(store.in, &sc, q_ranks, o.nquant, q_values, q_below);
+			got = tree != NULL;
+			if (got) {
+				lk_second_pass = true;
+				t_linkage = sa_hip_last_linkage_seconds();
+				lk_rounds = sa_hip_last_linkage_rounds();
+			}
+		} else {
+			got = sa_hip_select(store.in, &sc, q_ranks, o.nquant, q_values, q_below);
+		}
+		if (!got) {
+			err("%s", sa_last_error());
+			return 1;
+		}
+		q_done = q_second_pass = true;
+		t_quant = sa_hip_last_select_seconds();
+		stamp("score quantiles returned");
+	}
+	if (q_done) {
+		if (o.min_q >= 0) {
+			o.min_score = q_values[o.min_q];
+			info("Score graph: T = %d, the score at rank %lld of %lld: %lld pairs score at least T", o.min_score, (long long)q_ranks[o.min_q],
+			     npairs, npairs - (long long)q_below[o.min_q]);
+		}
+		if (o.clusters_q >= 0) {
+			o.clusters_at = q_values[o.clusters_q];
+			info("Clusters: T = %d, the score at rank %lld of %lld: %lld pairs score at least T", o.clusters_at,
+			     (long long)q_ranks[o.clusters_q], npairs, npairs - (long long)q_below[o.clusters_q]);
+		}
+	}
 	if (o.has_min_score && !edges) {
 		/* as for the neighbours: the matrix of the first pass is not on one device any more */
 		verb("Score graph: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
@@ -863,6 +1043,17 @@ int main(int argc, char **argv)
 		free(labels);
 		sa_linkage_destroy(tree);
 	}
+	if (q_done && !o.no_write) {
+		/* last: whatever was asked for beside the quantiles has made the file by now */
+		t0 = now();
+		if (sa_host_write_quantiles(o.output, &store, o.quantiles, q_values, q_below, o.nquant, o.min_q >= 0 ? &o.min_score : NULL,
+					    o.clusters_q >= 0 ? &o.clusters_at : NULL, 0)) {
+			err("%s", sa_host_error());
+			return 1;
+		}
+		t_out += now() - t0;
+		stamp("quantiles written");
+	}
 	if (o.benchmark) { /* -B: src/util/benchmark.c:50-64 */
 		const double total = t_in + t_filter + t_align + t_out;
 		printf("Timing breakdown:\n  Input: %.3f sec\n  Filter: %.3f sec\n  Alignment: %.3f sec\n  Output: %.3f sec\n"
@@ -883,6 +1074,9 @@ int main(int argc, char **argv)
 		if (o.alignments)
 			printf("  (alignments of the %lld neighbor pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
 			       (long long)store.in.num * o.neighbors, t_trace, trace_runs);
+		if (o.nquant)
+			printf("  (Score quantiles on the device: %d ranks of %lld pairs, %.6f sec%s)\n", o.nquant, npairs, t_quant,
+			       q_second_pass ? ", after a second alignment pass into device memory" : "");
 		if (o.has_min_score)
 			printf("  (score graph on the device, min score = %d: %lld edges, %.6f sec%s)\n", o.min_score, edge_count, t_edges,
 			       eg_second_pass ? ", after a second alignment pass into device memory" : "");

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge* and *_linkage calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -417,6 +417,42 @@ int sa_hip_last_linkage_rounds(void);
 int32_t sa_linkage_labels(const int32_t *pairs, const int32_t *score, int32_t num, int32_t min_score, int32_t *labels);
 /* left, right, size: N - 1 int32 each; 0 on success */
 int sa_linkage_merges(const int32_t *pairs, int32_t num, int32_t *left, int32_t *right, int32_t *size);
+
+/* ---- score distribution: exact order statistics of the matrix, selected on the device -------------------------------------
+ * No reference counterpart.  --min-score and --clusters cut at a score T; a sensible T is a property of the score distribution
+ * ("the best 1 % of the pairs"), and the scores are on the device when the alignment ends.
+ * Contract: let s_0 <= s_1 <= ... <= s_{P-1} be the P = N (N - 1) / 2 entries of the packed triangle in ascending order, each
+ * unordered pair once.  For a rank k, 0 <= k < P:
+ *   value  int32: s_k
+ *   below  int64: the number of pairs with score < s_k
+ * So P - below pairs score at least value: sa_hip_edges with min_score = value gives E = 2 (P - below) edges, and cutting the
+ * single-linkage tree at value leaves the components of exactly those pairs.
+ * A call takes m ranks, 1 <= m <= SA_HIP_SELECT_MAX, in any order, duplicates allowed; results come back in the caller's order.
+ * A rank outside [0, P), an m outside its range, N < 2 and a null pointer fail through sa_last_error with nothing written.  The
+ * result is exact for any int32 contents, INT32_MIN and INT32_MAX included, and is the same bytes run after run: a radix select
+ * (four passes over the matrix, csrc/sa_select.hip) whose only shared state are integer counts, which do not depend on which
+ * workgroup or wave arrives first.
+ * Fraction to rank (host only): sa_score_rank(pairs, q) = min(pairs - 1, (int64_t)floor(q * (double)pairs)) for 0 <= q <= 1, the
+ * product being the plain IEEE double product (Python: min(P - 1, int(q * P))); q = 0 is the minimum, q = 1 the maximum;
+ * -1 for a NaN, a q outside [0, 1] or pairs < 1. */
+#define SA_HIP_SELECT_MAX 16
+size_t  sa_select_scratch_bytes(int32_t m);                    /* host only; 0 for an m outside 1 .. SA_HIP_SELECT_MAX */
+int64_t sa_score_rank(int64_t pairs, double q);                /* host only */
+/* device-resident, asynchronous on `stream`, no host synchronisation, no allocation.  d_packed = whole packed matrix of
+ * ctx's store (4-byte aligned: an offset view will do); ranks: HOST array (travels as kernel arguments); d_value m int32,
+ * d_below m int64, d_scratch sa_select_scratch_bytes(m) bytes, 8-byte aligned, contents ignored */
+int  sa_ctx_select(sa_ctx *ctx, const int32_t *d_packed, const int64_t *ranks, int32_t m,
+		   int32_t *d_value, int64_t *d_below, void *d_scratch, void *stream);
+/* host in / host out, one device (the first), the matrix never leaves it (as sa_hip_neighbors) */
+bool sa_hip_select(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below);
+/* on a finished tile job: answers when sa_zjob_edges can, refuses in the same cases with the same wording; 0 on success */
+int  sa_zjob_select(sa_zjob *job, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below);
+/* one alignment, then the cut and what it feeds, from the same device matrix.  A bad rank is refused before the alignment is
+ * launched.  *min_score = the score at `rank`, the threshold of the returned graph; value / below as for sa_hip_select. */
+sa_edges   *sa_hip_edges_at_rank(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below);
+sa_linkage *sa_hip_linkage_with_ranks(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
+				      int32_t *value, int64_t *below);
+double sa_hip_last_select_seconds(void);                       /* device time of the rounds of the last successful call */
 
 /* ---- pair-space planning (host only, no device needed) -------------------
  * DP cells (sum of len_i*len_j) of the packed pair range [start, start+count),

@@ -62,6 +62,8 @@ ABI_SYMBOLS = (
     "sa_edges_destroy", "sa_hip_last_edges_seconds",
     "sa_linkage_scratch_bytes", "sa_ctx_linkage", "sa_hip_linkage", "sa_zjob_linkage", "sa_linkage_pairs", "sa_linkage_score",
     "sa_linkage_destroy", "sa_hip_last_linkage_seconds", "sa_hip_last_linkage_rounds", "sa_linkage_labels", "sa_linkage_merges",
+    "sa_select_scratch_bytes", "sa_score_rank", "sa_ctx_select", "sa_hip_select", "sa_zjob_select", "sa_hip_edges_at_rank",
+    "sa_hip_linkage_with_ranks", "sa_hip_last_select_seconds",
 )
 
 
@@ -245,6 +247,21 @@ def load_library() -> C.CDLL:
     lib.sa_linkage_labels.restype = C.c_int32
     lib.sa_linkage_merges.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sa_linkage_merges.restype = C.c_int
+    lib.sa_select_scratch_bytes.argtypes = [C.c_int32]
+    lib.sa_select_scratch_bytes.restype = C.c_size_t
+    lib.sa_score_rank.argtypes = [C.c_int64, C.c_double]
+    lib.sa_score_rank.restype = C.c_int64
+    lib.sa_ctx_select.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_select.restype = C.c_int
+    lib.sa_hip_select.argtypes = [_Input, C.POINTER(_Scoring), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_hip_select.restype = C.c_bool
+    lib.sa_zjob_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_zjob_select.restype = C.c_int
+    lib.sa_hip_edges_at_rank.argtypes = [_Input, C.POINTER(_Scoring), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    lib.sa_hip_edges_at_rank.restype = C.c_void_p
+    lib.sa_hip_linkage_with_ranks.argtypes = [_Input, C.POINTER(_Scoring), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_hip_linkage_with_ranks.restype = C.c_void_p
+    lib.sa_hip_last_select_seconds.restype = C.c_double
     _lib = lib
     return lib
 
@@ -575,6 +592,74 @@ def _tree_arrays(pairs, score, n: int):
     return n, pairs, score
 
 
+SELECT_MAX = 16  # SA_HIP_SELECT_MAX
+
+
+def _ranks(ranks) -> np.ndarray:
+    """the ranks of a select call as a contiguous int64 array; how many and which are valid is the library's to say"""
+    try:
+        return np.ascontiguousarray(np.asarray(ranks).reshape(-1), dtype=np.int64)
+    except (OverflowError, TypeError, ValueError) as e:
+        raise AlignError(f"ranks are not int64: {e}") from None
+
+
+def _select_room(m: int) -> tuple[np.ndarray, np.ndarray]:
+    """host arrays for value / below: room for a full call, so that a refused m never meets a short array"""
+    room = max(m, SELECT_MAX)
+    return np.zeros(room, np.int32), np.zeros(room, np.int64)
+
+
+def score_rank(pairs: int, q: float) -> int:
+    """sa_score_rank (host only): min(pairs - 1, int(q * pairs)) for 0 <= q <= 1; -1 for a NaN, a q outside [0, 1], pairs < 1"""
+    return int(load_library().sa_score_rank(int(pairs), float(q)))
+
+
+def select_scratch_bytes(m: int) -> int:
+    """sa_select_scratch_bytes: the device scratch memory Context.select needs for m ranks (0 for an m outside 1 .. 16)"""
+    return int(load_library().sa_select_scratch_bytes(int(m)))
+
+
+def hip_select(store: SequenceStore, scoring: Scoring, ranks) -> tuple[np.ndarray, np.ndarray]:
+    """sa_hip_select: for each rank k (up to 16, any order, duplicates allowed) into the ascending order of the N (N - 1) / 2
+    pair scores, (values int32 (m,), below int64 (m,)): the k-th smallest score and the number of pairs strictly below it,
+    selected on the device.  The matrix never leaves the device."""
+    lib = load_library()
+    sc = scoring._as_c()
+    r = _ranks(ranks)
+    value, below = _select_room(len(r))
+    if not lib.sa_hip_select(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data):
+        raise AlignError(_err())
+    return value[:len(r)].copy(), below[:len(r)].copy()
+
+
+def hip_edges_at_rank(store: SequenceStore, scoring: Scoring, rank: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, int, int]:
+    """sa_hip_edges_at_rank: one alignment, the score T at `rank` and the score graph at T from the same device matrix --
+    (offsets, index, score) as hip_edges returns them, then min_score = T and below = the pairs under T; E = 2 (P - below)"""
+    lib = load_library()
+    sc = scoring._as_c()
+    cut, below = C.c_int32(0), C.c_int64(0)
+    (rank,) = _ranks([rank])
+    offsets, index, score = _take_edges(lib, lib.sa_hip_edges_at_rank(store._as_c(), C.byref(sc), int(rank), C.byref(cut), C.byref(below)))
+    return offsets, index, score, int(cut.value), int(below.value)
+
+
+def hip_linkage_with_ranks(store: SequenceStore, scoring: Scoring, ranks) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """sa_hip_linkage_with_ranks: one alignment, then hip_select's (values, below) for `ranks` and hip_linkage's (pairs, score)
+    from the same device matrix -- (pairs, score, values, below)"""
+    lib = load_library()
+    sc = scoring._as_c()
+    r = _ranks(ranks)
+    value, below = _select_room(len(r))
+    pairs, score = _take_linkage(lib, lib.sa_hip_linkage_with_ranks(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data,
+                                                                     below.ctypes.data))
+    return pairs, score, value[:len(r)].copy(), below[:len(r)].copy()
+
+
+def last_select_seconds() -> float:
+    """device time of the rounds in the last hip_select / DeflateJob.select / *_at_rank / *_with_ranks call"""
+    return float(load_library().sa_hip_last_select_seconds())
+
+
 def linkage_labels(pairs, score, n: int, min_score: int) -> tuple[np.ndarray, int]:
     """sa_linkage_labels (host only): (labels int32 (N,), clusters) -- labels[r] is the smallest index in r's connected
     component of the graph score >= min_score, from the tree alone.  Any int32 threshold is valid."""
@@ -861,6 +946,15 @@ class Context:
                                     C.c_void_p(d_scratch_ptr), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def select(self, d_packed_ptr: int, ranks, d_value_ptr: int, d_below_ptr: int, d_scratch_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_select: from the whole packed device matrix of this store (any 4-byte-aligned device pointer), the scores at
+        `ranks` (host values, up to 16) into d_value (m int32) and the pairs below each into d_below (m int64), asynchronously on
+        `stream`; d_scratch: select_scratch_bytes(m) bytes, 8-byte aligned, contents ignored"""
+        r = _ranks(ranks)
+        if self._lib.sa_ctx_select(self._h, C.c_void_p(d_packed_ptr), r.ctypes.data, len(r), C.c_void_p(d_value_ptr),
+                                   C.c_void_p(d_below_ptr), C.c_void_p(d_scratch_ptr), C.c_void_p(stream)):
+            raise AlignError(_err())
+
     def alignments(self, pairs) -> Alignments:
         """sa_ctx_alignments: the alignments of the listed pairs of this context's store (see hip_alignments)"""
         arr = _pairs_array(pairs)
@@ -949,6 +1043,15 @@ class DeflateJob:
         """sa_zjob_linkage: (pairs, score) as hip_linkage returns them, from the finished packed matrix this job's device
         holds -- after next() has returned [] for a begin() job; raises when the matrix is dealt over several jobs"""
         return _take_linkage(self._lib, self._lib.sa_zjob_linkage(self._h))
+
+    def select(self, ranks) -> tuple[np.ndarray, np.ndarray]:
+        """sa_zjob_select: (values, below) as hip_select returns them, from the finished packed matrix this job's device
+        holds -- after next() has returned [] for a begin() job; raises when the matrix is dealt over several jobs"""
+        r = _ranks(ranks)
+        value, below = _select_room(len(r))
+        if self._lib.sa_zjob_select(self._h, r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data):
+            raise AlignError(_err())
+        return value[:len(r)].copy(), below[:len(r)].copy()
 
     def stats(self) -> dict:
         e, c, r, o = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()

@@ -549,6 +549,96 @@ extern "C" sa_linkage *sa_hip_linkage(struct sa_input in, const struct sa_scorin
 	return sa_guard("sa_hip_linkage", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc); });
 }
 
+/* ---- order statistics of the matrix, alone and as the cut of what follows them on the same device matrix -------------------- */
+static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below)
+{
+	if (!sc || !ranks || !value || !below) {
+		sa_set_error("sa_hip_select: null argument");
+		return false;
+	}
+	if (!sa_select_check("sa_hip_select", in.num, ranks, m)) /* (before the alignment: P follows from in.num) */
+		return false;
+	DeviceRun run;
+	if (!run.begin("sa_hip_select", in, sc))
+		return false;
+	if (!sa_select_to_host("sa_hip_select", run.d_packed, in.num, ranks, m, value, below, run.stream))
+		return false;
+	return run.finish();
+}
+
+extern "C" bool sa_hip_select(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below)
+{
+	return sa_guard("sa_hip_select", false, [&] { return select_impl(in, sc, ranks, m, value, below); });
+}
+
+static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below)
+{
+	if (!sc || !min_score || !below) {
+		sa_set_error("sa_hip_edges_at_rank: null argument");
+		return nullptr;
+	}
+	if (!sa_select_check("sa_hip_edges_at_rank", in.num, &rank, 1))
+		return nullptr;
+	DeviceRun run;
+	if (!run.begin("sa_hip_edges_at_rank", in, sc))
+		return nullptr;
+	int32_t cut = 0;
+	int64_t under = 0;
+	if (!sa_select_to_host("sa_hip_edges_at_rank", run.d_packed, in.num, &rank, 1, &cut, &under, run.stream))
+		return nullptr;
+	sa_edges *res = sa_edges_to_host("sa_hip_edges_at_rank", run.d_packed, in.num, cut, run.stream);
+	if (res && !run.finish()) {
+		sa_edges_destroy(res);
+		res = nullptr;
+	}
+	if (res) {
+		*min_score = cut;
+		*below = under;
+	}
+	return res;
+}
+
+extern "C" sa_edges *sa_hip_edges_at_rank(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below)
+{
+	return sa_guard("sa_hip_edges_at_rank", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below); });
+}
+
+static sa_linkage *linkage_with_ranks_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value,
+					   int64_t *below)
+{
+	if (!sc || !ranks || !value || !below) {
+		sa_set_error("sa_hip_linkage_with_ranks: null argument");
+		return nullptr;
+	}
+	if (!sa_select_check("sa_hip_linkage_with_ranks", in.num, ranks, m))
+		return nullptr;
+	DeviceRun run;
+	if (!run.begin("sa_hip_linkage_with_ranks", in, sc))
+		return nullptr;
+	int32_t cut[SA_HIP_SELECT_MAX];
+	int64_t under[SA_HIP_SELECT_MAX];
+	if (!sa_select_to_host("sa_hip_linkage_with_ranks", run.d_packed, in.num, ranks, m, cut, under, run.stream))
+		return nullptr;
+	sa_linkage *res = sa_linkage_to_host("sa_hip_linkage_with_ranks", run.d_packed, in.num, run.stream);
+	if (res && !run.finish()) {
+		sa_linkage_destroy(res);
+		res = nullptr;
+	}
+	if (res)
+		for (int32_t t = 0; t < m; t++) {
+			value[t] = cut[t];
+			below[t] = under[t];
+		}
+	return res;
+}
+
+extern "C" sa_linkage *sa_hip_linkage_with_ranks(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
+						 int32_t *value, int64_t *below)
+{
+	return sa_guard("sa_hip_linkage_with_ranks", (sa_linkage *)nullptr,
+			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below); });
+}
+
 extern "C" int sa_hip_last_align_path(void) { return g_last_align_path.load(); }
 
 extern "C" int sa_hip_last_align_breakdown(double *ms, int n)

@@ -1310,6 +1310,34 @@ extern "C" sa_edges *sa_zjob_edges(sa_zjob *z, int32_t min_score)
 	});
 }
 
+/* Order statistics of the job's packed matrix (sa_select.hip), in order behind whatever the job has on its stream.  Refuses what
+ * sa_zjob_edges refuses, with the same wording. */
+extern "C" int sa_zjob_select(sa_zjob *z, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below)
+{
+	return sa_guard("sa_zjob_select", 1, [&] {
+		if (!z || !ranks || !value || !below) {
+			sa_set_error("sa_zjob_select: null argument");
+			return 1;
+		}
+		if (!z->peers.empty()) {
+			sa_set_error("sa_zjob_select: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+			return 1;
+		}
+		if (!z->d_packed) {
+			sa_set_error("sa_zjob_select: the job walks a full matrix; the selection reads the packed index");
+			return 1;
+		}
+		if (z->shells && z->next_batch < zjob_batches(z)) {
+			sa_set_error("sa_zjob_select: the walk is not finished (sa_zjob_next has not returned 0 yet)");
+			return 1;
+		}
+		if (!sa_select_check("sa_zjob_select", z->num, ranks, m))
+			return 1;
+		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
+		return sa_select_to_host("sa_zjob_select", z->d_packed, z->num, ranks, m, value, below, z->stream) ? 0 : 1;
+	});
+}
+
 /* The single-linkage tree of the job's packed matrix (sa_linkage.hip), in order behind whatever the job has on its stream.
  * Refuses what sa_zjob_edges refuses, for the same reasons. */
 extern "C" sa_linkage *sa_zjob_linkage(sa_zjob *z)

@@ -127,4 +127,11 @@ sa_edges *sa_edges_to_host(const char *who, const int32_t *d_packed, int32_t num
 struct sa_linkage;
 sa_linkage *sa_linkage_to_host(const char *who, const int32_t *d_packed, int32_t num, hipStream_t s);
 
+/* order statistics of the score distribution (sa_select.hip).  sa_select_check: m, N and the ranks, before anything is launched.
+ * sa_select_to_host: value / below of the m ranks of a packed device matrix into host memory, in order on `s`, which is
+ * synchronised; the device time goes to sa_hip_last_select_seconds.  false + sa_set_error on failure, nothing written. */
+bool sa_select_check(const char *who, int32_t num, const int64_t *ranks, int32_t m);
+bool sa_select_to_host(const char *who, const int32_t *d_packed, int32_t num, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below,
+		       hipStream_t s);
+
 #endif /* SA_INTERNAL_H */

@@ -3,7 +3,7 @@ alignment that feeds it, both device-resident and timed with HIP events on one s
 (default 11).
 
 Stores: config 2 (10 000 proteins) and make_protein_set(40000, 96, 144, 5) (the store of profiles/neighbors_time.txt).
-T = the 0.99 quantile of the store's own packed matrix (torch.kthvalue on the device).  Per store: count + scan, fill, and the
+T = the 0.99 quantile of the store's own packed matrix (sa_ctx_select on the device).  Per store: count + scan, fill, and the
 three together with their share of the alignment ms of the same store in the same process.  Two comparison figures, neither a
 condition: sa_k_neighbors at k = 8 from the same run (one sweep of the same kind), and 8 N^2 bytes / time (the matrix is read
 twice) as a fraction of the 8 TB/s HBM roof.
@@ -53,8 +53,13 @@ for name, seqs in stores:
     with sa.Context(store, scoring, 0) as ctx:
         align_ms, lo, hi = median_ms(stream, lambda: ctx.align_range(0, store.pairs, d_packed.data_ptr(), stream=s), warm=2)
         print(f"\n{name}: N = {n}, {store.pairs} pairs; alignment (sa_ctx_align_range) {align_ms:.3f} ms ({lo:.3f} .. {hi:.3f})")
-        t = int(torch.kthvalue(d_packed, int(0.99 * store.pairs) + 1).values.item())
+        d_cut = torch.empty(1, dtype=torch.int32, device="cuda")
+        d_under = torch.empty(1, dtype=torch.int64, device="cuda")
+        d_work = torch.empty(sa.select_scratch_bytes(1), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
+        ctx.select(d_packed.data_ptr(), [sa.score_rank(store.pairs, 0.99)], d_cut.data_ptr(), d_under.data_ptr(), d_work.data_ptr(), stream=s)
+        stream.synchronize()
+        t = int(d_cut.item())
         ctx.edge_offsets(d_packed.data_ptr(), t, d_offsets.data_ptr(), stream=s)
         stream.synchronize()
         e = int(d_offsets[n].item())
