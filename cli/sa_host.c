@@ -980,6 +980,49 @@ int sa_host_write_quantiles(const char *path, const struct sa_host_store *s, con
 	return rc;
 }
 
+/* Normalised scores (include/seqalign_hip.h: struct sa_norm): /normalization_denominators N I32LE, /normalization_rule 2 I32LE
+ * (source, rule) and /normalization_scale 1 I32LE, contiguous, added to the finished file at `path`, whose other datasets stay as
+ * they are.  The arguments are checked before anything is opened. */
+int sa_host_write_normalization(const char *path, const struct sa_host_store *s, const int32_t *denominators, int32_t source, int32_t rule)
+{
+	if (!path || !s || !denominators)
+		return fail("Normalization data missing");
+	if (s->in.num < 1)
+		return fail("Normalization data missing");
+	if (source != SA_NORM_SELF && source != SA_NORM_LENGTH)
+		return fail("Normalization source %d is neither self-score (%d) nor length (%d)", source, (int)SA_NORM_SELF, (int)SA_NORM_LENGTH);
+	if (rule != SA_NORM_MIN && rule != SA_NORM_MAX && rule != SA_NORM_MEAN)
+		return fail("Normalization rule %d is none of min (%d), max (%d), mean (%d)", rule, (int)SA_NORM_MIN, (int)SA_NORM_MAX, (int)SA_NORM_MEAN);
+	hid_t file;
+	hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
+	H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
+	H5Pset_alignment(fapl, 4096, 4096);
+	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
+	H5Pclose(fapl);
+	if (file < 0)
+		return fail("Failed to open HDF5 file: %s", path);
+	const int32_t how[2] = { source, rule }, scale = SA_NORM_SCALE;
+	const struct {
+		const char *name;
+		hsize_t extent;
+		const int32_t *data;
+	} sets[3] = { { "/normalization_denominators", (hsize_t)s->in.num, denominators },
+		      { "/normalization_rule", 2, how },
+		      { "/normalization_scale", 1, &scale } };
+	int rc = 0;
+	for (int d = 0; d < 3 && !rc; d++) {
+		hid_t space = H5Screate_simple(1, &sets[d].extent, NULL);
+		hid_t set = H5Dcreate2(file, sets[d].name, H5T_STD_I32LE, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || H5Dwrite(set, H5T_NATIVE_INT32, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0)
+			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
+		if (set >= 0)
+			H5Dclose(set);
+		H5Sclose(space);
+	}
+	H5Fclose(file);
+	return rc;
+}
+
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder
  * when `compression` > 0, the raw tiles when 0.  Same file, dataset, chunk shape and filter pipeline as sa_host_write_hdf5 --
  * the tiles go to H5Dwrite_chunk as they are, tile row after tile row. */

@@ -102,6 +102,10 @@ int sa_host_write_linkage(const char *path, const struct sa_host_store *s, const
  * `create` is set. */
 int sa_host_write_quantiles(const char *path, const struct sa_host_store *s, const double *fractions, const int32_t *values,
 			    const int64_t *below, int32_t m, const int32_t *edge_min, const int32_t *cluster_min, int create);
+/* --normalize: /normalization_denominators (N I32LE, d[k] of include/seqalign_hip.h: struct sa_norm), /normalization_rule
+ * (2 I32LE: source, rule) and /normalization_scale (1 I32LE: SA_NORM_SCALE), added to the finished file at `path`, whose other
+ * datasets stay as they are.  A source or rule outside its enum gives an error before anything is opened. */
+int sa_host_write_normalization(const char *path, const struct sa_host_store *s, const int32_t *denominators, int32_t source, int32_t rule);
 
 #ifdef __cplusplus
 }

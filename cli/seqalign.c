@@ -19,6 +19,9 @@
  *             --min-quantile Q  --clusters-quantile Q  --quantiles Q1,Q2,...   (the cut as a fraction of the score distribution:
  *             the score at rank min(P - 1, floor(Q P)) of the P pair scores in ascending order, selected on the device by one
  *             sa_*_select call for all of them: /score_quantiles, /score_quantile_values, /score_quantile_below)
+ *             --normalize RULE   (everything selected from the scores -- neighbours, score graph, tree, clusters, quantiles -- from
+ *             scores divided on the device by the self-scores or the lengths, in parts per million; /similarity_matrix stays raw:
+ *             /normalization_denominators, /normalization_rule, /normalization_scale)
  * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> score graph -> linkage -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
@@ -112,6 +115,10 @@ struct options {
 	 * min_q / clusters_q: which of them sets min_score / clusters_at (-1: none) */
 	double quantiles[SA_HIP_SELECT_MAX];
 	int nquant, min_q, clusters_q;
+	/* --normalize RULE: what is selected from the scores is selected from normalised scores (include/seqalign_hip.h: struct sa_norm) */
+	bool normalize;
+	int32_t norm_source, norm_rule;
+	const char *norm_name;
 };
 
 static void usage(const char *argv0)
@@ -168,6 +175,17 @@ static void usage(const char *argv0)
 	       "      --quantiles Q1,Q2,...  Also write the scores at these fractions.  All fractions of the three options\n"
 	       "                           (16 at most together) come from one selection: /score_quantiles (the fractions),\n"
 	       "                           /score_quantile_values (the scores) and /score_quantile_below (pairs scoring less)\n"
+	       "      --normalize RULE     Select from NORMALISED scores: RULE = self-min | self-max | self-mean | len-min |\n"
+	       "                           len-max | len-mean.  Every sequence gets a denominator, its self-score (the score of\n"
+	       "                           the sequence aligned with itself, computed on the device) or its length; the score s\n"
+	       "                           of a pair becomes floor(1000000 s / D), D the smaller, the larger or the mean of the\n"
+	       "                           pair's two denominators (parts per million, rounded towards minus infinity; D <= 0\n"
+	       "                           gives the lowest value).  Applies to -k, --min-score, --min-quantile, --linkage,\n"
+	       "                           --clusters, --clusters-quantile, --quantiles and the --*-only modes, and needs one of\n"
+	       "                           them; T of --min-score and --clusters is then in parts per million.\n"
+	       "                           /similarity_matrix, when written, STAYS RAW, as does the score of --alignments.\n"
+	       "                           Writes /normalization_denominators (N), /normalization_rule (source 0 = self-score,\n"
+	       "                           1 = length; rule 0 = min, 1 = max, 2 = mean) and /normalization_scale (1000000)\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -231,7 +249,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { "alignments", 4, false },
 		     { "min-score", 5, true }, { "edges-only", 6, false }, { "linkage", 7, false }, { "clusters", 8, true },
 		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
-		     { "quantiles", 12, true }, { NULL, 0, false } };
+		     { "quantiles", 12, true }, { "normalize", 13, true }, { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -386,6 +404,27 @@ static int parse_args(int argc, char **argv, struct options *o)
 					p = comma + 1;
 				}
 				break;
+			case 13: {
+				static const struct {
+					const char *name;
+					int32_t source, rule;
+				} RULES[] = { { "self-min", SA_NORM_SELF, SA_NORM_MIN }, { "self-max", SA_NORM_SELF, SA_NORM_MAX },
+					      { "self-mean", SA_NORM_SELF, SA_NORM_MEAN }, { "len-min", SA_NORM_LENGTH, SA_NORM_MIN },
+					      { "len-max", SA_NORM_LENGTH, SA_NORM_MAX }, { "len-mean", SA_NORM_LENGTH, SA_NORM_MEAN } };
+				o->normalize = false;
+				for (size_t t = 0; t < sizeof(RULES) / sizeof(RULES[0]); t++)
+					if (!strcmp(val, RULES[t].name)) {
+						o->normalize = true;
+						o->norm_source = RULES[t].source;
+						o->norm_rule = RULES[t].rule;
+						o->norm_name = RULES[t].name;
+					}
+				if (!o->normalize) {
+					err("Normalization rule must be one of self-min, self-max, self-mean, len-min, len-max, len-mean: %s", val);
+					return 1;
+				}
+				break;
+			}
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -482,6 +521,9 @@ int main(int argc, char **argv)
 		ok = (err("Options --linkage-only and -k, --neighbors conflict: the neighbors need a pass of their own (use --linkage without --linkage-only)"), false);
 	if (ok && o.linkage_only && o.has_min_score)
 		ok = (err("Options --linkage-only and --min-score conflict: the score graph needs a pass of its own (use --linkage without --linkage-only)"), false);
+	if (ok && o.normalize && !o.neighbors && !o.has_min_score && !o.linkage && !o.nquant)
+		ok = (err("Option --normalize requires something selected from the scores: -k, --min-score, --min-quantile, --linkage, --clusters, "
+			  "--clusters-quantile or --quantiles (the similarity matrix itself stays raw)"), false);
 	if (ok && sa_matrix_load(o.matrix, sc.lut, sc.sub))
 		ok = (err("Invalid substitution matrix name"), false);
 	if (ok && (sc.method = sa_method_parse(o.align)) < 0)
@@ -556,6 +598,8 @@ int main(int argc, char **argv)
 		info("Clusters: connected components of the pairs that score at least %d", o.clusters_at);
 	if (o.nquant)
 		info("Score quantiles: %d, selected on the device", o.nquant);
+	if (o.normalize)
+		info("Normalization: %s, in parts per million (the similarity matrix stays raw)", o.norm_name);
 
 	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t_edges = 0, t_linkage = 0, t0;
 	stamp("options parsed");
@@ -611,6 +655,19 @@ int main(int argc, char **argv)
 	sa_linkage *tree = NULL;
 	bool lk_second_pass = false;
 	int lk_rounds = 0;
+	/* --normalize: every selection below goes the normalised way -- the tile job through sa_zjob_normalize, the rest through the
+	 * *_norm calls, which with norm == NULL are their namesakes */
+	struct sa_norm norm_spec = { o.norm_source, o.norm_rule, NULL };
+	const struct sa_norm *norm = NULL;
+	double t_norm = 0;
+	if (o.normalize) {
+		norm_spec.denominators = malloc(sizeof(int32_t) * (size_t)store.in.num);
+		if (!norm_spec.denominators) {
+			err("Out of memory allocating normalization denominators");
+			return 1;
+		}
+		norm = &norm_spec;
+	}
 	if (o.neighbors) {
 		nb_index = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
 		nb_score = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
@@ -720,8 +777,20 @@ int main(int argc, char **argv)
 		verb("%s on the device: %.2f GB -> %.2f GB (%.2f : 1); the writer waited %.0f ms for the encoder, %.0f ms for gather + copy",
 		     o.compression ? "Deflated" : "Tiled", (double)raw / 1e9, (double)outb / 1e9, outb ? (double)raw / (double)outb : 0.0, enc_ms,
 		     copy_ms);
+		/* --normalize: every tile is written, raw; the device's matrix is normalised in place for what is selected from it.  A job
+		 * that cannot (the matrix dealt over several jobs) answers nothing below: the second passes take over */
+		bool job_answers = true;
+		if (norm) {
+			if (sa_zjob_normalize(job, norm) == 0) {
+				t_norm = sa_hip_last_normalize_seconds();
+				verb("Scores normalised in place on the device (the tiles written are raw)");
+			} else {
+				job_answers = false;
+				verb("Normalization: %s", sa_last_error());
+			}
+		}
 		/* the finished matrix is still on the device: the neighbours come from it, nothing is aligned twice */
-		if (o.neighbors) {
+		if (o.neighbors && job_answers) {
 			if (sa_zjob_neighbors(job, o.neighbors, nb_index, nb_score) == 0) {
 				nb_done = true;
 				t_select = sa_hip_last_neighbors_seconds();
@@ -730,7 +799,7 @@ int main(int argc, char **argv)
 				verb("Neighbors: %s", sa_last_error());
 			}
 		}
-		if (o.nquant) { /* first: the cut of what follows */
+		if (o.nquant && job_answers) { /* first: the cut of what follows */
 			if (sa_zjob_select(job, q_ranks, o.nquant, q_values, q_below) == 0) {
 				q_done = true;
 				t_quant = sa_hip_last_select_seconds();
@@ -741,7 +810,7 @@ int main(int argc, char **argv)
 				verb("Score quantiles: %s", sa_last_error());
 			}
 		}
-		if (o.has_min_score && (o.min_q < 0 || q_done)) {
+		if (o.has_min_score && (o.min_q < 0 || q_done) && job_answers) {
 			edges = sa_zjob_edges(job, o.min_score);
 			if (edges) {
 				t_edges = sa_hip_last_edges_seconds();
@@ -750,7 +819,7 @@ int main(int argc, char **argv)
 				verb("Score graph: %s", sa_last_error());
 			}
 		}
-		if (o.linkage) {
+		if (o.linkage && job_answers) {
 			tree = sa_zjob_linkage(job);
 			if (tree) {
 				t_linkage = sa_hip_last_linkage_seconds();
@@ -766,7 +835,7 @@ int main(int argc, char **argv)
 		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the tree there, copy back 12 (N - 1) bytes */
 		info("Similarity Matrix stays on the device: the single-linkage tree is built there");
 		t0 = now();
-		tree = o.nquant ? sa_hip_linkage_with_ranks(store.in, &sc, q_ranks, o.nquant, q_values, q_below) : sa_hip_linkage(store.in, &sc);
+		tree = o.nquant ? sa_hip_linkage_with_ranks_norm(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm) : sa_hip_linkage_norm(store.in, &sc, norm);
 		if (!tree) {
 			err("%s", sa_last_error());
 			return 1;
@@ -794,10 +863,10 @@ int main(int argc, char **argv)
 			info("Similarity Matrix stays on the device: the pairs that score at least %d are selected there", o.min_score);
 		t0 = now();
 		if (o.min_q >= 0 && o.nquant == 1) { /* one alignment: the cut and the graph from the same device matrix */
-			edges = sa_hip_edges_at_rank(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0]);
+			edges = sa_hip_edges_at_rank_norm(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0], norm);
 		} else {
 			if (o.nquant) { /* further fractions: one select call for all of them, in a pass of its own */
-				if (!sa_hip_select(store.in, &sc, q_ranks, o.nquant, q_values, q_below)) {
+				if (!sa_hip_select_norm(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm)) {
 					err("%s", sa_last_error());
 					return 1;
 				}
@@ -805,7 +874,7 @@ int main(int argc, char **argv)
 			}
 			if (o.min_q >= 0)
 				o.min_score = q_values[o.min_q];
-			edges = sa_hip_edges(store.in, &sc, o.min_score);
+			edges = sa_hip_edges_norm(store.in, &sc, o.min_score, norm);
 		}
 		if (edges && o.nquant) {
 			q_done = true;
@@ -831,7 +900,7 @@ int main(int argc, char **argv)
 		/* no host matrix, no tiles, no matrix transfer: align into device memory, select there, copy back 2 N K ints */
 		info("Similarity Matrix stays on the device: %d neighbors per sequence are selected there", o.neighbors);
 		t0 = now();
-		if (!sa_hip_neighbors(store.in, &sc, o.neighbors, nb_index, nb_score)) {
+		if (!sa_hip_neighbors_norm(store.in, &sc, o.neighbors, nb_index, nb_score, norm)) {
 			err("%s", sa_last_error());
 			return 1;
 		}
@@ -879,7 +948,7 @@ int main(int argc, char **argv)
 		/* the other paths (N <= 256, SA_HOST_* switches, -W, several devices, a walk dealt over several jobs) no longer hold
 		 * the matrix on one device: a second pass aligns into device memory again and selects there */
 		verb("Neighbors: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		if (!sa_hip_neighbors(store.in, &sc, o.neighbors, nb_index, nb_score)) {
+		if (!sa_hip_neighbors_norm(store.in, &sc, o.neighbors, nb_index, nb_score, norm)) {
 			err("%s", sa_last_error());
 			return 1;
 		}
@@ -936,14 +1005,14 @@ int main(int argc, char **argv)
 		verb("Score quantiles: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
 		bool got;
 		if (o.min_q >= 0 && o.nquant == 1 && !edges) {
-			edges = sa_hip_edges_at_rank(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0]);
+			edges = sa_hip_edges_at_rank_norm(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0], norm);
 			got = edges != NULL;
 			if (got) {
 				eg_second_pass = true;
 				t_edges = sa_hip_last_edges_seconds();
 			}
 		} else if (o.linkage && !tree) {
-			tree = sa_hip_linkage_with_ranks(store.in, &sc, q_ranks, o.nquant, q_values, q_below);
+			tree = sa_hip_linkage_with_ranks_norm(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm);
 			got = tree != NULL;
 			if (got) {
 				lk_second_pass = true;
@@ -951,7 +1020,7 @@ int main(int argc, char **argv)
 				lk_rounds = sa_hip_last_linkage_rounds();
 			}
 		} else {
-			got = sa_hip_select(store.in, &sc, q_ranks, o.nquant, q_values, q_below);
+			got = sa_hip_select_norm(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm);
 		}
 		if (!got) {
 			err("%s", sa_last_error());
@@ -976,7 +1045,7 @@ int main(int argc, char **argv)
 	if (o.has_min_score && !edges) {
 		/* as for the neighbours: the matrix of the first pass is not on one device any more */
 		verb("Score graph: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		edges = sa_hip_edges(store.in, &sc, o.min_score);
+		edges = sa_hip_edges_norm(store.in, &sc, o.min_score, norm);
 		if (!edges) {
 			err("%s", sa_last_error());
 			return 1;
@@ -1004,7 +1073,7 @@ int main(int argc, char **argv)
 	if (o.linkage && !tree) {
 		/* as for the neighbours: the matrix of the first pass is not on one device any more */
 		verb("Single-linkage tree: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		tree = sa_hip_linkage(store.in, &sc);
+		tree = sa_hip_linkage_norm(store.in, &sc, norm);
 		if (!tree) {
 			err("%s", sa_last_error());
 			return 1;
@@ -1054,6 +1123,18 @@ int main(int argc, char **argv)
 		t_out += now() - t0;
 		stamp("quantiles written");
 	}
+	if (norm && !o.no_write) {
+		/* last, like the quantiles: the denominators came back with whichever call normalised */
+		t0 = now();
+		if (sa_host_write_normalization(o.output, &store, norm_spec.denominators, norm_spec.source, norm_spec.rule)) {
+			err("%s", sa_host_error());
+			return 1;
+		}
+		t_out += now() - t0;
+		stamp("normalization written");
+	}
+	if (norm && t_norm == 0)
+		t_norm = sa_hip_last_normalize_seconds(); /* (the *_norm calls: the last of them) */
 	if (o.benchmark) { /* -B: src/util/benchmark.c:50-64 */
 		const double total = t_in + t_filter + t_align + t_out;
 		printf("Timing breakdown:\n  Input: %.3f sec\n  Filter: %.3f sec\n  Alignment: %.3f sec\n  Output: %.3f sec\n"
@@ -1085,6 +1166,8 @@ int main(int argc, char **argv)
 			       lk_second_pass ? ", after a second alignment pass into device memory" : "");
 		if (o.has_clusters)
 			printf("  (clusters at score >= %d: %d)\n", o.clusters_at, cluster_count);
+		if (norm)
+			printf("  (Normalisation on the device, %s: denominators + sweep over %lld pairs, %.6f sec)\n", o.norm_name, npairs, t_norm);
 		printf("Alignments per second: %.2f\n", t_align > 0 ? (double)pairs / t_align : 0.0);
 	}
 	if (pinned)
@@ -1092,6 +1175,7 @@ int main(int argc, char **argv)
 	sa_host_matrix_free(out.matrix, n, out.triangular);
 	free(nb_index);
 	free(nb_score);
+	free(norm_spec.denominators);
 	sa_host_store_free(&store);
 	stamp("released");
 	/* everything is written and closed: leave without the runtime's teardown (device reset, queue and signal

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -453,6 +453,66 @@ sa_edges   *sa_hip_edges_at_rank(struct sa_input in, const struct sa_scoring *sc
 sa_linkage *sa_hip_linkage_with_ranks(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
 				      int32_t *value, int64_t *below);
 double sa_hip_last_select_seconds(void);                       /* device time of the rounds of the last successful call */
+
+/* ---- normalised scores: self-scores and a normalised triangle on the device ------------------------------------------------
+ * No reference counterpart.  Raw scores grow with length: two unrelated long proteins outscore two identical short peptides, so
+ * on a store of mixed lengths the neighbours, the graph, the tree and the order statistics above are led by the long sequences.
+ * Clustering by similarity divides the score by the self-scores or by the lengths first.  Here that division happens where the
+ * scores are: a normalised triangle in the same packed layout, which every consumer above reads unchanged.
+ * Denominator d[k] of sequence k (norm.source):
+ *   SA_NORM_SELF    the score the context's method and scoring give sequence k aligned with ITSELF: k is the row and the column
+ *                   sequence, the table indexed exactly as for a pair (sa_scoring: NW [code of row][code of column], Gotoh and
+ *                   SW [code of column][code of row] -- it matters for a table that is not symmetric), by the full DP; never
+ *                   assumed to be the sum of the table's diagonal
+ *   SA_NORM_LENGTH  meta[k].len
+ * Value of the pair (i, j) with score s (norm.rule), all arithmetic exact and 64-bit:
+ *   SA_NORM_MIN     D = min(d[i], d[j]),      num = s SA_NORM_SCALE
+ *   SA_NORM_MAX     D = max(d[i], d[j]),      num = s SA_NORM_SCALE
+ *   SA_NORM_MEAN    D = (int64) d[i] + d[j],  num = 2 s SA_NORM_SCALE
+ *   D <= 0: INT32_MIN (an undefined ratio is the worst score for every consumer); otherwise floor(num / D), rounded towards
+ *   MINUS INFINITY (Python's //; C's / truncates, and NW scores are often negative), saturated to [INT32_MIN, INT32_MAX].
+ * A normalised score is in parts per million: 1000000 = "as good as the denominator".  Thresholds given to the consumers
+ * (min_score of the graph, the cut of the tree) are then in parts per million too.  The same store, scoring and rule give the
+ * same bytes run after run. */
+enum { SA_NORM_SELF = 0, SA_NORM_LENGTH = 1 };               /* source of the per-sequence denominator d[k] */
+enum { SA_NORM_MIN = 0, SA_NORM_MAX = 1, SA_NORM_MEAN = 2 }; /* how d[i] and d[j] combine                   */
+#define SA_NORM_SCALE 1000000                                /* a normalised score is in parts per million  */
+struct sa_norm {
+	int32_t source;        /* SA_NORM_SELF / SA_NORM_LENGTH */
+	int32_t rule;          /* SA_NORM_MIN / SA_NORM_MAX / SA_NORM_MEAN */
+	int32_t *denominators; /* out, host, N int32: receives d[0 .. N); may be NULL */
+};
+/* host only: the value rule above for one entry.  INT32_MIN + sa_last_error for a rule outside the enum. */
+int32_t sa_norm_value(int32_t s, int32_t di, int32_t dj, int32_t rule);
+/* device-resident, asynchronous on `stream`: d_den = N int32 of device memory.  SA_NORM_SELF runs one wavefront per sequence
+ * over the context's strip-boundary scratch, so -- like sa_ctx_alignments -- it does not run beside sa_ctx_align_range (or
+ * another sa_ctx_denominators) of the SAME context on another stream; in order on one stream is fine.  SA_NORM_LENGTH copies
+ * the lengths.  Non-zero + sa_last_error for a null pointer or a source outside the enum, nothing launched. */
+int sa_ctx_denominators(sa_ctx *ctx, int32_t source, int32_t *d_den, void *stream);
+/* device-resident, asynchronous on `stream`, no scratch memory, no host synchronisation: d_out[p] = value of d_packed[p] for
+ * the whole packed matrix of ctx's store.  d_den: ANY N int32 of device memory -- sa_ctx_denominators' or the caller's own.
+ * d_packed / d_out need their natural 4-byte alignment only (an offset view will do); d_out == d_packed (in place) and
+ * disjoint buffers are both valid, partial overlap is not. */
+int sa_ctx_normalize(sa_ctx *ctx, const int32_t *d_packed, const int32_t *d_den, int32_t rule, int32_t *d_out, void *stream);
+/* on a sa_hip_tiles_begin job whose device holds the whole finished matrix (after sa_zjob_next has returned 0): normalises the
+ * job's matrix IN PLACE, once; sa_zjob_neighbors / _edges / _linkage / _select then answer over normalised scores.  The tiles
+ * already handed out stay raw.  Refused, in the wording of sa_zjob_edges: before the walk is finished, a second call, a
+ * sa_zjob_create job (its matrix is the caller's, and const), several devices, SA_HIP_TILES_SPLIT > 1, a d_full job. */
+int sa_zjob_normalize(sa_zjob *job, const struct sa_norm *norm);
+/* the one-call variants: the arguments of the namesake + norm.  norm == NULL: exactly the namesake.  Otherwise denominators and
+ * sweep follow the alignment on its stream, in place, and the selection reads normalised scores; norm->denominators, when not
+ * NULL, receives d[0 .. N) on success.  A source or rule outside its enum is refused before the alignment is launched. */
+bool sa_hip_neighbors_norm(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm);
+sa_edges *sa_hip_edges_norm(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm);
+sa_linkage *sa_hip_linkage_norm(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm);
+bool sa_hip_select_norm(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below,
+			const struct sa_norm *norm);
+sa_edges *sa_hip_edges_at_rank_norm(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below,
+				    const struct sa_norm *norm);
+sa_linkage *sa_hip_linkage_with_ranks_norm(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
+					   int32_t *value, int64_t *below, const struct sa_norm *norm);
+/* device time (seconds) of denominators + sweep in the last successful *_norm / sa_zjob_normalize call */
+double sa_hip_last_normalize_seconds(void);
 
 /* ---- pair-space planning (host only, no device needed) -------------------
  * DP cells (sum of len_i*len_j) of the packed pair range [start, start+count),

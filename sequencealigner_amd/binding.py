@@ -58,6 +58,8 @@ ABI_SYMBOLS = (
     "sa_ctx_neighbors", "sa_hip_neighbors", "sa_zjob_neighbors", "sa_hip_last_neighbors_seconds",
     "sa_ctx_alignments", "sa_hip_alignments", "sa_alns_records", "sa_alns_cigar", "sa_alns_count", "sa_alns_destroy",
     "sa_hip_last_alignments_seconds", "sa_hip_last_alignments_breakdown",
+    "sa_norm_value", "sa_ctx_denominators", "sa_ctx_normalize", "sa_zjob_normalize", "sa_hip_neighbors_norm", "sa_hip_edges_norm",
+    "sa_hip_linkage_norm", "sa_hip_select_norm", "sa_hip_edges_at_rank_norm", "sa_hip_linkage_with_ranks_norm", "sa_hip_last_normalize_seconds",
     "sa_ctx_edge_offsets", "sa_ctx_edge_fill", "sa_hip_edges", "sa_zjob_edges", "sa_edges_offsets", "sa_edges_index", "sa_edges_score",
     "sa_edges_destroy", "sa_hip_last_edges_seconds",
     "sa_linkage_scratch_bytes", "sa_ctx_linkage", "sa_hip_linkage", "sa_zjob_linkage", "sa_linkage_pairs", "sa_linkage_score",
@@ -65,6 +67,10 @@ ABI_SYMBOLS = (
     "sa_select_scratch_bytes", "sa_score_rank", "sa_ctx_select", "sa_hip_select", "sa_zjob_select", "sa_hip_edges_at_rank",
     "sa_hip_linkage_with_ranks", "sa_hip_last_select_seconds",
 )
+
+
+class _Norm(C.Structure):  # struct sa_norm
+    _fields_ = [("source", C.c_int32), ("rule", C.c_int32), ("denominators", C.c_void_p)]
 
 
 def library_path() -> pathlib.Path:
@@ -262,6 +268,27 @@ def load_library() -> C.CDLL:
     lib.sa_hip_linkage_with_ranks.argtypes = [_Input, C.POINTER(_Scoring), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.sa_hip_linkage_with_ranks.restype = C.c_void_p
     lib.sa_hip_last_select_seconds.restype = C.c_double
+    lib.sa_norm_value.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.sa_norm_value.restype = C.c_int32
+    lib.sa_ctx_denominators.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_denominators.restype = C.c_int
+    lib.sa_ctx_normalize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_normalize.restype = C.c_int
+    lib.sa_zjob_normalize.argtypes = [C.c_void_p, C.POINTER(_Norm)]
+    lib.sa_zjob_normalize.restype = C.c_int
+    lib.sa_hip_neighbors_norm.argtypes = lib.sa_hip_neighbors.argtypes + [C.POINTER(_Norm)]
+    lib.sa_hip_neighbors_norm.restype = C.c_bool
+    lib.sa_hip_edges_norm.argtypes = lib.sa_hip_edges.argtypes + [C.POINTER(_Norm)]
+    lib.sa_hip_edges_norm.restype = C.c_void_p
+    lib.sa_hip_linkage_norm.argtypes = lib.sa_hip_linkage.argtypes + [C.POINTER(_Norm)]
+    lib.sa_hip_linkage_norm.restype = C.c_void_p
+    lib.sa_hip_select_norm.argtypes = lib.sa_hip_select.argtypes + [C.POINTER(_Norm)]
+    lib.sa_hip_select_norm.restype = C.c_bool
+    lib.sa_hip_edges_at_rank_norm.argtypes = lib.sa_hip_edges_at_rank.argtypes + [C.POINTER(_Norm)]
+    lib.sa_hip_edges_at_rank_norm.restype = C.c_void_p
+    lib.sa_hip_linkage_with_ranks_norm.argtypes = lib.sa_hip_linkage_with_ranks.argtypes + [C.POINTER(_Norm)]
+    lib.sa_hip_linkage_with_ranks_norm.restype = C.c_void_p
+    lib.sa_hip_last_normalize_seconds.restype = C.c_double
     _lib = lib
     return lib
 
@@ -479,7 +506,49 @@ def hip_align(store: SequenceStore, scoring: Scoring, triangular: bool = False, 
     return matrix if triangular else matrix.reshape(n, n)
 
 
-def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int) -> tuple[np.ndarray, np.ndarray]:
+NORM_SELF, NORM_LENGTH = 0, 1        # SA_NORM_SELF, SA_NORM_LENGTH: where the per-sequence denominator comes from
+NORM_MIN, NORM_MAX, NORM_MEAN = 0, 1, 2  # SA_NORM_MIN, SA_NORM_MAX, SA_NORM_MEAN: how d[i] and d[j] combine
+NORM_SCALE = 1000000                 # SA_NORM_SCALE: a normalised score is in parts per million
+
+
+class Norm:
+    """struct sa_norm: normalised scores for the selections -- source NORM_SELF (self-scores) or NORM_LENGTH (lengths), rule
+    NORM_MIN / NORM_MAX / NORM_MEAN.  Which values are valid is the library's to say."""
+
+    def __init__(self, source: int = NORM_SELF, rule: int = NORM_MIN):
+        self.source, self.rule = int(source), int(rule)
+        for v in (self.source, self.rule):
+            if not -2**31 <= v < 2**31:
+                raise AlignError(f"{v} is not an int32")
+
+    def _as_c(self, n: int) -> tuple["_Norm", np.ndarray]:
+        """the C struct and the host array that receives the denominators"""
+        den = np.zeros(max(int(n), 1), np.int32)
+        return _Norm(self.source, self.rule, den.ctypes.data), den
+
+    def __repr__(self) -> str:
+        return f"Norm(source={self.source}, rule={self.rule})"
+
+
+def norm_value(s: int, di: int, dj: int, rule: int) -> int:
+    """sa_norm_value (host only): the normalised value of score s under denominators di, dj -- floor division towards minus
+    infinity in parts per million, saturated to int32; INT32_MIN for a denominator <= 0"""
+    args = [int(s), int(di), int(dj), int(rule)]
+    for v in args:
+        if not -2**31 <= v < 2**31:
+            raise AlignError(f"{v} is not an int32")
+    got = int(load_library().sa_norm_value(*args))
+    if args[3] not in (NORM_MIN, NORM_MAX, NORM_MEAN):  # (refused by the library: the message is its own)
+        raise AlignError(_err())
+    return got
+
+
+def last_normalize_seconds() -> float:
+    """device time of denominators + sweep in the last call with a norm / DeflateJob.normalize call"""
+    return float(load_library().sa_hip_last_normalize_seconds())
+
+
+def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int, norm: Optional[Norm] = None):
     """sa_hip_neighbors: the k best partners of every sequence, selected on the device -- (index, score), two (N, k) int32
     arrays; row r lists the c != r by score descending, then index ascending.  The matrix never leaves the device.
     1 <= k <= min(N - 1, NEIGHBORS_MAX)."""
@@ -489,6 +558,11 @@ def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int) -> tuple[np.nd
     rows = max(n, 1) * max(min(k, NEIGHBORS_MAX), 1)
     index, score = np.empty(rows, np.int32), np.empty(rows, np.int32)
     sc = scoring._as_c()
+    if norm is not None:  # normalised scores: (index, score, denominators)
+        cn, den = norm._as_c(n)
+        if not load_library().sa_hip_neighbors_norm(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data, C.byref(cn)):
+            raise AlignError(_err())
+        return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k), den[:n]
     if not load_library().sa_hip_neighbors(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data):
         raise AlignError(_err())
     return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k)
@@ -524,12 +598,15 @@ def _take_edges(lib, handle) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     return offsets, index, score
 
 
-def hip_edges(store: SequenceStore, scoring: Scoring, min_score: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+def hip_edges(store: SequenceStore, scoring: Scoring, min_score: int, norm: Optional[Norm] = None):
     """sa_hip_edges: every pair that scores at least min_score, as the symmetric adjacency in CSR form, built on the device --
     (offsets int64[N + 1], index int32[E], score int32[E]); row r's columns are index[offsets[r]:offsets[r + 1]], ascending.
     The matrix never leaves the device.  Any int32 threshold is valid."""
     lib = load_library()
     sc = scoring._as_c()
+    if norm is not None:  # min_score in parts per million: (offsets, index, score, denominators)
+        cn, den = norm._as_c(store.num)
+        return _take_edges(lib, lib.sa_hip_edges_norm(store._as_c(), C.byref(sc), _min_score(min_score), C.byref(cn))) + (den[:store.num],)
     return _take_edges(lib, lib.sa_hip_edges(store._as_c(), C.byref(sc), _min_score(min_score)))
 
 
@@ -554,12 +631,15 @@ def _take_linkage(lib, handle) -> tuple[np.ndarray, np.ndarray]:
     return pairs.reshape(m, 2), score
 
 
-def hip_linkage(store: SequenceStore, scoring: Scoring) -> tuple[np.ndarray, np.ndarray]:
+def hip_linkage(store: SequenceStore, scoring: Scoring, norm: Optional[Norm] = None):
     """sa_hip_linkage: the single-linkage tree (the maximum spanning tree of the score matrix), built on the device --
     (pairs int32 (N - 1, 2) with lo < hi, score int32 (N - 1,)), sorted by score descending, then packed index ascending: the
     order in which single linkage joins clusters.  The matrix never leaves the device."""
     lib = load_library()
     sc = scoring._as_c()
+    if norm is not None:  # the tree of the normalised scores: (pairs, score, denominators)
+        cn, den = norm._as_c(store.num)
+        return _take_linkage(lib, lib.sa_hip_linkage_norm(store._as_c(), C.byref(sc), C.byref(cn))) + (den[:store.num],)
     return _take_linkage(lib, lib.sa_hip_linkage(store._as_c(), C.byref(sc)))
 
 
@@ -619,7 +699,7 @@ def select_scratch_bytes(m: int) -> int:
     return int(load_library().sa_select_scratch_bytes(int(m)))
 
 
-def hip_select(store: SequenceStore, scoring: Scoring, ranks) -> tuple[np.ndarray, np.ndarray]:
+def hip_select(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Norm] = None):
     """sa_hip_select: for each rank k (up to 16, any order, duplicates allowed) into the ascending order of the N (N - 1) / 2
     pair scores, (values int32 (m,), below int64 (m,)): the k-th smallest score and the number of pairs strictly below it,
     selected on the device.  The matrix never leaves the device."""
@@ -627,29 +707,44 @@ def hip_select(store: SequenceStore, scoring: Scoring, ranks) -> tuple[np.ndarra
     sc = scoring._as_c()
     r = _ranks(ranks)
     value, below = _select_room(len(r))
+    if norm is not None:  # order statistics of the normalised scores: (values, below, denominators)
+        cn, den = norm._as_c(store.num)
+        if not lib.sa_hip_select_norm(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data, C.byref(cn)):
+            raise AlignError(_err())
+        return value[:len(r)].copy(), below[:len(r)].copy(), den[:store.num]
     if not lib.sa_hip_select(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data):
         raise AlignError(_err())
     return value[:len(r)].copy(), below[:len(r)].copy()
 
 
-def hip_edges_at_rank(store: SequenceStore, scoring: Scoring, rank: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, int, int]:
+def hip_edges_at_rank(store: SequenceStore, scoring: Scoring, rank: int, norm: Optional[Norm] = None):
     """sa_hip_edges_at_rank: one alignment, the score T at `rank` and the score graph at T from the same device matrix --
     (offsets, index, score) as hip_edges returns them, then min_score = T and below = the pairs under T; E = 2 (P - below)"""
     lib = load_library()
     sc = scoring._as_c()
     cut, below = C.c_int32(0), C.c_int64(0)
     (rank,) = _ranks([rank])
+    if norm is not None:  # (offsets, index, score, min_score, below, denominators), all over the normalised scores
+        cn, den = norm._as_c(store.num)
+        offsets, index, score = _take_edges(lib, lib.sa_hip_edges_at_rank_norm(store._as_c(), C.byref(sc), int(rank), C.byref(cut),
+                                                                               C.byref(below), C.byref(cn)))
+        return offsets, index, score, int(cut.value), int(below.value), den[:store.num]
     offsets, index, score = _take_edges(lib, lib.sa_hip_edges_at_rank(store._as_c(), C.byref(sc), int(rank), C.byref(cut), C.byref(below)))
     return offsets, index, score, int(cut.value), int(below.value)
 
 
-def hip_linkage_with_ranks(store: SequenceStore, scoring: Scoring, ranks) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+def hip_linkage_with_ranks(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Norm] = None):
     """sa_hip_linkage_with_ranks: one alignment, then hip_select's (values, below) for `ranks` and hip_linkage's (pairs, score)
     from the same device matrix -- (pairs, score, values, below)"""
     lib = load_library()
     sc = scoring._as_c()
     r = _ranks(ranks)
     value, below = _select_room(len(r))
+    if norm is not None:  # (pairs, score, values, below, denominators), all over the normalised scores
+        cn, den = norm._as_c(store.num)
+        pairs, score = _take_linkage(lib, lib.sa_hip_linkage_with_ranks_norm(store._as_c(), C.byref(sc), r.ctypes.data, len(r),
+                                                                              value.ctypes.data, below.ctypes.data, C.byref(cn)))
+        return pairs, score, value[:len(r)].copy(), below[:len(r)].copy(), den[:store.num]
     pairs, score = _take_linkage(lib, lib.sa_hip_linkage_with_ranks(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data,
                                                                      below.ctypes.data))
     return pairs, score, value[:len(r)].copy(), below[:len(r)].copy()
@@ -955,6 +1050,25 @@ class Context:
                                    C.c_void_p(d_below_ptr), C.c_void_p(d_scratch_ptr), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def denominators(self, source: int, d_den_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_denominators: the per-sequence denominators (NORM_SELF: self-scores by the full DP, NORM_LENGTH: lengths) into
+        the device array d_den (N int32), asynchronously on `stream`; not beside align_range of this context on another stream"""
+        source = int(source)
+        if not -2**31 <= source < 2**31:
+            raise AlignError(f"source = {source} is not an int32")
+        if self._lib.sa_ctx_denominators(self._h, source, C.c_void_p(d_den_ptr or None), C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def normalize(self, d_packed_ptr: int, d_den_ptr: int, rule: int, d_out_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_normalize: the whole packed device matrix of this store divided by the denominators d_den (any N int32 of
+        device memory) under `rule`, into d_out -- d_packed itself (in place) or a disjoint buffer -- asynchronously on `stream`"""
+        rule = int(rule)
+        if not -2**31 <= rule < 2**31:
+            raise AlignError(f"rule = {rule} is not an int32")
+        if self._lib.sa_ctx_normalize(self._h, C.c_void_p(d_packed_ptr or None), C.c_void_p(d_den_ptr or None), rule,
+                                      C.c_void_p(d_out_ptr or None), C.c_void_p(stream)):
+            raise AlignError(_err())
+
     def alignments(self, pairs) -> Alignments:
         """sa_ctx_alignments: the alignments of the listed pairs of this context's store (see hip_alignments)"""
         arr = _pairs_array(pairs)
@@ -1052,6 +1166,15 @@ class DeflateJob:
         if self._lib.sa_zjob_select(self._h, r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data):
             raise AlignError(_err())
         return value[:len(r)].copy(), below[:len(r)].copy()
+
+    def normalize(self, norm: Norm) -> np.ndarray:
+        """sa_zjob_normalize: normalises the finished matrix of a begin() job in place, once, after next() has returned [];
+        neighbors / edges / linkage / select then answer over normalised scores (the tiles handed out stay raw).  Returns the
+        denominators (N int32)."""
+        cn, den = norm._as_c(self.num)
+        if self._lib.sa_zjob_normalize(self._h, C.byref(cn)):
+            raise AlignError(_err())
+        return den[:self.num]
 
     def stats(self) -> dict:
         e, c, r, o = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()

@@ -443,8 +443,12 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 			sa_ctx_destroy(ctx);
 	}
 	/* the alignment is in order on `stream` when this returns true; `who` names the entry point in messages */
-	bool begin(const char *who, struct sa_input in, const struct sa_scoring *sc)
+	/* norm != nullptr: denominators + sweep follow the alignment on the stream, in place (sa_normalize.hip), and the stream is
+	 * synchronised once here; what the caller selects next reads normalised scores */
+	bool begin(const char *who, struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm = nullptr)
 	{
+		if (norm && !sa_norm_check(who, norm)) /* (before the alignment is launched) */
+			return false;
 		if (sa_hip_device_count() <= 0) {
 			sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
 			return false;
@@ -468,6 +472,8 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 		if (sa_ctx_align_range(ctx, 0, pairs, d_packed, stream) != 0)
 			return false;
 		SA_HIP_CHECK(hipEventRecord(e1, stream), return false);
+		if (norm && !sa_normalize_in_place(who, ctx, d_packed, norm, stream))
+			return false;
 		return true;
 	}
 	/* after the stream has been synchronised: the alignment's device time goes to sa_hip_last_align_seconds */
@@ -480,20 +486,23 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 	}
 };
 
-static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score)
+static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm)
 {
+	const char *who = norm ? "sa_hip_neighbors_norm" : "sa_hip_neighbors";
 	if (!sc || !index || !score) {
-		sa_set_error("sa_hip_neighbors: null argument");
+		sa_set_error("%s: null argument", who);
 		return false;
 	}
+	if (norm && !sa_norm_check(who, norm))
+		return false;
 	if (sa_hip_device_count() <= 0) {
 		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
 		return false;
 	}
-	if (!sa_neighbors_check("sa_hip_neighbors", in.num, k))
+	if (!sa_neighbors_check(who, in.num, k))
 		return false;
 	DeviceRun run;
-	if (!run.begin("sa_hip_neighbors", in, sc))
+	if (!run.begin(who, in, sc, norm))
 		return false;
 	if (!sa_neighbors_to_host(run.d_packed, in.num, k, index, score, run.stream))
 		return false;
@@ -502,19 +511,25 @@ static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int3
 
 extern "C" bool sa_hip_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score)
 {
-	return sa_guard("sa_hip_neighbors", false, [&] { return neighbors_impl(in, sc, k, index, score); });
+	return sa_guard("sa_hip_neighbors", false, [&] { return neighbors_impl(in, sc, k, index, score, nullptr); });
 }
 
-static sa_edges *edges_impl(struct sa_input in, const struct sa_scoring *sc, int32_t min_score)
+extern "C" bool sa_hip_neighbors_norm(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm)
 {
+	return sa_guard("sa_hip_neighbors_norm", false, [&] { return neighbors_impl(in, sc, k, index, score, norm); });
+}
+
+static sa_edges *edges_impl(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm)
+{
+	const char *who = norm ? "sa_hip_edges_norm" : "sa_hip_edges";
 	if (!sc) {
-		sa_set_error("sa_hip_edges: null argument");
+		sa_set_error("%s: null argument", who);
 		return nullptr;
 	}
 	DeviceRun run;
-	if (!run.begin("sa_hip_edges", in, sc))
+	if (!run.begin(who, in, sc, norm))
 		return nullptr;
-	sa_edges *res = sa_edges_to_host("sa_hip_edges", run.d_packed, in.num, min_score, run.stream);
+	sa_edges *res = sa_edges_to_host(who, run.d_packed, in.num, min_score, run.stream);
 	if (res && !run.finish()) {
 		sa_edges_destroy(res);
 		res = nullptr;
@@ -524,19 +539,25 @@ static sa_edges *edges_impl(struct sa_input in, const struct sa_scoring *sc, int
 
 extern "C" sa_edges *sa_hip_edges(struct sa_input in, const struct sa_scoring *sc, int32_t min_score)
 {
-	return sa_guard("sa_hip_edges", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score); });
+	return sa_guard("sa_hip_edges", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, nullptr); });
 }
 
-static sa_linkage *linkage_impl(struct sa_input in, const struct sa_scoring *sc)
+extern "C" sa_edges *sa_hip_edges_norm(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm)
 {
+	return sa_guard("sa_hip_edges_norm", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, norm); });
+}
+
+static sa_linkage *linkage_impl(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm)
+{
+	const char *who = norm ? "sa_hip_linkage_norm" : "sa_hip_linkage";
 	if (!sc) {
-		sa_set_error("sa_hip_linkage: null argument");
+		sa_set_error("%s: null argument", who);
 		return nullptr;
 	}
 	DeviceRun run;
-	if (!run.begin("sa_hip_linkage", in, sc))
+	if (!run.begin(who, in, sc, norm))
 		return nullptr;
-	sa_linkage *res = sa_linkage_to_host("sa_hip_linkage", run.d_packed, in.num, run.stream);
+	sa_linkage *res = sa_linkage_to_host(who, run.d_packed, in.num, run.stream);
 	if (res && !run.finish()) {
 		sa_linkage_destroy(res);
 		res = nullptr;
@@ -546,47 +567,59 @@ static sa_linkage *linkage_impl(struct sa_input in, const struct sa_scoring *sc)
 
 extern "C" sa_linkage *sa_hip_linkage(struct sa_input in, const struct sa_scoring *sc)
 {
-	return sa_guard("sa_hip_linkage", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc); });
+	return sa_guard("sa_hip_linkage", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, nullptr); });
+}
+
+extern "C" sa_linkage *sa_hip_linkage_norm(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm)
+{
+	return sa_guard("sa_hip_linkage_norm", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, norm); });
 }
 
 /* ---- order statistics of the matrix, alone and as the cut of what follows them on the same device matrix -------------------- */
-static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below)
+static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below, const struct sa_norm *norm)
 {
+	const char *who = norm ? "sa_hip_select_norm" : "sa_hip_select";
 	if (!sc || !ranks || !value || !below) {
-		sa_set_error("sa_hip_select: null argument");
+		sa_set_error("%s: null argument", who);
 		return false;
 	}
-	if (!sa_select_check("sa_hip_select", in.num, ranks, m)) /* (before the alignment: P follows from in.num) */
+	if (!sa_select_check(who, in.num, ranks, m)) /* (before the alignment: P follows from in.num) */
 		return false;
 	DeviceRun run;
-	if (!run.begin("sa_hip_select", in, sc))
+	if (!run.begin(who, in, sc, norm))
 		return false;
-	if (!sa_select_to_host("sa_hip_select", run.d_packed, in.num, ranks, m, value, below, run.stream))
+	if (!sa_select_to_host(who, run.d_packed, in.num, ranks, m, value, below, run.stream))
 		return false;
 	return run.finish();
 }
 
 extern "C" bool sa_hip_select(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below)
 {
-	return sa_guard("sa_hip_select", false, [&] { return select_impl(in, sc, ranks, m, value, below); });
+	return sa_guard("sa_hip_select", false, [&] { return select_impl(in, sc, ranks, m, value, below, nullptr); });
 }
 
-static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below)
+extern "C" bool sa_hip_select_norm(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below, const struct sa_norm *norm)
 {
+	return sa_guard("sa_hip_select_norm", false, [&] { return select_impl(in, sc, ranks, m, value, below, norm); });
+}
+
+static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below, const struct sa_norm *norm)
+{
+	const char *who = norm ? "sa_hip_edges_at_rank_norm" : "sa_hip_edges_at_rank";
 	if (!sc || !min_score || !below) {
-		sa_set_error("sa_hip_edges_at_rank: null argument");
+		sa_set_error("%s: null argument", who);
 		return nullptr;
 	}
-	if (!sa_select_check("sa_hip_edges_at_rank", in.num, &rank, 1))
+	if (!sa_select_check(who, in.num, &rank, 1))
 		return nullptr;
 	DeviceRun run;
-	if (!run.begin("sa_hip_edges_at_rank", in, sc))
+	if (!run.begin(who, in, sc, norm))
 		return nullptr;
 	int32_t cut = 0;
 	int64_t under = 0;
-	if (!sa_select_to_host("sa_hip_edges_at_rank", run.d_packed, in.num, &rank, 1, &cut, &under, run.stream))
+	if (!sa_select_to_host(who, run.d_packed, in.num, &rank, 1, &cut, &under, run.stream))
 		return nullptr;
-	sa_edges *res = sa_edges_to_host("sa_hip_edges_at_rank", run.d_packed, in.num, cut, run.stream);
+	sa_edges *res = sa_edges_to_host(who, run.d_packed, in.num, cut, run.stream);
 	if (res && !run.finish()) {
 		sa_edges_destroy(res);
 		res = nullptr;
@@ -600,26 +633,32 @@ static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring 
 
 extern "C" sa_edges *sa_hip_edges_at_rank(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below)
 {
-	return sa_guard("sa_hip_edges_at_rank", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below); });
+	return sa_guard("sa_hip_edges_at_rank", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, nullptr); });
+}
+
+extern "C" sa_edges *sa_hip_edges_at_rank_norm(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below, const struct sa_norm *norm)
+{
+	return sa_guard("sa_hip_edges_at_rank_norm", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, norm); });
 }
 
 static sa_linkage *linkage_with_ranks_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value,
-					   int64_t *below)
+					   int64_t *below, const struct sa_norm *norm)
 {
+	const char *who = norm ? "sa_hip_linkage_with_ranks_norm" : "sa_hip_linkage_with_ranks";
 	if (!sc || !ranks || !value || !below) {
-		sa_set_error("sa_hip_linkage_with_ranks: null argument");
+		sa_set_error("%s: null argument", who);
 		return nullptr;
 	}
-	if (!sa_select_check("sa_hip_linkage_with_ranks", in.num, ranks, m))
+	if (!sa_select_check(who, in.num, ranks, m))
 		return nullptr;
 	DeviceRun run;
-	if (!run.begin("sa_hip_linkage_with_ranks", in, sc))
+	if (!run.begin(who, in, sc, norm))
 		return nullptr;
 	int32_t cut[SA_HIP_SELECT_MAX];
 	int64_t under[SA_HIP_SELECT_MAX];
-	if (!sa_select_to_host("sa_hip_linkage_with_ranks", run.d_packed, in.num, ranks, m, cut, under, run.stream))
+	if (!sa_select_to_host(who, run.d_packed, in.num, ranks, m, cut, under, run.stream))
 		return nullptr;
-	sa_linkage *res = sa_linkage_to_host("sa_hip_linkage_with_ranks", run.d_packed, in.num, run.stream);
+	sa_linkage *res = sa_linkage_to_host(who, run.d_packed, in.num, run.stream);
 	if (res && !run.finish()) {
 		sa_linkage_destroy(res);
 		res = nullptr;
@@ -636,7 +675,14 @@ extern "C" sa_linkage *sa_hip_linkage_with_ranks(struct sa_input in, const struc
 						 int32_t *value, int64_t *below)
 {
 	return sa_guard("sa_hip_linkage_with_ranks", (sa_linkage *)nullptr,
-			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below); });
+			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, nullptr); });
+}
+
+extern "C" sa_linkage *sa_hip_linkage_with_ranks_norm(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
+						 int32_t *value, int64_t *below, const struct sa_norm *norm)
+{
+	return sa_guard("sa_hip_linkage_with_ranks_norm", (sa_linkage *)nullptr,
+			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, norm); });
 }
 
 extern "C" int sa_hip_last_align_path(void) { return g_last_align_path.load(); }

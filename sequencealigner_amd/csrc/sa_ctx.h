@@ -176,4 +176,10 @@ bool sa_align_gathered(struct sa_input in, struct sa_output out, const struct sa
 		       double *phase_seconds, double *breakdown_ms);
 bool sa_rccl_available(std::string *why);
 
+/* sa_normalize.hip: source and rule inside their enums, or sa_set_error; denominators + sweep IN PLACE over a finished device
+ * matrix of ctx's store, in order on `s`, which is synchronised (the *_norm calls, sa_zjob_normalize).  norm->denominators,
+ * when not null, receives d[0 .. N); the device time goes to sa_hip_last_normalize_seconds. */
+bool sa_norm_check(const char *who, const struct sa_norm *norm);
+bool sa_normalize_in_place(const char *who, sa_ctx *ctx, int32_t *d_packed, const struct sa_norm *norm, hipStream_t s);
+
 #endif /* SA_CTX_H */

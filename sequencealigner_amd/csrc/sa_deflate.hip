@@ -736,6 +736,7 @@ struct sa_zjob {
 	bool pairs = false;  /* levels SA_Z_PAIR_LEVEL .. 9: the pair parse */
 	const int32_t *d_packed = nullptr, *d_full = nullptr;
 	int32_t *d_owned = nullptr; /* the packed matrix, when the job made it (sa_hip_tiles_begin) */
+	bool normalized = false;    /* sa_zjob_normalize has rewritten it in place */
 	sa_ctx *ctx = nullptr;
 	uint32_t *d_slots = nullptr, *d_seg = nullptr; /* d_seg: bytes, s1, s2, offset, [nc * nseg] each */
 	uint32_t *d_ghist = nullptr, *d_tile_adler = nullptr;
@@ -1361,6 +1362,46 @@ extern "C" sa_linkage *sa_zjob_linkage(sa_zjob *z)
 		}
 		SA_HIP_CHECK(hipSetDevice(z->device), return nullptr);
 		return sa_linkage_to_host("sa_zjob_linkage", z->d_packed, z->num, z->stream);
+	});
+}
+
+/* Normalises the job's own packed matrix in place (sa_normalize.hip), in order behind whatever the job has on its stream: every
+ * tile has been encoded and handed out by then, so the tiles stay raw and what is selected afterwards is normalised.  Refuses what
+ * sa_zjob_edges refuses, with the same wording, and a matrix that is not the job's to rewrite. */
+extern "C" int sa_zjob_normalize(sa_zjob *z, const struct sa_norm *norm)
+{
+	return sa_guard("sa_zjob_normalize", 1, [&] {
+		if (!z || !norm) {
+			sa_set_error("sa_zjob_normalize: null argument");
+			return 1;
+		}
+		if (!z->peers.empty()) {
+			sa_set_error("sa_zjob_normalize: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+			return 1;
+		}
+		if (!z->d_packed) {
+			sa_set_error("sa_zjob_normalize: the job walks a full matrix; the sweep reads the packed index");
+			return 1;
+		}
+		if (!z->d_owned || !z->ctx || z->d_owned != z->d_packed) {
+			sa_set_error("sa_zjob_normalize: the job walks the caller's matrix, which is const; only a sa_hip_tiles_begin job owns its matrix");
+			return 1;
+		}
+		if (z->shells && z->next_batch < zjob_batches(z)) {
+			sa_set_error("sa_zjob_normalize: the walk is not finished (sa_zjob_next has not returned 0 yet)");
+			return 1;
+		}
+		if (z->normalized) {
+			sa_set_error("sa_zjob_normalize: the job's matrix has been normalised already");
+			return 1;
+		}
+		if (!sa_norm_check("sa_zjob_normalize", norm))
+			return 1;
+		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
+		if (!sa_normalize_in_place("sa_zjob_normalize", z->ctx, z->d_owned, norm, z->stream))
+			return 1;
+		z->normalized = true;
+		return 0;
 	});
 }
 
