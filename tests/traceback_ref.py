@@ -4,7 +4,12 @@ mirror for a > b.  Shares no code with the library; slow and literal on purpose 
 
 align_pair(scoring, seq_a, seq_b, a_index, b_index) -> dict(score, a_begin, a_end, b_begin, b_end, columns, identities, cigar)
 with cigar a list of (length, op) and op one of "M", "I" (a residue of a only), "D" (a residue of b only).
-rescore(...) is what "the alignment has this score" means."""
+rescore(...) is what "the alignment has this score" means.
+
+align_pair(..., flipped_ties=True) walks the same tables with the OTHER order among equally good moves (NW: up, diagonal,
+left; Gotoh / SW in state M: X, Y, diagonal): an alignment of the same score that breaks the contract wherever there was a
+tie.  The tests count with it how many of their pairs a device with another tie order could not pass; nothing else uses it.
+`tabs` takes the result of tables(...) for the pair in its canonical orientation, so that both walks share one fill."""
 from __future__ import annotations
 
 SCORE_MIN = -(1 << 30)
@@ -58,12 +63,19 @@ def tables(scoring, lo: list[int], hi: list[int]):
     return M, X, Y
 
 
-def align_pair(scoring, seq_a: bytes, seq_b: bytes, a_index: int, b_index: int) -> dict:
+def canonical(scoring, seq_a: bytes, seq_b: bytes, a_index: int, b_index: int):
+    """(lo, hi): the codes of the row and of the column sequence"""
+    if a_index > b_index:
+        return _codes(scoring, seq_b), _codes(scoring, seq_a)
+    return _codes(scoring, seq_a), _codes(scoring, seq_b)
+
+
+def align_pair(scoring, seq_a: bytes, seq_b: bytes, a_index: int, b_index: int, flipped_ties: bool = False, tabs=None) -> dict:
     assert a_index != b_index
     flip = a_index > b_index
-    lo, hi = (_codes(scoring, seq_b), _codes(scoring, seq_a)) if flip else (_codes(scoring, seq_a), _codes(scoring, seq_b))
+    lo, hi = canonical(scoring, seq_a, seq_b, a_index, b_index)
     m, n = len(lo), len(hi)
-    M, X, Y = tables(scoring, lo, hi)
+    M, X, Y = tabs if tabs is not None else tables(scoring, lo, hi)
     g, o = scoring.gap_pen, scoring.gap_opn
     r, c = m, n
     ops = []  # end first, canonical orientation: "I" consumes lo, "D" consumes hi
@@ -77,7 +89,19 @@ def align_pair(scoring, seq_a: bytes, seq_b: bytes, a_index: int, b_index: int) 
         score = M[m][n]
     r_end, c_end = r, c
     ident = 0
-    if scoring.method == NW:
+    if scoring.method == NW and flipped_ties:
+        while (r, c) != (0, 0):
+            if r > 0 and M[r][c] == M[r - 1][c] + g:
+                ops.append("I")
+                r -= 1
+            elif r > 0 and c > 0 and M[r][c] == M[r - 1][c - 1] + _sim(scoring, lo[r - 1], hi[c - 1]):
+                ops.append("M")
+                ident += lo[r - 1] == hi[c - 1]
+                r, c = r - 1, c - 1
+            else:
+                ops.append("D")
+                c -= 1
+    elif scoring.method == NW:
         while (r, c) != (0, 0):
             if r > 0 and c > 0 and M[r][c] == M[r - 1][c - 1] + _sim(scoring, lo[r - 1], hi[c - 1]):
                 ops.append("M")
@@ -97,7 +121,10 @@ def align_pair(scoring, seq_a: bytes, seq_b: bytes, a_index: int, b_index: int) 
                     break
                 if (r, c) == (0, 0):
                     break
-                if r > 0 and c > 0 and M[r][c] == M[r - 1][c - 1] + _sim(scoring, lo[r - 1], hi[c - 1]):
+                diagonal = r > 0 and c > 0 and M[r][c] == M[r - 1][c - 1] + _sim(scoring, lo[r - 1], hi[c - 1])
+                if flipped_ties and M[r][c] in (X[r][c], Y[r][c]):
+                    diagonal = False
+                if diagonal:
                     ops.append("M")
                     ident += lo[r - 1] == hi[c - 1]
                     r, c = r - 1, c - 1
