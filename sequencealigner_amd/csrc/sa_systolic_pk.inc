@@ -32,8 +32,8 @@
  * step run before its DPP move, while X[0] still holds the previous step's left value -- the diagonal input of column
  * 0 -- so the two alternating left-neighbour registers of the other methods are one here.  (Bubble rows may wrap as
  * before; a carry out of such a field lands in a cell of the same bubble row of the same lane, which is never stored.)
- * The instruction's issue cost on this chip is NOT on record yet: tools/microbench/valu_rates.hip (row v_lshl_add_u64)
- * and max3_f16.hip (paired chains of 8 and 7 registers) are the measurement, DESIGN.md 4.1 / 4.2 say what is known.
+ * The instruction issues like every other VOP3 here (tools/microbench/valu_rates.hip, row v_lshl_add_u64), and the step
+ * with it is 9.9 % faster on cfg 2 than with two plain adds (DESIGN.md 4.1 / 4.2, profiles/nw_step_ab_parent.txt).
  * Gotoh and SW make their diagonal adds just in time inside the chain and keep the 32-bit add.
  *
  * Three-way maxima in one instruction (8-lane groups).  gfx950 has v_pk_maximum3_f16, and on the bit patterns
@@ -102,6 +102,9 @@
 #ifndef SA_PK_PAIRED_ADDS
 #define SA_PK_PAIRED_ADDS 1 /* NW: one v_lshl_add_u64 for the diagonal adds of two neighbouring columns (0: two v_add_u32) */
 #endif
+#ifndef SA_PK_CHAINED_MAX3
+#define SA_PK_CHAINED_MAX3 1 /* NW: the step's dependent maxima as asm statements of up to eight links, no wait states between them (0: one statement per link) */
+#endif
 #ifndef SA_PK_QUIET_BLOCKS
 #define SA_PK_QUIET_BLOCKS 0 /* measured slower, see do_block */
 #endif
@@ -135,6 +138,61 @@ template <bool F16> __device__ __forceinline__ uint32_t pkmax3(uint32_t a, uint3
 	}
 	return pkmax(pkmax(a, b), c);
 }
+#if SA_PK_CHAINED_MAX3
+/* N = 1..8 links of NW's dependent chain V[i] = max3(d[i], V[i], V[i - 1]) (V[-1] = left) as ONE asm statement.  The compiler
+ * puts a wait state (s_nop 0) between a v_pk_maximum3_f16 and an adjacent instruction that reads its result: behind inline
+ * asm because any asm result may be a partial-register (destination-select) write, and behind the same instruction selected
+ * from __builtin_elementwise_maximum just as well (tried: 12 of the 13 pads of a K = 14 step stay, DESIGN.md 4.2).  The
+ * instruction writes its whole destination register and the hardware needs no such state: tools/microbench/max3_f16.hip
+ * runs eight links back to back at one wave per SIMD over every pair of patterns against the u16 recurrence.  The compiler
+ * does not look inside a statement, so the chain is written as statements of eight links: K = 14 keeps 1 pad of 13. */
+template <int N> __device__ __forceinline__ void pkmax3_chain(uint32_t *V, const uint32_t *d, uint32_t left)
+{
+	static_assert(N >= 1 && N <= 8, "one statement holds up to eight links");
+#define SA_LK0 "v_pk_maximum3_f16 %[v0], %[d0], %[v0], %[l]"
+#define SA_LK(i, p) "\n\tv_pk_maximum3_f16 %[v" #i "], %[d" #i "], %[v" #i "], %[v" #p "]"
+#define SA_VO(i) [v##i] "+v"(V[i])
+#define SA_DI(i) [d##i] "v"(d[i])
+	if constexpr (N == 1)
+		asm(SA_LK0 : SA_VO(0) : SA_DI(0), [l] "v"(left));
+	else if constexpr (N == 2)
+		asm(SA_LK0 SA_LK(1, 0) : SA_VO(0), SA_VO(1) : SA_DI(0), SA_DI(1), [l] "v"(left));
+	else if constexpr (N == 3)
+		asm(SA_LK0 SA_LK(1, 0) SA_LK(2, 1) : SA_VO(0), SA_VO(1), SA_VO(2) : SA_DI(0), SA_DI(1), SA_DI(2), [l] "v"(left));
+	else if constexpr (N == 4)
+		asm(SA_LK0 SA_LK(1, 0) SA_LK(2, 1) SA_LK(3, 2)
+		    : SA_VO(0), SA_VO(1), SA_VO(2), SA_VO(3)
+		    : SA_DI(0), SA_DI(1), SA_DI(2), SA_DI(3), [l] "v"(left));
+	else if constexpr (N == 5)
+		asm(SA_LK0 SA_LK(1, 0) SA_LK(2, 1) SA_LK(3, 2) SA_LK(4, 3)
+		    : SA_VO(0), SA_VO(1), SA_VO(2), SA_VO(3), SA_VO(4)
+		    : SA_DI(0), SA_DI(1), SA_DI(2), SA_DI(3), SA_DI(4), [l] "v"(left));
+	else if constexpr (N == 6)
+		asm(SA_LK0 SA_LK(1, 0) SA_LK(2, 1) SA_LK(3, 2) SA_LK(4, 3) SA_LK(5, 4)
+		    : SA_VO(0), SA_VO(1), SA_VO(2), SA_VO(3), SA_VO(4), SA_VO(5)
+		    : SA_DI(0), SA_DI(1), SA_DI(2), SA_DI(3), SA_DI(4), SA_DI(5), [l] "v"(left));
+	else if constexpr (N == 7)
+		asm(SA_LK0 SA_LK(1, 0) SA_LK(2, 1) SA_LK(3, 2) SA_LK(4, 3) SA_LK(5, 4) SA_LK(6, 5)
+		    : SA_VO(0), SA_VO(1), SA_VO(2), SA_VO(3), SA_VO(4), SA_VO(5), SA_VO(6)
+		    : SA_DI(0), SA_DI(1), SA_DI(2), SA_DI(3), SA_DI(4), SA_DI(5), SA_DI(6), [l] "v"(left));
+	else
+		asm(SA_LK0 SA_LK(1, 0) SA_LK(2, 1) SA_LK(3, 2) SA_LK(4, 3) SA_LK(5, 4) SA_LK(6, 5) SA_LK(7, 6)
+		    : SA_VO(0), SA_VO(1), SA_VO(2), SA_VO(3), SA_VO(4), SA_VO(5), SA_VO(6), SA_VO(7)
+		    : SA_DI(0), SA_DI(1), SA_DI(2), SA_DI(3), SA_DI(4), SA_DI(5), SA_DI(6), SA_DI(7), [l] "v"(left));
+#undef SA_LK0
+#undef SA_LK
+#undef SA_VO
+#undef SA_DI
+}
+template <int K, int Q0 = 0> __device__ __forceinline__ void pkmax3_chain_all(uint32_t (&V)[K], const uint32_t (&d)[K], uint32_t left)
+{
+	if constexpr (Q0 < K) {
+		constexpr int N = K - Q0 < 8 ? K - Q0 : 8;
+		pkmax3_chain<N>(&V[Q0], &d[Q0], Q0 ? V[Q0 ? Q0 - 1 : 0] : left);
+		pkmax3_chain_all<K, Q0 + N>(V, d, left);
+	}
+}
+#endif
 /* Two diagonal adds in one instruction: (hi:lo) + (phi:plo) as ONE 64-bit integer add (v_lshl_add_u64, shift 0) on
  * even-aligned register pairs.  Exact for the same reason the 32-bit add is (see the header): no u16 field of a live
  * value carries, so nothing crosses from a register's high half into its neighbour's low half either. */
@@ -805,9 +863,13 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 				/* (NW keeps its K diagonal adds ahead of the chain -- issued before the DPP move, above: measured 2.6 %
 				 * faster than just-in-time adds) */
 				if (F16) {
+#if SA_PK_CHAINED_MAX3
+					pkmax3_chain_all<K>(V, dnw, vleft);
+#else
 #pragma unroll
 					for (int q = 0; q < K; q++)
 						V[q] = pkmax3<true>(dnw[q], V[q], q ? V[q - 1] : vleft);
+#endif
 				} else {
 					uint32_t tq[K];
 					tq[0] = pkmax(dnw[0], V[0]);
