@@ -1023,6 +1023,44 @@ int sa_host_write_normalization(const char *path, const struct sa_host_store *s,
 	return rc;
 }
 
+/* Percent identity (include/seqalign_hip.h: SA_PID_*): /identity_rule 1 I32LE (the denominator) and /identity_scale 1 I32LE,
+ * contiguous, added to the finished file at `path`, whose other datasets stay as they are.  The arguments are checked before
+ * anything is opened. */
+int sa_host_write_identity(const char *path, int32_t denom)
+{
+	if (!path)
+		return fail("Identity data missing");
+	if (denom != SA_PID_COLUMNS && denom != SA_PID_SHORTER && denom != SA_PID_LONGER && denom != SA_PID_MEAN)
+		return fail("Identity denominator %d is none of columns (%d), shorter (%d), longer (%d), mean (%d)", denom, (int)SA_PID_COLUMNS,
+			    (int)SA_PID_SHORTER, (int)SA_PID_LONGER, (int)SA_PID_MEAN);
+	hid_t file;
+	hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
+	H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
+	H5Pset_alignment(fapl, 4096, 4096);
+	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
+	H5Pclose(fapl);
+	if (file < 0)
+		return fail("Failed to open HDF5 file: %s", path);
+	const int32_t scale = SA_NORM_SCALE;
+	const struct {
+		const char *name;
+		const int32_t *data;
+	} sets[2] = { { "/identity_rule", &denom }, { "/identity_scale", &scale } };
+	int rc = 0;
+	for (int d = 0; d < 2 && !rc; d++) {
+		const hsize_t extent = 1;
+		hid_t space = H5Screate_simple(1, &extent, NULL);
+		hid_t set = H5Dcreate2(file, sets[d].name, H5T_STD_I32LE, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || H5Dwrite(set, H5T_NATIVE_INT32, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0)
+			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
+		if (set >= 0)
+			H5Dclose(set);
+		H5Sclose(space);
+	}
+	H5Fclose(file);
+	return rc;
+}
+
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder
  * when `compression` > 0, the raw tiles when 0.  Same file, dataset, chunk shape and filter pipeline as sa_host_write_hdf5 --
  * the tiles go to H5Dwrite_chunk as they are, tile row after tile row. */

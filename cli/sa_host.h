@@ -106,6 +106,9 @@ int sa_host_write_quantiles(const char *path, const struct sa_host_store *s, con
  * (2 I32LE: source, rule) and /normalization_scale (1 I32LE: SA_NORM_SCALE), added to the finished file at `path`, whose other
  * datasets stay as they are.  A source or rule outside its enum gives an error before anything is opened. */
 int sa_host_write_normalization(const char *path, const struct sa_host_store *s, const int32_t *denominators, int32_t source, int32_t rule);
+/* --identity: /identity_rule (1 I32LE: the denominator, SA_PID_* of include/seqalign_hip.h) and /identity_scale (1 I32LE:
+ * SA_NORM_SCALE), added to the finished file at `path`, whose other datasets stay as they are.  0 on success. */
+int sa_host_write_identity(const char *path, int32_t denom);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,9 @@
  *             --normalize RULE   (everything selected from the scores -- neighbours, score graph, tree, clusters, quantiles -- from
  *             scores divided on the device by the self-scores or the lengths, in parts per million; /similarity_matrix stays raw:
  *             /normalization_denominators, /normalization_rule, /normalization_scale)
+ *             --identity DENOM   (the same selections from PERCENT IDENTITY in parts per million: identities of the canonical
+ *             alignment of every pair, carried through one sweep on the device, over columns | shorter | longer | mean;
+ *             /similarity_matrix stays raw: /identity_rule, /identity_scale)
  * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> score graph -> linkage -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
@@ -119,6 +122,10 @@ struct options {
 	bool normalize;
 	int32_t norm_source, norm_rule;
 	const char *norm_name;
+	/* --identity DENOM: what is selected from the scores is selected from percent identity (include/seqalign_hip.h: SA_PID_*) */
+	bool identity;
+	int32_t pid_denom;
+	const char *pid_name;
 };
 
 static void usage(const char *argv0)
@@ -186,6 +193,17 @@ static void usage(const char *argv0)
 	       "                           /similarity_matrix, when written, STAYS RAW, as does the score of --alignments.\n"
 	       "                           Writes /normalization_denominators (N), /normalization_rule (source 0 = self-score,\n"
 	       "                           1 = length; rule 0 = min, 1 = max, 2 = mean) and /normalization_scale (1000000)\n"
+	       "      --identity DENOM     Select from PERCENT IDENTITY: DENOM = columns | shorter | longer | mean.  Every pair gets\n"
+	       "                           the identities of its canonical alignment (the M columns with equal residues of the one\n"
+	       "                           alignment --alignments would report), from one sweep on the device with no traceback;\n"
+	       "                           its value is floor(1000000 identities / D), D the alignment's columns, the shorter or\n"
+	       "                           the longer of the two lengths, or their mean (parts per million; an empty alignment\n"
+	       "                           over its columns gives the lowest value).  Applies to -k, --min-score, --min-quantile,\n"
+	       "                           --linkage, --clusters, --clusters-quantile, --quantiles and the --*-only modes, and\n"
+	       "                           needs one of them; T of --min-score and --clusters is then in parts per million\n"
+	       "                           (900000: 90 %% identity).  /similarity_matrix, when written, STAYS RAW.  Not together\n"
+	       "                           with --normalize.  Writes /identity_rule (0 = columns, 1 = shorter, 2 = longer,\n"
+	       "                           3 = mean) and /identity_scale (1000000)\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -249,7 +267,8 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "neighbors", 'k', true }, { "neighbors-only", 3, false }, { "alignments", 4, false },
 		     { "min-score", 5, true }, { "edges-only", 6, false }, { "linkage", 7, false }, { "clusters", 8, true },
 		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
-		     { "quantiles", 12, true }, { "normalize", 13, true }, { NULL, 0, false } };
+		     { "quantiles", 12, true }, { "normalize", 13, true }, { "identity", 14, true },
+		     { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -425,6 +444,24 @@ static int parse_args(int argc, char **argv, struct options *o)
 				}
 				break;
 			}
+			case 14: {
+				static const struct {
+					const char *name;
+					int32_t denom;
+				} DENOMS[] = { { "columns", SA_PID_COLUMNS }, { "shorter", SA_PID_SHORTER }, { "longer", SA_PID_LONGER }, { "mean", SA_PID_MEAN } };
+				o->identity = false;
+				for (size_t t = 0; t < sizeof(DENOMS) / sizeof(DENOMS[0]); t++)
+					if (!strcmp(val, DENOMS[t].name)) {
+						o->identity = true;
+						o->pid_denom = DENOMS[t].denom;
+						o->pid_name = DENOMS[t].name;
+					}
+				if (!o->identity) {
+					err("Identity denominator must be one of columns, shorter, longer, mean: %s", val);
+					return 1;
+				}
+				break;
+			}
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -467,6 +504,43 @@ static int next_tiles(void *user, uint32_t *rows, uint32_t *cols, const uint8_t 
 		progress_line((double)(b + 1) * (double)(b + 1) / ((double)f->nc * (double)f->nc), NULL);
 	}
 	return n;
+}
+
+/* the one-call selections, whichever quantity they select from: pid != NULL percent identity under *pid (the *_pid calls),
+ * otherwise the *_norm calls, which with norm == NULL are their namesakes */
+static bool sel_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm,
+			  const int32_t *pid)
+{
+	return pid ? sa_hip_neighbors_pid(in, sc, k, index, score, *pid) : sa_hip_neighbors_norm(in, sc, k, index, score, norm);
+}
+
+static sa_edges *sel_edges(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm, const int32_t *pid)
+{
+	return pid ? sa_hip_edges_pid(in, sc, min_score, *pid) : sa_hip_edges_norm(in, sc, min_score, norm);
+}
+
+static sa_linkage *sel_linkage(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm, const int32_t *pid)
+{
+	return pid ? sa_hip_linkage_pid(in, sc, *pid) : sa_hip_linkage_norm(in, sc, norm);
+}
+
+static bool sel_select(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below,
+		       const struct sa_norm *norm, const int32_t *pid)
+{
+	return pid ? sa_hip_select_pid(in, sc, ranks, m, value, below, *pid) : sa_hip_select_norm(in, sc, ranks, m, value, below, norm);
+}
+
+static sa_edges *sel_edges_at_rank(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below,
+				   const struct sa_norm *norm, const int32_t *pid)
+{
+	return pid ? sa_hip_edges_at_rank_pid(in, sc, rank, min_score, below, *pid) : sa_hip_edges_at_rank_norm(in, sc, rank, min_score, below, norm);
+}
+
+static sa_linkage *sel_linkage_with_ranks(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value,
+					  int64_t *below, const struct sa_norm *norm, const int32_t *pid)
+{
+	return pid ? sa_hip_linkage_with_ranks_pid(in, sc, ranks, m, value, below, *pid)
+		   : sa_hip_linkage_with_ranks_norm(in, sc, ranks, m, value, below, norm);
 }
 
 int main(int argc, char **argv)
@@ -523,6 +597,11 @@ int main(int argc, char **argv)
 		ok = (err("Options --linkage-only and --min-score conflict: the score graph needs a pass of its own (use --linkage without --linkage-only)"), false);
 	if (ok && o.normalize && !o.neighbors && !o.has_min_score && !o.linkage && !o.nquant)
 		ok = (err("Option --normalize requires something selected from the scores: -k, --min-score, --min-quantile, --linkage, --clusters, "
+			  "--clusters-quantile or --quantiles (the similarity matrix itself stays raw)"), false);
+	if (ok && o.identity && o.normalize)
+		ok = (err("Options --identity and --normalize conflict: one quantity to select from"), false);
+	if (ok && o.identity && !o.neighbors && !o.has_min_score && !o.linkage && !o.nquant)
+		ok = (err("Option --identity requires something selected from the scores: -k, --min-score, --min-quantile, --linkage, --clusters, "
 			  "--clusters-quantile or --quantiles (the similarity matrix itself stays raw)"), false);
 	if (ok && sa_matrix_load(o.matrix, sc.lut, sc.sub))
 		ok = (err("Invalid substitution matrix name"), false);
@@ -601,6 +680,9 @@ int main(int argc, char **argv)
 	if (o.normalize)
 		info("Normalization: %s, in parts per million (the similarity matrix stays raw)", o.norm_name);
 
+	if (o.identity)
+		info("Percent identity over %s, in parts per million (the similarity matrix stays raw)", o.pid_name);
+
 	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t_edges = 0, t_linkage = 0, t0;
 	stamp("options parsed");
 	struct sa_host_store store;
@@ -668,6 +750,9 @@ int main(int argc, char **argv)
 		}
 		norm = &norm_spec;
 	}
+	/* --identity: the same, through sa_zjob_identity and the *_pid calls */
+	const int32_t *pid = o.identity ? &o.pid_denom : NULL;
+	double t_pid = 0;
 	if (o.neighbors) {
 		nb_index = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
 		nb_score = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
@@ -789,6 +874,16 @@ int main(int argc, char **argv)
 				verb("Normalization: %s", sa_last_error());
 			}
 		}
+		/* --identity: likewise; the device's matrix is overwritten with percent identity by one more sweep */
+		if (pid) {
+			if (sa_zjob_identity(job, *pid) == 0) {
+				t_pid = sa_hip_last_identity_seconds();
+				verb("Percent identity in place on the device (the tiles written are raw)");
+			} else {
+				job_answers = false;
+				verb("Identity: %s", sa_last_error());
+			}
+		}
 		/* the finished matrix is still on the device: the neighbours come from it, nothing is aligned twice */
 		if (o.neighbors && job_answers) {
 			if (sa_zjob_neighbors(job, o.neighbors, nb_index, nb_score) == 0) {
@@ -835,7 +930,7 @@ int main(int argc, char **argv)
 		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the tree there, copy back 12 (N - 1) bytes */
 		info("Similarity Matrix stays on the device: the single-linkage tree is built there");
 		t0 = now();
-		tree = o.nquant ? sa_hip_linkage_with_ranks_norm(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm) : sa_hip_linkage_norm(store.in, &sc, norm);
+		tree = o.nquant ? sel_linkage_with_ranks(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm, pid) : sel_linkage(store.in, &sc, norm, pid);
 		if (!tree) {
 			err("%s", sa_last_error());
 			return 1;
@@ -863,10 +958,10 @@ int main(int argc, char **argv)
 			info("Similarity Matrix stays on the device: the pairs that score at least %d are selected there", o.min_score);
 		t0 = now();
 		if (o.min_q >= 0 && o.nquant == 1) { /* one alignment: the cut and the graph from the same device matrix */
-			edges = sa_hip_edges_at_rank_norm(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0], norm);
+			edges = sel_edges_at_rank(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0], norm, pid);
 		} else {
 			if (o.nquant) { /* further fractions: one select call for all of them, in a pass of its own */
-				if (!sa_hip_select_norm(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm)) {
+				if (!sel_select(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm, pid)) {
 					err("%s", sa_last_error());
 					return 1;
 				}
@@ -874,7 +969,7 @@ int main(int argc, char **argv)
 			}
 			if (o.min_q >= 0)
 				o.min_score = q_values[o.min_q];
-			edges = sa_hip_edges_norm(store.in, &sc, o.min_score, norm);
+			edges = sel_edges(store.in, &sc, o.min_score, norm, pid);
 		}
 		if (edges && o.nquant) {
 			q_done = true;
@@ -900,7 +995,7 @@ int main(int argc, char **argv)
 		/* no host matrix, no tiles, no matrix transfer: align into device memory, select there, copy back 2 N K ints */
 		info("Similarity Matrix stays on the device: %d neighbors per sequence are selected there", o.neighbors);
 		t0 = now();
-		if (!sa_hip_neighbors_norm(store.in, &sc, o.neighbors, nb_index, nb_score, norm)) {
+		if (!sel_neighbors(store.in, &sc, o.neighbors, nb_index, nb_score, norm, pid)) {
 			err("%s", sa_last_error());
 			return 1;
 		}
@@ -948,7 +1043,7 @@ int main(int argc, char **argv)
 		/* the other paths (N <= 256, SA_HOST_* switches, -W, several devices, a walk dealt over several jobs) no longer hold
 		 * the matrix on one device: a second pass aligns into device memory again and selects there */
 		verb("Neighbors: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		if (!sa_hip_neighbors_norm(store.in, &sc, o.neighbors, nb_index, nb_score, norm)) {
+		if (!sel_neighbors(store.in, &sc, o.neighbors, nb_index, nb_score, norm, pid)) {
 			err("%s", sa_last_error());
 			return 1;
 		}
@@ -1005,14 +1100,14 @@ int main(int argc, char **argv)
 		verb("Score quantiles: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
 		bool got;
 		if (o.min_q >= 0 && o.nquant == 1 && !edges) {
-			edges = sa_hip_edges_at_rank_norm(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0], norm);
+			edges = sel_edges_at_rank(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0], norm, pid);
 			got = edges != NULL;
 			if (got) {
 				eg_second_pass = true;
 				t_edges = sa_hip_last_edges_seconds();
 			}
 		} else if (o.linkage && !tree) {
-			tree = sa_hip_linkage_with_ranks_norm(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm);
+			tree = sel_linkage_with_ranks(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm, pid);
 			got = tree != NULL;
 			if (got) {
 				lk_second_pass = true;
@@ -1020,7 +1115,7 @@ int main(int argc, char **argv)
 				lk_rounds = sa_hip_last_linkage_rounds();
 			}
 		} else {
-			got = sa_hip_select_norm(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm);
+			got = sel_select(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm, pid);
 		}
 		if (!got) {
 			err("%s", sa_last_error());
@@ -1045,7 +1140,7 @@ int main(int argc, char **argv)
 	if (o.has_min_score && !edges) {
 		/* as for the neighbours: the matrix of the first pass is not on one device any more */
 		verb("Score graph: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		edges = sa_hip_edges_norm(store.in, &sc, o.min_score, norm);
+		edges = sel_edges(store.in, &sc, o.min_score, norm, pid);
 		if (!edges) {
 			err("%s", sa_last_error());
 			return 1;
@@ -1073,7 +1168,7 @@ int main(int argc, char **argv)
 	if (o.linkage && !tree) {
 		/* as for the neighbours: the matrix of the first pass is not on one device any more */
 		verb("Single-linkage tree: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		tree = sa_hip_linkage_norm(store.in, &sc, norm);
+		tree = sel_linkage(store.in, &sc, norm, pid);
 		if (!tree) {
 			err("%s", sa_last_error());
 			return 1;
@@ -1133,6 +1228,17 @@ int main(int argc, char **argv)
 		t_out += now() - t0;
 		stamp("normalization written");
 	}
+	if (pid && !o.no_write) {
+		t0 = now();
+		if (sa_host_write_identity(o.output, *pid)) {
+			err("%s", sa_host_error());
+			return 1;
+		}
+		t_out += now() - t0;
+		stamp("identity rule written");
+	}
+	if (pid && t_pid == 0)
+		t_pid = sa_hip_last_identity_seconds(); /* (the *_pid calls: the last of them) */
 	if (norm && t_norm == 0)
 		t_norm = sa_hip_last_normalize_seconds(); /* (the *_norm calls: the last of them) */
 	if (o.benchmark) { /* -B: src/util/benchmark.c:50-64 */
@@ -1168,6 +1274,8 @@ int main(int argc, char **argv)
 			printf("  (clusters at score >= %d: %d)\n", o.clusters_at, cluster_count);
 		if (norm)
 			printf("  (Normalisation on the device, %s: denominators + sweep over %lld pairs, %.6f sec)\n", o.norm_name, npairs, t_norm);
+		if (pid)
+			printf("  (Percent identity on the device, over %s: one sweep over %lld pairs, %.6f sec)\n", o.pid_name, npairs, t_pid);
 		printf("Alignments per second: %.2f\n", t_align > 0 ? (double)pairs / t_align : 0.0);
 	}
 	if (pinned)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -513,6 +513,64 @@ sa_linkage *sa_hip_linkage_with_ranks_norm(struct sa_input in, const struct sa_s
 					   int32_t *value, int64_t *below, const struct sa_norm *norm);
 /* device time (seconds) of denominators + sweep in the last successful *_norm / sa_zjob_normalize call */
 double sa_hip_last_normalize_seconds(void);
+
+/* ---- percent identity of every pair: identities and columns carried through the sweep ----------------------------------------
+ * No reference counterpart.  The number biologists cut at is percent identity ("cluster at 90 % identity"); the -f filter knows
+ * only the positional identity of unaligned prefixes, and sa_ctx_alignments costs a decision byte per DP cell plus a walk per
+ * chosen pair.  Here every pair of the store gets the `identities` and `columns` of its canonical alignment -- the ONE alignment
+ * the tie rule of "alignments for chosen pairs" above fixes, the same two numbers struct sa_aln reports -- from one forward
+ * sweep: the canonical path is a per-cell function of the DP tables, so both numbers travel with the scores (csrc/sa_identity.hip,
+ * csrc/sa_identity_core.h).  No decision scratch, no walk.
+ * Everything is in the canonical orientation: pair i < j, i the row sequence; the score is the similarity-matrix entry, always,
+ * and nothing depends on the order in which a caller names the two sequences.  An empty SW alignment (best == 0) has
+ * identities = columns = 0.
+ * Percent identity in parts per million (pid), exact 64-bit arithmetic, from identities, columns and the two lengths:
+ *   SA_PID_COLUMNS   D = columns,             num = identities SA_NORM_SCALE
+ *   SA_PID_SHORTER   D = min(len_i, len_j),   num = identities SA_NORM_SCALE
+ *   SA_PID_LONGER    D = max(len_i, len_j),   num = identities SA_NORM_SCALE
+ *   SA_PID_MEAN      D = len_i + len_j,       num = 2 identities SA_NORM_SCALE
+ *   D <= 0: INT32_MIN, as sa_norm_value (only an empty SW alignment under SA_PID_COLUMNS gets there); otherwise floor(num / D),
+ *   in [0, 1000000].
+ * A triangle of pid is a packed triangle like any other: the neighbours, the graph, the tree and the order statistics above read
+ * it unchanged, and their thresholds are then in parts per million.  The same store and scoring give the same bytes run after run. */
+enum { SA_PID_COLUMNS = 0, SA_PID_SHORTER = 1, SA_PID_LONGER = 2, SA_PID_MEAN = 3 };
+struct sa_identity_out {
+	int32_t *score, *identities, *columns, *pid; /* any subset non-NULL; element [p - start] belongs to pair p */
+	int32_t denom;                               /* SA_PID_*; read iff pid != NULL */
+};
+/* host only: the value rule above for one pair.  INT32_MIN + sa_last_error for a denom outside the enum. */
+int32_t sa_pid_value(int32_t identities, int32_t columns, int32_t len_i, int32_t len_j, int32_t denom);
+/* device-resident, asynchronous on `stream`: the packed pair range [start, start + count) into the DEVICE arrays of *d_out (the
+ * struct itself is host memory).  Any two outputs may not overlap; an output may be a buffer that held something else -- the
+ * kernel reads none of them, so pid can replace a triangle of scores in place.  One wavefront per pair over the context's
+ * strip-boundary scratch plus a buffer of boundary payloads the context allocates at its first identity call (twice the bytes
+ * of that scratch): like sa_ctx_alignments, the call does not run beside sa_ctx_align_range or another identity call of the SAME
+ * context on another stream; in order on one stream is fine.  Non-zero + sa_last_error, nothing launched, for a null argument,
+ * all four outputs NULL, a denom outside the enum (when pid is asked for), a range outside [0, pairs). */
+int sa_ctx_identity_range(sa_ctx *ctx, int64_t start, int64_t count, const struct sa_identity_out *d_out, void *stream);
+/* host in / host out, one device (the first): identities, columns, pid are HOST packed triangles (N (N - 1) / 2 int32 each), any
+ * subset non-NULL; denom is read iff pid != NULL.  Runs in column-aligned ranges sized from the free device memory
+ * (SA_HIP_IDENTITY_BATCH_BYTES caps a range), so any N whose triangles fit the host works.  The arguments are checked before a
+ * device is looked for. */
+bool sa_hip_identity(struct sa_input in, const struct sa_scoring *sc, int32_t denom, int32_t *identities, int32_t *columns, int32_t *pid);
+/* on a sa_hip_tiles_begin job whose device holds the whole finished matrix: overwrites the job's matrix with pid IN PLACE, once;
+ * sa_zjob_neighbors / _edges / _linkage / _select then answer over percent identity.  The tiles already handed out stay raw.
+ * Refused when sa_zjob_normalize is, with the same wording; also after sa_zjob_normalize, and sa_zjob_normalize after it. */
+int sa_zjob_identity(sa_zjob *job, int32_t denom);
+/* the one-call selections over percent identity: the arguments of the namesake + denom.  The identity sweep fills the device
+ * triangle with pid; no score alignment runs.  Null arguments, a bad denom, a bad k / rank are refused before a device is
+ * looked for. */
+bool sa_hip_neighbors_pid(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, int32_t denom);
+sa_edges *sa_hip_edges_pid(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, int32_t denom);
+sa_linkage *sa_hip_linkage_pid(struct sa_input in, const struct sa_scoring *sc, int32_t denom);
+bool sa_hip_select_pid(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below,
+		       int32_t denom);
+sa_edges *sa_hip_edges_at_rank_pid(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below,
+				   int32_t denom);
+sa_linkage *sa_hip_linkage_with_ranks_pid(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
+					  int32_t *value, int64_t *below, int32_t denom);
+/* device time (seconds) of the identity sweep in the last successful sa_hip_identity / *_pid / sa_zjob_identity call */
+double sa_hip_last_identity_seconds(void);
 
 /* ---- pair-space planning (host only, no device needed) -------------------
  * DP cells (sum of len_i*len_j) of the packed pair range [start, start+count),

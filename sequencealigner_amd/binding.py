@@ -66,11 +66,17 @@ ABI_SYMBOLS = (
     "sa_linkage_destroy", "sa_hip_last_linkage_seconds", "sa_hip_last_linkage_rounds", "sa_linkage_labels", "sa_linkage_merges",
     "sa_select_scratch_bytes", "sa_score_rank", "sa_ctx_select", "sa_hip_select", "sa_zjob_select", "sa_hip_edges_at_rank",
     "sa_hip_linkage_with_ranks", "sa_hip_last_select_seconds",
+    "sa_pid_value", "sa_ctx_identity_range", "sa_hip_identity", "sa_zjob_identity", "sa_hip_neighbors_pid", "sa_hip_edges_pid",
+    "sa_hip_linkage_pid", "sa_hip_select_pid", "sa_hip_edges_at_rank_pid", "sa_hip_linkage_with_ranks_pid", "sa_hip_last_identity_seconds",
 )
 
 
 class _Norm(C.Structure):  # struct sa_norm
     _fields_ = [("source", C.c_int32), ("rule", C.c_int32), ("denominators", C.c_void_p)]
+
+
+class _IdentityOut(C.Structure):  # struct sa_identity_out
+    _fields_ = [("score", C.c_void_p), ("identities", C.c_void_p), ("columns", C.c_void_p), ("pid", C.c_void_p), ("denom", C.c_int32)]
 
 
 def library_path() -> pathlib.Path:
@@ -289,6 +295,27 @@ def load_library() -> C.CDLL:
     lib.sa_hip_linkage_with_ranks_norm.argtypes = lib.sa_hip_linkage_with_ranks.argtypes + [C.POINTER(_Norm)]
     lib.sa_hip_linkage_with_ranks_norm.restype = C.c_void_p
     lib.sa_hip_last_normalize_seconds.restype = C.c_double
+    lib.sa_pid_value.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.sa_pid_value.restype = C.c_int32
+    lib.sa_ctx_identity_range.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(_IdentityOut), C.c_void_p]
+    lib.sa_ctx_identity_range.restype = C.c_int
+    lib.sa_hip_identity.argtypes = [_Input, C.POINTER(_Scoring), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_hip_identity.restype = C.c_bool
+    lib.sa_zjob_identity.argtypes = [C.c_void_p, C.c_int32]
+    lib.sa_zjob_identity.restype = C.c_int
+    lib.sa_hip_neighbors_pid.argtypes = lib.sa_hip_neighbors.argtypes + [C.c_int32]
+    lib.sa_hip_neighbors_pid.restype = C.c_bool
+    lib.sa_hip_edges_pid.argtypes = lib.sa_hip_edges.argtypes + [C.c_int32]
+    lib.sa_hip_edges_pid.restype = C.c_void_p
+    lib.sa_hip_linkage_pid.argtypes = lib.sa_hip_linkage.argtypes + [C.c_int32]
+    lib.sa_hip_linkage_pid.restype = C.c_void_p
+    lib.sa_hip_select_pid.argtypes = lib.sa_hip_select.argtypes + [C.c_int32]
+    lib.sa_hip_select_pid.restype = C.c_bool
+    lib.sa_hip_edges_at_rank_pid.argtypes = lib.sa_hip_edges_at_rank.argtypes + [C.c_int32]
+    lib.sa_hip_edges_at_rank_pid.restype = C.c_void_p
+    lib.sa_hip_linkage_with_ranks_pid.argtypes = lib.sa_hip_linkage_with_ranks.argtypes + [C.c_int32]
+    lib.sa_hip_linkage_with_ranks_pid.restype = C.c_void_p
+    lib.sa_hip_last_identity_seconds.restype = C.c_double
     _lib = lib
     return lib
 
@@ -548,7 +575,50 @@ def last_normalize_seconds() -> float:
     return float(load_library().sa_hip_last_normalize_seconds())
 
 
-def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int, norm: Optional[Norm] = None):
+PID_COLUMNS, PID_SHORTER, PID_LONGER, PID_MEAN = 0, 1, 2, 3  # SA_PID_*: what the identities are divided by
+
+
+def _denom(denom) -> int:
+    d = int(denom)
+    if not -2**31 <= d < 2**31:
+        raise AlignError(f"denom = {d} is not an int32")
+    return d
+
+
+def pid_value(identities: int, columns: int, len_i: int, len_j: int, denom: int) -> int:
+    """sa_pid_value (host only): percent identity in parts per million -- floor(num / D) under `denom` (PID_COLUMNS, PID_SHORTER,
+    PID_LONGER, PID_MEAN); INT32_MIN for D <= 0"""
+    args = [int(identities), int(columns), int(len_i), int(len_j), int(denom)]
+    for v in args:
+        if not -2**31 <= v < 2**31:
+            raise AlignError(f"{v} is not an int32")
+    got = int(load_library().sa_pid_value(*args))
+    if args[4] not in (PID_COLUMNS, PID_SHORTER, PID_LONGER, PID_MEAN):  # (refused by the library: the message is its own)
+        raise AlignError(_err())
+    return got
+
+
+def hip_identity(store: SequenceStore, scoring: Scoring, denom: Optional[int] = None, identities: bool = True, columns: bool = True):
+    """sa_hip_identity: identities and columns of the canonical alignment of every pair, and with a `denom` their percent identity
+    in parts per million, as packed triangles (N (N - 1) / 2 int32) -- (identities, columns, pid), None for what was not asked
+    for.  One forward sweep on the device, no traceback."""
+    pairs = pair_count(store.num)
+    ident = np.empty(max(pairs, 1), np.int32) if identities else None
+    cols = np.empty(max(pairs, 1), np.int32) if columns else None
+    pid = np.empty(max(pairs, 1), np.int32) if denom is not None else None
+    sc = scoring._as_c()
+    ptr = [None if a is None else a.ctypes.data for a in (ident, cols, pid)]
+    if not load_library().sa_hip_identity(store._as_c(), C.byref(sc), _denom(0 if denom is None else denom), *ptr):
+        raise AlignError(_err())
+    return tuple(None if a is None else a[:pairs] for a in (ident, cols, pid))
+
+
+def last_identity_seconds() -> float:
+    """device time of the identity sweep in the last hip_identity / pid= selection / DeflateJob.identity call"""
+    return float(load_library().sa_hip_last_identity_seconds())
+
+
+def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_neighbors: the k best partners of every sequence, selected on the device -- (index, score), two (N, k) int32
     arrays; row r lists the c != r by score descending, then index ascending.  The matrix never leaves the device.
     1 <= k <= min(N - 1, NEIGHBORS_MAX)."""
@@ -558,6 +628,12 @@ def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int, norm: Optional
     rows = max(n, 1) * max(min(k, NEIGHBORS_MAX), 1)
     index, score = np.empty(rows, np.int32), np.empty(rows, np.int32)
     sc = scoring._as_c()
+    if pid is not None:  # percent identity under the denominator `pid`, in parts per million: (index, score)
+        if norm is not None:
+            raise AlignError("norm and pid exclude each other")
+        if not load_library().sa_hip_neighbors_pid(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data, _denom(pid)):
+            raise AlignError(_err())
+        return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k)
     if norm is not None:  # normalised scores: (index, score, denominators)
         cn, den = norm._as_c(n)
         if not load_library().sa_hip_neighbors_norm(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data, C.byref(cn)):
@@ -598,12 +674,14 @@ def _take_edges(lib, handle) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     return offsets, index, score
 
 
-def hip_edges(store: SequenceStore, scoring: Scoring, min_score: int, norm: Optional[Norm] = None):
+def hip_edges(store: SequenceStore, scoring: Scoring, min_score: int, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_edges: every pair that scores at least min_score, as the symmetric adjacency in CSR form, built on the device --
     (offsets int64[N + 1], index int32[E], score int32[E]); row r's columns are index[offsets[r]:offsets[r + 1]], ascending.
     The matrix never leaves the device.  Any int32 threshold is valid."""
     lib = load_library()
     sc = scoring._as_c()
+    if pid is not None:  # min_score in parts per million of identity
+        return _take_edges(lib, lib.sa_hip_edges_pid(store._as_c(), C.byref(sc), _min_score(min_score), _denom(pid)))
     if norm is not None:  # min_score in parts per million: (offsets, index, score, denominators)
         cn, den = norm._as_c(store.num)
         return _take_edges(lib, lib.sa_hip_edges_norm(store._as_c(), C.byref(sc), _min_score(min_score), C.byref(cn))) + (den[:store.num],)
@@ -631,12 +709,14 @@ def _take_linkage(lib, handle) -> tuple[np.ndarray, np.ndarray]:
     return pairs.reshape(m, 2), score
 
 
-def hip_linkage(store: SequenceStore, scoring: Scoring, norm: Optional[Norm] = None):
+def hip_linkage(store: SequenceStore, scoring: Scoring, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_linkage: the single-linkage tree (the maximum spanning tree of the score matrix), built on the device --
     (pairs int32 (N - 1, 2) with lo < hi, score int32 (N - 1,)), sorted by score descending, then packed index ascending: the
     order in which single linkage joins clusters.  The matrix never leaves the device."""
     lib = load_library()
     sc = scoring._as_c()
+    if pid is not None:  # the tree of percent identity
+        return _take_linkage(lib, lib.sa_hip_linkage_pid(store._as_c(), C.byref(sc), _denom(pid)))
     if norm is not None:  # the tree of the normalised scores: (pairs, score, denominators)
         cn, den = norm._as_c(store.num)
         return _take_linkage(lib, lib.sa_hip_linkage_norm(store._as_c(), C.byref(sc), C.byref(cn))) + (den[:store.num],)
@@ -699,7 +779,7 @@ def select_scratch_bytes(m: int) -> int:
     return int(load_library().sa_select_scratch_bytes(int(m)))
 
 
-def hip_select(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Norm] = None):
+def hip_select(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_select: for each rank k (up to 16, any order, duplicates allowed) into the ascending order of the N (N - 1) / 2
     pair scores, (values int32 (m,), below int64 (m,)): the k-th smallest score and the number of pairs strictly below it,
     selected on the device.  The matrix never leaves the device."""
@@ -707,6 +787,10 @@ def hip_select(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Nor
     sc = scoring._as_c()
     r = _ranks(ranks)
     value, below = _select_room(len(r))
+    if pid is not None:  # order statistics of percent identity
+        if not lib.sa_hip_select_pid(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data, _denom(pid)):
+            raise AlignError(_err())
+        return value[:len(r)].copy(), below[:len(r)].copy()
     if norm is not None:  # order statistics of the normalised scores: (values, below, denominators)
         cn, den = norm._as_c(store.num)
         if not lib.sa_hip_select_norm(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data, C.byref(cn)):
@@ -717,13 +801,17 @@ def hip_select(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Nor
     return value[:len(r)].copy(), below[:len(r)].copy()
 
 
-def hip_edges_at_rank(store: SequenceStore, scoring: Scoring, rank: int, norm: Optional[Norm] = None):
+def hip_edges_at_rank(store: SequenceStore, scoring: Scoring, rank: int, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_edges_at_rank: one alignment, the score T at `rank` and the score graph at T from the same device matrix --
     (offsets, index, score) as hip_edges returns them, then min_score = T and below = the pairs under T; E = 2 (P - below)"""
     lib = load_library()
     sc = scoring._as_c()
     cut, below = C.c_int32(0), C.c_int64(0)
     (rank,) = _ranks([rank])
+    if pid is not None:  # all over percent identity
+        offsets, index, score = _take_edges(lib, lib.sa_hip_edges_at_rank_pid(store._as_c(), C.byref(sc), int(rank), C.byref(cut),
+                                                                              C.byref(below), _denom(pid)))
+        return offsets, index, score, int(cut.value), int(below.value)
     if norm is not None:  # (offsets, index, score, min_score, below, denominators), all over the normalised scores
         cn, den = norm._as_c(store.num)
         offsets, index, score = _take_edges(lib, lib.sa_hip_edges_at_rank_norm(store._as_c(), C.byref(sc), int(rank), C.byref(cut),
@@ -733,13 +821,17 @@ def hip_edges_at_rank(store: SequenceStore, scoring: Scoring, rank: int, norm: O
     return offsets, index, score, int(cut.value), int(below.value)
 
 
-def hip_linkage_with_ranks(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Norm] = None):
+def hip_linkage_with_ranks(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_linkage_with_ranks: one alignment, then hip_select's (values, below) for `ranks` and hip_linkage's (pairs, score)
     from the same device matrix -- (pairs, score, values, below)"""
     lib = load_library()
     sc = scoring._as_c()
     r = _ranks(ranks)
     value, below = _select_room(len(r))
+    if pid is not None:  # all over percent identity
+        pairs, score = _take_linkage(lib, lib.sa_hip_linkage_with_ranks_pid(store._as_c(), C.byref(sc), r.ctypes.data, len(r),
+                                                                             value.ctypes.data, below.ctypes.data, _denom(pid)))
+        return pairs, score, value[:len(r)].copy(), below[:len(r)].copy()
     if norm is not None:  # (pairs, score, values, below, denominators), all over the normalised scores
         cn, den = norm._as_c(store.num)
         pairs, score = _take_linkage(lib, lib.sa_hip_linkage_with_ranks_norm(store._as_c(), C.byref(sc), r.ctypes.data, len(r),
@@ -1069,6 +1161,15 @@ class Context:
                                       C.c_void_p(d_out_ptr or None), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def identity_range(self, start: int, count: int, score: int = 0, identities: int = 0, columns: int = 0, pid: int = 0,
+                       denom: int = 0, stream: int = 0) -> None:
+        """sa_ctx_identity_range: score / identities / columns / pid of the packed pair range [start, start + count) into the
+        device arrays given (count int32 each, 0: not asked for; `denom` is read iff pid), asynchronously on `stream`; not beside
+        align_range or another identity_range of this context on another stream"""
+        out = _IdentityOut(score or None, identities or None, columns or None, pid or None, _denom(denom))
+        if self._lib.sa_ctx_identity_range(self._h, int(start), int(count), C.byref(out), C.c_void_p(stream)):
+            raise AlignError(_err())
+
     def alignments(self, pairs) -> Alignments:
         """sa_ctx_alignments: the alignments of the listed pairs of this context's store (see hip_alignments)"""
         arr = _pairs_array(pairs)
@@ -1175,6 +1276,13 @@ class DeflateJob:
         if self._lib.sa_zjob_normalize(self._h, C.byref(cn)):
             raise AlignError(_err())
         return den[:self.num]
+
+    def identity(self, denom: int) -> None:
+        """sa_zjob_identity: overwrites the finished matrix of a begin() job with percent identity under `denom`, in place, once,
+        after next() has returned []; neighbors / edges / linkage / select then answer over parts per million of identity (the
+        tiles handed out stay raw)"""
+        if self._lib.sa_zjob_identity(self._h, _denom(denom)):
+            raise AlignError(_err())
 
     def stats(self) -> dict:
         e, c, r, o = C.c_double(), C.c_double(), C.c_uint64(), C.c_uint64()

@@ -445,10 +445,17 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 	/* the alignment is in order on `stream` when this returns true; `who` names the entry point in messages */
 	/* norm != nullptr: denominators + sweep follow the alignment on the stream, in place (sa_normalize.hip), and the stream is
 	 * synchronised once here; what the caller selects next reads normalised scores */
-	bool begin(const char *who, struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm = nullptr)
+	/* denom != nullptr, the second way to fill d_packed: the identity sweep (sa_identity.hip) writes pid under *denom for every
+	 * pair, no score alignment runs, and the stream is synchronised once here; what the caller selects next reads parts per
+	 * million of identity */
+	bool pid_run = false;
+	bool begin(const char *who, struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm = nullptr, const int32_t *denom = nullptr)
 	{
 		if (norm && !sa_norm_check(who, norm)) /* (before the alignment is launched) */
 			return false;
+		if (denom && !sa_identity_denom_check(who, *denom)) /* (before a device is looked for) */
+			return false;
+		pid_run = denom != nullptr;
 		if (sa_hip_device_count() <= 0) {
 			sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
 			return false;
@@ -468,6 +475,8 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 		SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), return false);
 		SA_HIP_CHECK(hipEventCreate(&e0), return false);
 		SA_HIP_CHECK(hipEventCreate(&e1), return false);
+		if (denom)
+			return sa_identity_in_place(who, ctx, d_packed, *denom, stream);
 		SA_HIP_CHECK(hipEventRecord(e0, stream), return false);
 		if (sa_ctx_align_range(ctx, 0, pairs, d_packed, stream) != 0)
 			return false;
@@ -479,6 +488,8 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 	/* after the stream has been synchronised: the alignment's device time goes to sa_hip_last_align_seconds */
 	bool finish()
 	{
+		if (pid_run) /* (no alignment ran: sa_hip_last_identity_seconds has the sweep) */
+			return true;
 		float ms = 0.f;
 		SA_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1), return false);
 		g_last_align_seconds.store((double)ms * 1e-3);
@@ -486,14 +497,16 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 	}
 };
 
-static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm)
+static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm, const int32_t *denom = nullptr)
 {
-	const char *who = norm ? "sa_hip_neighbors_norm" : "sa_hip_neighbors";
+	const char *who = denom ? "sa_hip_neighbors_pid" : norm ? "sa_hip_neighbors_norm" : "sa_hip_neighbors";
 	if (!sc || !index || !score) {
 		sa_set_error("%s: null argument", who);
 		return false;
 	}
 	if (norm && !sa_norm_check(who, norm))
+		return false;
+	if (denom && (!sa_identity_denom_check(who, *denom) || !sa_neighbors_check(who, in.num, k)))
 		return false;
 	if (sa_hip_device_count() <= 0) {
 		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
@@ -502,7 +515,7 @@ static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int3
 	if (!sa_neighbors_check(who, in.num, k))
 		return false;
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm))
+	if (!run.begin(who, in, sc, norm, denom))
 		return false;
 	if (!sa_neighbors_to_host(run.d_packed, in.num, k, index, score, run.stream))
 		return false;
@@ -519,15 +532,15 @@ extern "C" bool sa_hip_neighbors_norm(struct sa_input in, const struct sa_scorin
 	return sa_guard("sa_hip_neighbors_norm", false, [&] { return neighbors_impl(in, sc, k, index, score, norm); });
 }
 
-static sa_edges *edges_impl(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm)
+static sa_edges *edges_impl(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm, const int32_t *denom = nullptr)
 {
-	const char *who = norm ? "sa_hip_edges_norm" : "sa_hip_edges";
+	const char *who = denom ? "sa_hip_edges_pid" : norm ? "sa_hip_edges_norm" : "sa_hip_edges";
 	if (!sc) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
 	}
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm))
+	if (!run.begin(who, in, sc, norm, denom))
 		return nullptr;
 	sa_edges *res = sa_edges_to_host(who, run.d_packed, in.num, min_score, run.stream);
 	if (res && !run.finish()) {
@@ -547,15 +560,15 @@ extern "C" sa_edges *sa_hip_edges_norm(struct sa_input in, const struct sa_scori
 	return sa_guard("sa_hip_edges_norm", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, norm); });
 }
 
-static sa_linkage *linkage_impl(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm)
+static sa_linkage *linkage_impl(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm, const int32_t *denom = nullptr)
 {
-	const char *who = norm ? "sa_hip_linkage_norm" : "sa_hip_linkage";
+	const char *who = denom ? "sa_hip_linkage_pid" : norm ? "sa_hip_linkage_norm" : "sa_hip_linkage";
 	if (!sc) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
 	}
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm))
+	if (!run.begin(who, in, sc, norm, denom))
 		return nullptr;
 	sa_linkage *res = sa_linkage_to_host(who, run.d_packed, in.num, run.stream);
 	if (res && !run.finish()) {
@@ -576,9 +589,9 @@ extern "C" sa_linkage *sa_hip_linkage_norm(struct sa_input in, const struct sa_s
 }
 
 /* ---- order statistics of the matrix, alone and as the cut of what follows them on the same device matrix -------------------- */
-static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below, const struct sa_norm *norm)
+static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below, const struct sa_norm *norm, const int32_t *denom = nullptr)
 {
-	const char *who = norm ? "sa_hip_select_norm" : "sa_hip_select";
+	const char *who = denom ? "sa_hip_select_pid" : norm ? "sa_hip_select_norm" : "sa_hip_select";
 	if (!sc || !ranks || !value || !below) {
 		sa_set_error("%s: null argument", who);
 		return false;
@@ -586,7 +599,7 @@ static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const i
 	if (!sa_select_check(who, in.num, ranks, m)) /* (before the alignment: P follows from in.num) */
 		return false;
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm))
+	if (!run.begin(who, in, sc, norm, denom))
 		return false;
 	if (!sa_select_to_host(who, run.d_packed, in.num, ranks, m, value, below, run.stream))
 		return false;
@@ -603,9 +616,9 @@ extern "C" bool sa_hip_select_norm(struct sa_input in, const struct sa_scoring *
 	return sa_guard("sa_hip_select_norm", false, [&] { return select_impl(in, sc, ranks, m, value, below, norm); });
 }
 
-static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below, const struct sa_norm *norm)
+static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below, const struct sa_norm *norm, const int32_t *denom = nullptr)
 {
-	const char *who = norm ? "sa_hip_edges_at_rank_norm" : "sa_hip_edges_at_rank";
+	const char *who = denom ? "sa_hip_edges_at_rank_pid" : norm ? "sa_hip_edges_at_rank_norm" : "sa_hip_edges_at_rank";
 	if (!sc || !min_score || !below) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
@@ -613,7 +626,7 @@ static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring 
 	if (!sa_select_check(who, in.num, &rank, 1))
 		return nullptr;
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm))
+	if (!run.begin(who, in, sc, norm, denom))
 		return nullptr;
 	int32_t cut = 0;
 	int64_t under = 0;
@@ -642,9 +655,9 @@ extern "C" sa_edges *sa_hip_edges_at_rank_norm(struct sa_input in, const struct 
 }
 
 static sa_linkage *linkage_with_ranks_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value,
-					   int64_t *below, const struct sa_norm *norm)
+					   int64_t *below, const struct sa_norm *norm, const int32_t *denom = nullptr)
 {
-	const char *who = norm ? "sa_hip_linkage_with_ranks_norm" : "sa_hip_linkage_with_ranks";
+	const char *who = denom ? "sa_hip_linkage_with_ranks_pid" : norm ? "sa_hip_linkage_with_ranks_norm" : "sa_hip_linkage_with_ranks";
 	if (!sc || !ranks || !value || !below) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
@@ -652,7 +665,7 @@ static sa_linkage *linkage_with_ranks_impl(struct sa_input in, const struct sa_s
 	if (!sa_select_check(who, in.num, ranks, m))
 		return nullptr;
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm))
+	if (!run.begin(who, in, sc, norm, denom))
 		return nullptr;
 	int32_t cut[SA_HIP_SELECT_MAX];
 	int64_t under[SA_HIP_SELECT_MAX];
@@ -683,6 +696,41 @@ extern "C" sa_linkage *sa_hip_linkage_with_ranks_norm(struct sa_input in, const 
 {
 	return sa_guard("sa_hip_linkage_with_ranks_norm", (sa_linkage *)nullptr,
 			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, norm); });
+}
+
+/* ---- the same selections over percent identity: the identity sweep fills the device triangle (DeviceRun::begin) ---------------- */
+extern "C" bool sa_hip_neighbors_pid(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, int32_t denom)
+{
+	return sa_guard("sa_hip_neighbors_pid", false, [&] { return neighbors_impl(in, sc, k, index, score, nullptr, &denom); });
+}
+
+extern "C" sa_edges *sa_hip_edges_pid(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, int32_t denom)
+{
+	return sa_guard("sa_hip_edges_pid", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, nullptr, &denom); });
+}
+
+extern "C" sa_linkage *sa_hip_linkage_pid(struct sa_input in, const struct sa_scoring *sc, int32_t denom)
+{
+	return sa_guard("sa_hip_linkage_pid", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, nullptr, &denom); });
+}
+
+extern "C" bool sa_hip_select_pid(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below,
+				  int32_t denom)
+{
+	return sa_guard("sa_hip_select_pid", false, [&] { return select_impl(in, sc, ranks, m, value, below, nullptr, &denom); });
+}
+
+extern "C" sa_edges *sa_hip_edges_at_rank_pid(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below,
+					      int32_t denom)
+{
+	return sa_guard("sa_hip_edges_at_rank_pid", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, nullptr, &denom); });
+}
+
+extern "C" sa_linkage *sa_hip_linkage_with_ranks_pid(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
+						     int32_t *value, int64_t *below, int32_t denom)
+{
+	return sa_guard("sa_hip_linkage_with_ranks_pid", (sa_linkage *)nullptr,
+			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, nullptr, &denom); });
 }
 
 extern "C" int sa_hip_last_align_path(void) { return g_last_align_path.load(); }

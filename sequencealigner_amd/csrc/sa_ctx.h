@@ -5,6 +5,7 @@
  *   sa_launch.hip  : plan cache + upload, sa_ctx_align_range, shares and placement
  *   sa_deliver.hip : sa_ctx_align_host (the launch/copy loop towards host memory)
  *   sa_gather.hip  : several devices of one process through dense shares + RCCL all-gather
+ *   sa_identity.hip: sa_ctx_identity_range, sa_hip_identity (percent identity of every pair)
  *   sa_abi.hip     : sa_hip_align, sa_hip_memory, sa_hip_filter, progress, side channels
  */
 #ifndef SA_CTX_H
@@ -41,6 +42,7 @@ struct sa_ctx {
 	int32_t *d_scratch = nullptr;
 	int64_t scratch_stride = 0;
 	int generic_blocks = 0;
+	void *d_id_scratch = nullptr; /* strip-boundary payloads of sa_k_identity (sa_identity.hip): one per int of d_scratch, allocated on first use */
 	/* Tile counters of the persistent launches: one slot of COUNTERS_PER_SLOT counters per sa_ctx_align_range call, taken
 	 * round-robin from a ring so that ranges issued back to back on DIFFERENT streams never share a counter.
 	 * INVARIANT: a slot's counters are zero whenever no launch is using them -- zeroed at context creation, and every
@@ -181,5 +183,11 @@ bool sa_rccl_available(std::string *why);
  * when not null, receives d[0 .. N); the device time goes to sa_hip_last_normalize_seconds. */
 bool sa_norm_check(const char *who, const struct sa_norm *norm);
 bool sa_normalize_in_place(const char *who, sa_ctx *ctx, int32_t *d_packed, const struct sa_norm *norm, hipStream_t s);
+
+/* sa_identity.hip: denom inside its enum, or sa_set_error; the identity sweep over the whole pair space of ctx's store with pid
+ * written to d_packed[p] -- in place of whatever the matrix held -- in order on `s`, which is synchronised (the *_pid calls,
+ * sa_zjob_identity); the device time goes to sa_hip_last_identity_seconds. */
+bool sa_identity_denom_check(const char *who, int32_t denom);
+bool sa_identity_in_place(const char *who, sa_ctx *ctx, int32_t *d_packed, int32_t denom, hipStream_t s);
 
 #endif /* SA_CTX_H */

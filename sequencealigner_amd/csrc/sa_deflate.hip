@@ -737,6 +737,7 @@ struct sa_zjob {
 	const int32_t *d_packed = nullptr, *d_full = nullptr;
 	int32_t *d_owned = nullptr; /* the packed matrix, when the job made it (sa_hip_tiles_begin) */
 	bool normalized = false;    /* sa_zjob_normalize has rewritten it in place */
+	bool identity = false;      /* sa_zjob_identity has rewritten it in place  */
 	sa_ctx *ctx = nullptr;
 	uint32_t *d_slots = nullptr, *d_seg = nullptr; /* d_seg: bytes, s1, s2, offset, [nc * nseg] each */
 	uint32_t *d_ghist = nullptr, *d_tile_adler = nullptr;
@@ -1395,12 +1396,60 @@ extern "C" int sa_zjob_normalize(sa_zjob *z, const struct sa_norm *norm)
 			sa_set_error("sa_zjob_normalize: the job's matrix has been normalised already");
 			return 1;
 		}
+		if (z->identity) {
+			sa_set_error("sa_zjob_normalize: the job's matrix holds percent identity (sa_zjob_identity), not scores");
+			return 1;
+		}
 		if (!sa_norm_check("sa_zjob_normalize", norm))
 			return 1;
 		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
 		if (!sa_normalize_in_place("sa_zjob_normalize", z->ctx, z->d_owned, norm, z->stream))
 			return 1;
 		z->normalized = true;
+		return 0;
+	});
+}
+
+/* Overwrites the job's own packed matrix with percent identity (sa_identity.hip), in order behind whatever the job has on its
+ * stream: every tile has been encoded and handed out by then, so the tiles stay raw and what is selected afterwards reads parts
+ * per million of identity.  Refuses what sa_zjob_normalize refuses, with the same wording, and a matrix that is normalised. */
+extern "C" int sa_zjob_identity(sa_zjob *z, int32_t denom)
+{
+	return sa_guard("sa_zjob_identity", 1, [&] {
+		if (!z) {
+			sa_set_error("sa_zjob_identity: null argument");
+			return 1;
+		}
+		if (!z->peers.empty()) {
+			sa_set_error("sa_zjob_identity: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+			return 1;
+		}
+		if (!z->d_packed) {
+			sa_set_error("sa_zjob_identity: the job walks a full matrix; the sweep reads the packed index");
+			return 1;
+		}
+		if (!z->d_owned || !z->ctx || z->d_owned != z->d_packed) {
+			sa_set_error("sa_zjob_identity: the job walks the caller's matrix, which is const; only a sa_hip_tiles_begin job owns its matrix");
+			return 1;
+		}
+		if (z->shells && z->next_batch < zjob_batches(z)) {
+			sa_set_error("sa_zjob_identity: the walk is not finished (sa_zjob_next has not returned 0 yet)");
+			return 1;
+		}
+		if (z->identity) {
+			sa_set_error("sa_zjob_identity: the job's matrix has been overwritten with percent identity already");
+			return 1;
+		}
+		if (z->normalized) {
+			sa_set_error("sa_zjob_identity: the job's matrix has been normalised already");
+			return 1;
+		}
+		if (!sa_identity_denom_check("sa_zjob_identity", denom))
+			return 1;
+		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
+		if (!sa_identity_in_place("sa_zjob_identity", z->ctx, z->d_owned, denom, z->stream))
+			return 1;
+		z->identity = true;
 		return 0;
 	});
 }

@@ -31,6 +31,7 @@ SaEnv sa_env_read()
 	e.gather = getenv("SA_HIP_GATHER") ? (atoi(getenv("SA_HIP_GATHER")) != 0) : -1;
 	e.tiles_split = number("SA_HIP_TILES_SPLIT", 0, 0, 64);
 	e.trace_batch_bytes = getenv("SA_HIP_TRACE_BATCH_BYTES") ? std::max(0LL, atoll(getenv("SA_HIP_TRACE_BATCH_BYTES"))) : 0LL;
+	e.identity_batch_bytes = getenv("SA_HIP_IDENTITY_BATCH_BYTES") ? std::max(0LL, atoll(getenv("SA_HIP_IDENTITY_BATCH_BYTES"))) : 0LL;
 	e.verbose = flag("SA_HIP_VERBOSE");
 	e.stamps = flag("SA_HIP_STAMPS");
 	e.stamps_dump = getenv("SA_HIP_STAMPS_DUMP");
