@@ -697,17 +697,27 @@ static int create_with_sequences(const char *path, const struct sa_host_store *s
 	return 0;
 }
 
-/* /neighbor_indices and /neighbor_scores: N x k int32 little endian, contiguous -- row r lists the k best partners of
- * sequence r (include/seqalign_hip.h: sa_hip_neighbors).  create = 0: added to the finished file at `path`, whose other
- * datasets stay as they are; create = 1: a new file with /sequences and these two, no /similarity_matrix. */
-int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int32_t k, const int32_t *index, const int32_t *score,
-			    int create)
+/* ---- side datasets: what is selected from the scores, beside (or instead of) /similarity_matrix --------------------------------- */
+/* one dataset of a side writer: contiguous, rank <= 3; `optional`: left out when there is no data (otherwise a set without data
+ * must have extent 0: it is created and nothing is written) */
+struct side_set {
+	const char *name;
+	int rank;
+	hsize_t dims[3];
+	hid_t file_type, mem_type;
+	const void *data;
+	bool optional;
+};
+#define SIDE_I32 H5T_STD_I32LE, H5T_NATIVE_INT32
+#define SIDE_I64 H5T_STD_I64LE, H5T_NATIVE_INT64
+
+/* The tail of every side writer.  create = 0: the sets are added to the finished file at `path`, whose other datasets stay as they
+ * are; create = 1: a new file with /sequences of `s` and these sets, no /similarity_matrix.  The sets are created in table order
+ * (the order decides the file's layout); the first failure ends the call with its message, the file closed, and a file this call
+ * created removed if `remove_failed`. */
+static int write_side_sets(const char *path, const struct sa_host_store *s, int create, bool remove_failed, const struct side_set *sets,
+			   int count)
 {
-	if (!path || !s || !index || !score)
-		return fail("Neighbor data missing");
-	const size_t dim = (size_t)s->in.num;
-	if (k < 1 || k > SA_HIP_NEIGHBORS_MAX || dim < 2 || (size_t)k > dim - 1)
-		return fail("Neighbor count must be between 1 and %d and below the number of sequences", SA_HIP_NEIGHBORS_MAX);
 	hid_t file;
 	if (create) {
 		if (create_with_sequences(path, s, &file))
@@ -721,21 +731,38 @@ int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int
 		if (file < 0)
 			return fail("Failed to open HDF5 file: %s", path);
 	}
-	const char *names[2] = { "/neighbor_indices", "/neighbor_scores" };
-	const int32_t *data[2] = { index, score };
-	hsize_t nd[2] = { dim, (hsize_t)k };
-	hid_t space = H5Screate_simple(2, nd, NULL);
 	int rc = 0;
-	for (int d = 0; d < 2 && !rc; d++) {
-		hid_t set = H5Dcreate2(file, names[d], H5T_STD_I32LE, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-		if (set < 0 || H5Dwrite(set, H5T_NATIVE_INT32, H5S_ALL, H5S_ALL, H5P_DEFAULT, data[d]) < 0)
-			rc = fail("Failed to write %s to HDF5", names[d] + 1);
+	for (int d = 0; d < count && !rc; d++) {
+		if (sets[d].optional && !sets[d].data)
+			continue;
+		hid_t space = H5Screate_simple(sets[d].rank, sets[d].dims, NULL);
+		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || (sets[d].dims[0] && H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
+			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
 		if (set >= 0)
 			H5Dclose(set);
+		H5Sclose(space);
 	}
-	H5Sclose(space);
 	H5Fclose(file);
+	if (rc && create && remove_failed)
+		remove(path);
 	return rc;
+}
+
+/* /neighbor_indices and /neighbor_scores: N x k int32 little endian -- row r lists the k best partners of sequence r
+ * (include/seqalign_hip.h: sa_hip_neighbors).  create: as write_side_sets has it. */
+int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int32_t k, const int32_t *index, const int32_t *score,
+			    int create)
+{
+	if (!path || !s || !index || !score)
+		return fail("Neighbor data missing");
+	const size_t dim = (size_t)s->in.num;
+	if (k < 1 || k > SA_HIP_NEIGHBORS_MAX || dim < 2 || (size_t)k > dim - 1)
+		return fail("Neighbor count must be between 1 and %d and below the number of sequences", SA_HIP_NEIGHBORS_MAX);
+	const struct side_set sets[2] = { { "/neighbor_indices", 2, { dim, (hsize_t)k }, SIDE_I32, index, false },
+					  { "/neighbor_scores", 2, { dim, (hsize_t)k }, SIDE_I32, score, false } };
+	/* (the one writer that leaves a failed file of its own behind: the others remove it.  Kept as it was) */
+	return write_side_sets(path, s, create, false, sets, 2);
 }
 
 /* The alignments of the N x k neighbour pairs (include/seqalign_hip.h: sa_hip_alignments), added to the finished file:
@@ -763,46 +790,18 @@ int sa_host_write_alignments(const char *path, const struct sa_host_store *s, in
 		offs[t] = r->cigar_off;
 	}
 	offs[np] = runs;
-	hid_t fapl = H5Pcreate(H5P_FILE_ACCESS), file;
-	H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
-	H5Pset_alignment(fapl, 4096, 4096);
-	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
-	H5Pclose(fapl);
-	if (file < 0) {
-		free(fields);
-		free(offs);
-		return fail("Failed to open HDF5 file: %s", path);
-	}
-	const uint32_t none = 0;
-	const struct {
-		const char *name;
-		int rank;
-		hsize_t dims[3];
-		hid_t file_type, mem_type;
-		const void *data;
-	} sets[3] = { { "/neighbor_alignment_records", 3, { dim, (hsize_t)k, 8 }, H5T_STD_I32LE, H5T_NATIVE_INT32, fields },
-		      { "/neighbor_cigar_offsets", 1, { np + 1, 0, 0 }, H5T_STD_I64LE, H5T_NATIVE_INT64, offs },
-		      { "/neighbor_cigars", 1, { (hsize_t)runs, 0, 0 }, H5T_STD_U32LE, H5T_NATIVE_UINT32, runs ? (const void *)cigar : &none } };
-	int rc = 0;
-	for (int d = 0; d < 3 && !rc; d++) {
-		hid_t space = H5Screate_simple(sets[d].rank, sets[d].dims, NULL);
-		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-		if (set < 0 || (sets[d].dims[0] && H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
-			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
-		if (set >= 0)
-			H5Dclose(set);
-		H5Sclose(space);
-	}
-	H5Fclose(file);
+	const struct side_set sets[3] = { { "/neighbor_alignment_records", 3, { dim, (hsize_t)k, 8 }, SIDE_I32, fields, false },
+					  { "/neighbor_cigar_offsets", 1, { np + 1 }, SIDE_I64, offs, false },
+					  { "/neighbor_cigars", 1, { (hsize_t)runs }, H5T_STD_U32LE, H5T_NATIVE_UINT32, cigar, false } };
+	const int rc = write_side_sets(path, s, 0, false, sets, 3);
 	free(fields);
 	free(offs);
 	return rc;
 }
 
 /* The score graph as CSR (include/seqalign_hip.h: sa_hip_edges): /edge_offsets N + 1 I64LE, /edge_indices and /edge_scores
- * E = offsets[N] I32LE each (extent 0 when there is no edge), contiguous.  create = 0: added to the finished file at `path`, whose
- * other datasets stay as they are; create = 1: a new file with /sequences and these three, no /similarity_matrix.  The arrays
- * are checked before anything is opened: offsets[0] == 0, offsets non-decreasing, every index in [0, N). */
+ * E = offsets[N] I32LE each (extent 0 when there is no edge).  create: as write_side_sets has it.  The arrays are checked before
+ * anything is opened: offsets[0] == 0, offsets non-decreasing, every index in [0, N). */
 int sa_host_write_edges(const char *path, const struct sa_host_store *s, const int64_t *offsets, const int32_t *index, const int32_t *score,
 			int create)
 {
@@ -820,47 +819,15 @@ int sa_host_write_edges(const char *path, const struct sa_host_store *s, const i
 	for (int64_t t = 0; t < count; t++)
 		if (index[t] < 0 || (size_t)index[t] >= dim)
 			return fail("Edge index %d at position %lld is outside the %zu sequences", index[t], (long long)t, dim);
-	hid_t file;
-	if (create) {
-		if (create_with_sequences(path, s, &file))
-			return 1;
-	} else {
-		hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
-		H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
-		H5Pset_alignment(fapl, 4096, 4096);
-		H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
-		H5Pclose(fapl);
-		if (file < 0)
-			return fail("Failed to open HDF5 file: %s", path);
-	}
-	const struct {
-		const char *name;
-		hsize_t extent;
-		hid_t file_type, mem_type;
-		const void *data;
-	} sets[3] = { { "/edge_offsets", (hsize_t)dim + 1, H5T_STD_I64LE, H5T_NATIVE_INT64, offsets },
-		      { "/edge_indices", (hsize_t)count, H5T_STD_I32LE, H5T_NATIVE_INT32, index },
-		      { "/edge_scores", (hsize_t)count, H5T_STD_I32LE, H5T_NATIVE_INT32, score } };
-	int rc = 0;
-	for (int d = 0; d < 3 && !rc; d++) {
-		hid_t space = H5Screate_simple(1, &sets[d].extent, NULL);
-		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-		if (set < 0 || (sets[d].extent && H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
-			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
-		if (set >= 0)
-			H5Dclose(set);
-		H5Sclose(space);
-	}
-	H5Fclose(file);
-	if (rc && create)
-		remove(path);
-	return rc;
+	const struct side_set sets[3] = { { "/edge_offsets", 1, { (hsize_t)dim + 1 }, SIDE_I64, offsets, false },
+					  { "/edge_indices", 1, { (hsize_t)count }, SIDE_I32, index, false },
+					  { "/edge_scores", 1, { (hsize_t)count }, SIDE_I32, score, false } };
+	return write_side_sets(path, s, create, true, sets, 3);
 }
 
 /* The single-linkage tree (include/seqalign_hip.h: sa_hip_linkage): /linkage_pairs (N - 1) x 2 I32LE and /linkage_scores N - 1
- * I32LE, contiguous; with `labels` also /cluster_labels N I32LE (--clusters T).  create = 0: added to the finished file at `path`,
- * whose other datasets stay as they are; create = 1: a new file with /sequences and these, no /similarity_matrix.  The pairs are
- * checked before anything is opened: every index in [0, N), lo < hi. */
+ * I32LE; with `labels` also /cluster_labels N I32LE (--clusters T).  create: as write_side_sets has it.  The pairs are checked
+ * before anything is opened: every index in [0, N), lo < hi. */
 int sa_host_write_linkage(const char *path, const struct sa_host_store *s, const int32_t *pairs, const int32_t *score, const int32_t *labels,
 			  int create)
 {
@@ -883,48 +850,16 @@ int sa_host_write_linkage(const char *path, const struct sa_host_store *s, const
 		for (size_t r = 0; r < dim; r++)
 			if (labels[r] < 0 || (size_t)labels[r] > r)
 				return fail("Cluster label %d of sequence %zu is not the smallest index of a cluster", labels[r], r);
-	hid_t file;
-	if (create) {
-		if (create_with_sequences(path, s, &file))
-			return 1;
-	} else {
-		hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
-		H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
-		H5Pset_alignment(fapl, 4096, 4096);
-		H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
-		H5Pclose(fapl);
-		if (file < 0)
-			return fail("Failed to open HDF5 file: %s", path);
-	}
-	const struct {
-		const char *name;
-		int rank;
-		hsize_t dims[2];
-		const int32_t *data;
-	} sets[3] = { { "/linkage_pairs", 2, { (hsize_t)merges, 2 }, pairs },
-		      { "/linkage_scores", 1, { (hsize_t)merges, 0 }, score },
-		      { "/cluster_labels", 1, { (hsize_t)dim, 0 }, labels } };
-	int rc = 0;
-	for (int d = 0; d < (labels ? 3 : 2) && !rc; d++) {
-		hid_t space = H5Screate_simple(sets[d].rank, sets[d].dims, NULL);
-		hid_t set = H5Dcreate2(file, sets[d].name, H5T_STD_I32LE, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-		if (set < 0 || (sets[d].dims[0] && H5Dwrite(set, H5T_NATIVE_INT32, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
-			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
-		if (set >= 0)
-			H5Dclose(set);
-		H5Sclose(space);
-	}
-	H5Fclose(file);
-	if (rc && create)
-		remove(path);
-	return rc;
+	const struct side_set sets[3] = { { "/linkage_pairs", 2, { (hsize_t)merges, 2 }, SIDE_I32, pairs, false },
+					  { "/linkage_scores", 1, { (hsize_t)merges }, SIDE_I32, score, false },
+					  { "/cluster_labels", 1, { (hsize_t)dim }, SIDE_I32, labels, true } };
+	return write_side_sets(path, s, create, true, sets, 3);
 }
 
 /* Order statistics of the scores (include/seqalign_hip.h: sa_hip_select): /score_quantiles m F64LE (the fractions as given),
- * /score_quantile_values m I32LE and /score_quantile_below m I64LE, contiguous; with `edge_min` also /edge_min_score 1 I32LE
- * (--min-quantile), with `cluster_min` also /cluster_min_score 1 I32LE (--clusters-quantile).  create = 0: added to the finished
- * file at `path`, whose other datasets stay as they are; create = 1: a new file with /sequences and these.  The arrays are checked
- * before anything is opened: 1 <= m <= 16, every fraction in [0, 1], every count in [0, P). */
+ * /score_quantile_values m I32LE and /score_quantile_below m I64LE; with `edge_min` also /edge_min_score 1 I32LE (--min-quantile),
+ * with `cluster_min` also /cluster_min_score 1 I32LE (--clusters-quantile).  create: as write_side_sets has it.  The arrays are
+ * checked before anything is opened: 1 <= m <= 16, every fraction in [0, 1], every count in [0, P). */
 int sa_host_write_quantiles(const char *path, const struct sa_host_store *s, const double *fractions, const int32_t *values,
 			    const int64_t *below, int32_t m, const int32_t *edge_min, const int32_t *cluster_min, int create)
 {
@@ -939,50 +874,17 @@ int sa_host_write_quantiles(const char *path, const struct sa_host_store *s, con
 		if (below[t] < 0 || below[t] >= pairs)
 			return fail("Quantile %d has %lld pairs below it, outside the %lld pairs", t, (long long)below[t], (long long)pairs);
 	}
-	hid_t file;
-	if (create) {
-		if (create_with_sequences(path, s, &file))
-			return 1;
-	} else {
-		hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
-		H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
-		H5Pset_alignment(fapl, 4096, 4096);
-		H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
-		H5Pclose(fapl);
-		if (file < 0)
-			return fail("Failed to open HDF5 file: %s", path);
-	}
-	const struct {
-		const char *name;
-		hsize_t extent;
-		hid_t file_type, mem_type;
-		const void *data;
-	} sets[5] = { { "/score_quantiles", (hsize_t)m, H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, fractions },
-		      { "/score_quantile_values", (hsize_t)m, H5T_STD_I32LE, H5T_NATIVE_INT32, values },
-		      { "/score_quantile_below", (hsize_t)m, H5T_STD_I64LE, H5T_NATIVE_INT64, below },
-		      { "/edge_min_score", 1, H5T_STD_I32LE, H5T_NATIVE_INT32, edge_min },
-		      { "/cluster_min_score", 1, H5T_STD_I32LE, H5T_NATIVE_INT32, cluster_min } };
-	int rc = 0;
-	for (int d = 0; d < 5 && !rc; d++) {
-		if (!sets[d].data)
-			continue;
-		hid_t space = H5Screate_simple(1, &sets[d].extent, NULL);
-		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-		if (set < 0 || H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0)
-			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
-		if (set >= 0)
-			H5Dclose(set);
-		H5Sclose(space);
-	}
-	H5Fclose(file);
-	if (rc && create)
-		remove(path);
-	return rc;
+	const struct side_set sets[5] = { { "/score_quantiles", 1, { (hsize_t)m }, H5T_IEEE_F64LE, H5T_NATIVE_DOUBLE, fractions, false },
+					  { "/score_quantile_values", 1, { (hsize_t)m }, SIDE_I32, values, false },
+					  { "/score_quantile_below", 1, { (hsize_t)m }, SIDE_I64, below, false },
+					  { "/edge_min_score", 1, { 1 }, SIDE_I32, edge_min, true },
+					  { "/cluster_min_score", 1, { 1 }, SIDE_I32, cluster_min, true } };
+	return write_side_sets(path, s, create, true, sets, 5);
 }
 
 /* Normalised scores (include/seqalign_hip.h: struct sa_norm): /normalization_denominators N I32LE, /normalization_rule 2 I32LE
- * (source, rule) and /normalization_scale 1 I32LE, contiguous, added to the finished file at `path`, whose other datasets stay as
- * they are.  The arguments are checked before anything is opened. */
+ * (source, rule) and /normalization_scale 1 I32LE, added to the finished file at `path`.  The arguments are checked before anything
+ * is opened. */
 int sa_host_write_normalization(const char *path, const struct sa_host_store *s, const int32_t *denominators, int32_t source, int32_t rule)
 {
 	if (!path || !s || !denominators)
@@ -993,39 +895,15 @@ int sa_host_write_normalization(const char *path, const struct sa_host_store *s,
 		return fail("Normalization source %d is neither self-score (%d) nor length (%d)", source, (int)SA_NORM_SELF, (int)SA_NORM_LENGTH);
 	if (rule != SA_NORM_MIN && rule != SA_NORM_MAX && rule != SA_NORM_MEAN)
 		return fail("Normalization rule %d is none of min (%d), max (%d), mean (%d)", rule, (int)SA_NORM_MIN, (int)SA_NORM_MAX, (int)SA_NORM_MEAN);
-	hid_t file;
-	hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
-	H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
-	H5Pset_alignment(fapl, 4096, 4096);
-	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
-	H5Pclose(fapl);
-	if (file < 0)
-		return fail("Failed to open HDF5 file: %s", path);
 	const int32_t how[2] = { source, rule }, scale = SA_NORM_SCALE;
-	const struct {
-		const char *name;
-		hsize_t extent;
-		const int32_t *data;
-	} sets[3] = { { "/normalization_denominators", (hsize_t)s->in.num, denominators },
-		      { "/normalization_rule", 2, how },
-		      { "/normalization_scale", 1, &scale } };
-	int rc = 0;
-	for (int d = 0; d < 3 && !rc; d++) {
-		hid_t space = H5Screate_simple(1, &sets[d].extent, NULL);
-		hid_t set = H5Dcreate2(file, sets[d].name, H5T_STD_I32LE, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-		if (set < 0 || H5Dwrite(set, H5T_NATIVE_INT32, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0)
-			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
-		if (set >= 0)
-			H5Dclose(set);
-		H5Sclose(space);
-	}
-	H5Fclose(file);
-	return rc;
+	const struct side_set sets[3] = { { "/normalization_denominators", 1, { (hsize_t)s->in.num }, SIDE_I32, denominators, false },
+					  { "/normalization_rule", 1, { 2 }, SIDE_I32, how, false },
+					  { "/normalization_scale", 1, { 1 }, SIDE_I32, &scale, false } };
+	return write_side_sets(path, s, 0, false, sets, 3);
 }
 
-/* Percent identity (include/seqalign_hip.h: SA_PID_*): /identity_rule 1 I32LE (the denominator) and /identity_scale 1 I32LE,
- * contiguous, added to the finished file at `path`, whose other datasets stay as they are.  The arguments are checked before
- * anything is opened. */
+/* Percent identity (include/seqalign_hip.h: SA_PID_*): /identity_rule 1 I32LE (the denominator) and /identity_scale 1 I32LE, added
+ * to the finished file at `path`.  The arguments are checked before anything is opened. */
 int sa_host_write_identity(const char *path, int32_t denom)
 {
 	if (!path)
@@ -1033,32 +911,10 @@ int sa_host_write_identity(const char *path, int32_t denom)
 	if (denom != SA_PID_COLUMNS && denom != SA_PID_SHORTER && denom != SA_PID_LONGER && denom != SA_PID_MEAN)
 		return fail("Identity denominator %d is none of columns (%d), shorter (%d), longer (%d), mean (%d)", denom, (int)SA_PID_COLUMNS,
 			    (int)SA_PID_SHORTER, (int)SA_PID_LONGER, (int)SA_PID_MEAN);
-	hid_t file;
-	hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
-	H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
-	H5Pset_alignment(fapl, 4096, 4096);
-	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDWR, fapl); } H5E_END_TRY
-	H5Pclose(fapl);
-	if (file < 0)
-		return fail("Failed to open HDF5 file: %s", path);
 	const int32_t scale = SA_NORM_SCALE;
-	const struct {
-		const char *name;
-		const int32_t *data;
-	} sets[2] = { { "/identity_rule", &denom }, { "/identity_scale", &scale } };
-	int rc = 0;
-	for (int d = 0; d < 2 && !rc; d++) {
-		const hsize_t extent = 1;
-		hid_t space = H5Screate_simple(1, &extent, NULL);
-		hid_t set = H5Dcreate2(file, sets[d].name, H5T_STD_I32LE, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-		if (set < 0 || H5Dwrite(set, H5T_NATIVE_INT32, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0)
-			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
-		if (set >= 0)
-			H5Dclose(set);
-		H5Sclose(space);
-	}
-	H5Fclose(file);
-	return rc;
+	const struct side_set sets[2] = { { "/identity_rule", 1, { 1 }, SIDE_I32, &denom, false },
+					  { "/identity_scale", 1, { 1 }, SIDE_I32, &scale, false } };
+	return write_side_sets(path, NULL, 0, false, sets, 2);
 }
 
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder

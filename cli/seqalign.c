@@ -25,7 +25,8 @@
  *             --identity DENOM   (the same selections from PERCENT IDENTITY in parts per million: identities of the canonical
  *             alignment of every pair, carried through one sweep on the device, over columns | shorter | longer | mean;
  *             /similarity_matrix stays raw: /identity_rule, /identity_scale)
- * Flow: parse+validate -> load (FASTA/DSV) -> filter -> allocate matrix -> sa_hip_align -> HDF5 -> neighbours -> their alignments -> score graph -> linkage -> -B report.
+ * Flow (main, one function per phase): options -> banner -> load + filter -> output plan -> the first pass (tile job | one selection only |
+ * host matrix) -> per selection, in the order of the file: its second pass where the first left it unanswered, then its datasets -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
 #define _GNU_SOURCE
@@ -210,10 +211,6 @@ static void usage(const char *argv0)
 	       argv0);
 }
 
-/* a fraction in [0, 1] (no NaN, nothing behind it) onto the list of an option set; false + message otherwise */
-struct options;
-static bool add_quantile(struct options *o, const char *s, size_t len, int *at);
-
 static bool parse_long(const char *s, long lo, long hi, long *out)
 {
 	char *end;
@@ -225,6 +222,7 @@ static bool parse_long(const char *s, long lo, long hi, long *out)
 	return true;
 }
 
+/* a fraction in [0, 1] (no NaN, nothing behind it) onto the list of an option set; false + message otherwise */
 static bool add_quantile(struct options *o, const char *s, size_t len, int *at)
 {
 	char text[64], *end;
@@ -506,54 +504,173 @@ static int next_tiles(void *user, uint32_t *rows, uint32_t *cols, const uint8_t 
 	return n;
 }
 
-/* the one-call selections, whichever quantity they select from: pid != NULL percent identity under *pid (the *_pid calls),
- * otherwise the *_norm calls, which with norm == NULL are their namesakes */
-static bool sel_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm,
-			  const int32_t *pid)
+/* what is selected from: pid != NULL percent identity under *pid (the *_pid calls, sa_zjob_identity), otherwise norm != NULL
+ * normalised scores (the *_norm calls, sa_zjob_normalize), otherwise the scores: the *_norm calls with norm == NULL are their namesakes */
+struct quantity {
+	const struct sa_norm *norm;
+	const int32_t *pid;
+};
+
+/* the one-call selections, whichever quantity they select from */
+static bool sel_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, struct quantity q)
 {
-	return pid ? sa_hip_neighbors_pid(in, sc, k, index, score, *pid) : sa_hip_neighbors_norm(in, sc, k, index, score, norm);
+	return q.pid ? sa_hip_neighbors_pid(in, sc, k, index, score, *q.pid) : sa_hip_neighbors_norm(in, sc, k, index, score, q.norm);
 }
 
-static sa_edges *sel_edges(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm, const int32_t *pid)
+static sa_edges *sel_edges(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, struct quantity q)
 {
-	return pid ? sa_hip_edges_pid(in, sc, min_score, *pid) : sa_hip_edges_norm(in, sc, min_score, norm);
+	return q.pid ? sa_hip_edges_pid(in, sc, min_score, *q.pid) : sa_hip_edges_norm(in, sc, min_score, q.norm);
 }
 
-static sa_linkage *sel_linkage(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm, const int32_t *pid)
+static sa_linkage *sel_linkage(struct sa_input in, const struct sa_scoring *sc, struct quantity q)
 {
-	return pid ? sa_hip_linkage_pid(in, sc, *pid) : sa_hip_linkage_norm(in, sc, norm);
+	return q.pid ? sa_hip_linkage_pid(in, sc, *q.pid) : sa_hip_linkage_norm(in, sc, q.norm);
 }
 
-static bool sel_select(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below,
-		       const struct sa_norm *norm, const int32_t *pid)
+static bool sel_select(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below, struct quantity q)
 {
-	return pid ? sa_hip_select_pid(in, sc, ranks, m, value, below, *pid) : sa_hip_select_norm(in, sc, ranks, m, value, below, norm);
+	return q.pid ? sa_hip_select_pid(in, sc, ranks, m, value, below, *q.pid) : sa_hip_select_norm(in, sc, ranks, m, value, below, q.norm);
 }
 
-static sa_edges *sel_edges_at_rank(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below,
-				   const struct sa_norm *norm, const int32_t *pid)
+static sa_edges *sel_edges_at_rank(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below, struct quantity q)
 {
-	return pid ? sa_hip_edges_at_rank_pid(in, sc, rank, min_score, below, *pid) : sa_hip_edges_at_rank_norm(in, sc, rank, min_score, below, norm);
+	return q.pid ? sa_hip_edges_at_rank_pid(in, sc, rank, min_score, below, *q.pid) : sa_hip_edges_at_rank_norm(in, sc, rank, min_score, below, q.norm);
 }
 
 static sa_linkage *sel_linkage_with_ranks(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value,
-					  int64_t *below, const struct sa_norm *norm, const int32_t *pid)
+					  int64_t *below, struct quantity q)
 {
-	return pid ? sa_hip_linkage_with_ranks_pid(in, sc, ranks, m, value, below, *pid)
-		   : sa_hip_linkage_with_ranks_norm(in, sc, ranks, m, value, below, norm);
+	return q.pid ? sa_hip_linkage_with_ranks_pid(in, sc, ranks, m, value, below, *q.pid)
+		     : sa_hip_linkage_with_ranks_norm(in, sc, ranks, m, value, below, q.norm);
 }
 
-int main(int argc, char **argv)
-{
-	t_process0 = now();
+/* One run of the tool: what main's phases hand to each other.  Every selection keeps its result with its bookkeeping: `seconds` the
+ * device time of the call that answered it, `second_pass` whether that call aligned again (the -B report says so). */
+struct run {
+	const char *argv0;
 	struct options o;
-	const int prc = parse_args(argc, argv, &o);
-	if (prc == 2)
-		return 0;
 	struct sa_scoring sc;
-	memset(&sc, 0, sizeof(sc));
+	struct sa_host_store store;
+	size_t n;
+	long long npairs;
+	bool show_progress;
+	double t_in, t_filter, t_align, t_out, t_setup; /* the phases of the -B report; set-up is outside them, as in the reference */
+	int schedule; /* sa_hip_last_align_path of the host-matrix branch */
+	struct sa_output out; /* the output plan: the host matrix, or the tile job (device_deflate), or no matrix at all */
+	bool pinned, no_matrix, device_deflate;
+	size_t zchunk;
+	struct sa_norm norm_spec; /* the quantity (--normalize or --identity, never both), and the device time of its sweep */
+	struct quantity q;
+	double t_quantity;
+	double t_write0; /* WRITE_OUT */
+	struct { int32_t *index, *score; bool done, second_pass; double seconds; } nb;
+	struct { double seconds; long long runs; } trace;
+	struct { /* the fractions' ranks: one select call answers all of them, where the matrix is */
+		int64_t ranks[SA_HIP_SELECT_MAX], below[SA_HIP_SELECT_MAX];
+		int32_t values[SA_HIP_SELECT_MAX];
+		bool done, second_pass;
+		double seconds;
+	} qt;
+	struct { sa_edges *edges; bool second_pass; double seconds; long long count; } eg;
+	struct { sa_linkage *tree; bool second_pass; double seconds; int rounds; int32_t merges, clusters; } lk;
+};
+
+/* the end of a phase that cannot go on: the message (sa_last_error(), sa_host_error(), or the tool's own), and false */
+static bool failed(const char *message)
+{
+	err("%s", message);
+	return false;
+}
+
+/* the end of the progress line, once the alignment is done */
+static void finish_progress(const struct run *r)
+{
+	if (!r->show_progress)
+		return;
+	progress_line(1.0, NULL);
+	fputc('\n', stderr);
+	sa_hip_set_progress(NULL, NULL);
+}
+
+/* a sa_host_write_* call, unless -W: its message when it failed, otherwise its time to Output and its stamp */
+#define WRITE_OUT(r, call, what) ((r)->o.no_write || ((r)->t_write0 = now(), written((r), (call), (what))))
+static bool written(struct run *r, int rc, const char *what)
+{
+	if (rc)
+		return failed(sa_host_error());
+	r->t_out += now() - r->t_write0;
+	stamp(what);
+	return true;
+}
+
+/* a score graph / a tree as it comes back from whichever call built it (NULL: the call failed, the message is the caller's) */
+static bool take_edges(struct run *r, sa_edges *edges)
+{
+	r->eg.edges = edges;
+	r->eg.seconds = sa_hip_last_edges_seconds();
+	return edges != NULL;
+}
+
+static bool take_tree(struct run *r, sa_linkage *tree)
+{
+	r->lk.tree = tree;
+	r->lk.seconds = sa_hip_last_linkage_seconds();
+	r->lk.rounds = sa_hip_last_linkage_rounds();
+	return tree != NULL;
+}
+
+static double last_quantity_seconds(struct quantity q)
+{
+	return q.norm ? sa_hip_last_normalize_seconds() : sa_hip_last_identity_seconds();
+}
+
+static void quantiles_answered(struct run *r)
+{
+	r->qt.done = true;
+	r->qt.seconds = sa_hip_last_select_seconds();
+	if (r->o.min_q >= 0)
+		r->o.min_score = r->qt.values[r->o.min_q];
+}
+
+/* Which call answers the fractions when it takes one more alignment into device memory, decided here for every caller: with the score
+ * graph where its cut is the only fraction (one alignment serves both), else with the tree where `with_tree` allows it and one is
+ * still due, else a plain select in a pass of its own.  Makes that call; Q_FAILED with the message printed. */
+enum q_call { Q_FAILED, Q_EDGES_AT_RANK, Q_LINKAGE_WITH_RANKS, Q_SELECT };
+static enum q_call answer_quantiles(struct run *r, bool with_tree)
+{
+	const struct options *o = &r->o;
+	enum q_call call;
+	bool got;
+	if (o->min_q >= 0 && o->nquant == 1 && !r->eg.edges) {
+		call = Q_EDGES_AT_RANK;
+		got = take_edges(r, sel_edges_at_rank(r->store.in, &r->sc, r->qt.ranks[0], &r->qt.values[0], &r->qt.below[0], r->q));
+	} else if (with_tree && o->linkage && !r->lk.tree) {
+		call = Q_LINKAGE_WITH_RANKS;
+		got = take_tree(r, sel_linkage_with_ranks(r->store.in, &r->sc, r->qt.ranks, o->nquant, r->qt.values, r->qt.below, r->q));
+	} else {
+		call = Q_SELECT;
+		got = sel_select(r->store.in, &r->sc, r->qt.ranks, o->nquant, r->qt.values, r->qt.below, r->q);
+	}
+	if (!got) {
+		err("%s", sa_last_error());
+		return Q_FAILED;
+	}
+	quantiles_answered(r);
+	return call;
+}
+
+/* ---- the phases of main, in its order ------------------------------------------------------------------------------------------ */
+/* options, -l, validation in the reference's terms (src/bio/align.c:130-201, ga.c:70-88, output.c:126-148) and the scoring.
+ * returns 0 ok, 1 error, 2 handled-and-exit-success */
+static int set_up(int argc, char **argv, struct run *r)
+{
+	struct options *o = &r->o;
+	struct sa_scoring *sc = &r->sc;
+	const int prc = parse_args(argc, argv, o);
+	if (prc == 2)
+		return 2;
 	bool ok = prc == 0;
-	if (ok && o.list) { /* -l: src/bio/matrices.c:27-33 */
+	if (ok && o->list) { /* -l: src/bio/matrices.c:27-33 */
 		printf("\nListing available substitution matrices\n");
 		for (int fam = 0; fam < 2; fam++) {
 			printf("\n%s Matrices:\n  ", fam ? "Nucleotide" : "Amino");
@@ -562,730 +679,609 @@ int main(int argc, char **argv)
 					printf("%-10s%s", sa_matrix_name(k), ++col % 5 ? "" : "\n  ");
 			putchar('\n');
 		}
-		return 0;
+		return 2;
 	}
-	/* ---- validation, in the reference's terms (src/bio/align.c:130-201, ga.c:70-88, output.c:126-148) */
-	if (ok && !o.input)
+	if (ok && !o->input)
 		ok = (err("Missing required option: -i, --input"), false);
-	if (ok && !o.matrix)
+	if (ok && !o->matrix)
 		ok = (err("Missing required option: -m, --matrix"), false);
-	if (ok && !o.align)
+	if (ok && !o->align)
 		ok = (err("Missing required option: -a, --align"), false);
-	if (ok && o.output && o.no_write)
+	if (ok && o->output && o->no_write)
 		ok = (err("Options -o, --output and -W, --no-write conflict"), false);
-	if (ok && !o.output && !o.no_write)
+	if (ok && !o->output && !o->no_write)
 		ok = (err("Missing required option: -o, --output"), false);
-	if (ok && o.neighbors_only && !o.neighbors)
+	if (ok && o->neighbors_only && !o->neighbors)
 		ok = (err("Option --neighbors-only requires -k, --neighbors"), false);
-	if (ok && o.alignments && !o.neighbors)
+	if (ok && o->alignments && !o->neighbors)
 		ok = (err("Option --alignments requires -k, --neighbors"), false);
-	if (ok && o.has_min_score && o.min_q >= 0)
+	if (ok && o->has_min_score && o->min_q >= 0)
 		ok = (err("Options --min-score and --min-quantile conflict: one threshold for the score graph"), false);
-	if (ok && o.has_clusters && o.clusters_q >= 0)
+	if (ok && o->has_clusters && o->clusters_q >= 0)
 		ok = (err("Options --clusters and --clusters-quantile conflict: one threshold for the clusters"), false);
-	if (ok && o.min_q >= 0)
-		o.has_min_score = true; /* (min_score itself follows from the selection) */
-	if (ok && o.clusters_q >= 0)
-		o.has_clusters = true;
-	if (ok && o.edges_only && !o.has_min_score)
+	if (ok && o->min_q >= 0)
+		o->has_min_score = true; /* (min_score itself follows from the selection) */
+	if (ok && o->clusters_q >= 0)
+		o->has_clusters = true;
+	if (ok && o->edges_only && !o->has_min_score)
 		ok = (err("Option --edges-only requires --min-score or --min-quantile"), false);
-	if (ok && o.edges_only && o.neighbors)
+	if (ok && o->edges_only && o->neighbors)
 		ok = (err("Options --edges-only and -k, --neighbors conflict: the neighbors need a pass of their own (use --min-score without --edges-only)"), false);
-	if (ok && o.linkage_only && o.neighbors)
+	if (ok && o->linkage_only && o->neighbors)
 		ok = (err("Options --linkage-only and -k, --neighbors conflict: the neighbors need a pass of their own (use --linkage without --linkage-only)"), false);
-	if (ok && o.linkage_only && o.has_min_score)
+	if (ok && o->linkage_only && o->has_min_score)
 		ok = (err("Options --linkage-only and --min-score conflict: the score graph needs a pass of its own (use --linkage without --linkage-only)"), false);
-	if (ok && o.normalize && !o.neighbors && !o.has_min_score && !o.linkage && !o.nquant)
+	if (ok && o->normalize && !o->neighbors && !o->has_min_score && !o->linkage && !o->nquant)
 		ok = (err("Option --normalize requires something selected from the scores: -k, --min-score, --min-quantile, --linkage, --clusters, "
 			  "--clusters-quantile or --quantiles (the similarity matrix itself stays raw)"), false);
-	if (ok && o.identity && o.normalize)
+	if (ok && o->identity && o->normalize)
 		ok = (err("Options --identity and --normalize conflict: one quantity to select from"), false);
-	if (ok && o.identity && !o.neighbors && !o.has_min_score && !o.linkage && !o.nquant)
+	if (ok && o->identity && !o->neighbors && !o->has_min_score && !o->linkage && !o->nquant)
 		ok = (err("Option --identity requires something selected from the scores: -k, --min-score, --min-quantile, --linkage, --clusters, "
 			  "--clusters-quantile or --quantiles (the similarity matrix itself stays raw)"), false);
-	if (ok && sa_matrix_load(o.matrix, sc.lut, sc.sub))
+	if (ok && sa_matrix_load(o->matrix, sc->lut, sc->sub))
 		ok = (err("Invalid substitution matrix name"), false);
-	if (ok && (sc.method = sa_method_parse(o.align)) < 0)
+	if (ok && (sc->method = sa_method_parse(o->align)) < 0)
 		ok = (err("Invalid alignment method"), false);
-	if (ok && o.gap_pen >= 0 && (o.gap_open >= 0 || o.gap_ext >= 0))
+	if (ok && o->gap_pen >= 0 && (o->gap_open >= 0 || o->gap_ext >= 0))
 		ok = (err("Options -p and -s/-e conflict"), false);
-	if (ok && sa_method_gap_kind(sc.method) == SA_GAP_LINEAR) {
-		if (o.gap_open >= 0 || o.gap_ext >= 0)
+	if (ok && sa_method_gap_kind(sc->method) == SA_GAP_LINEAR) {
+		if (o->gap_open >= 0 || o->gap_ext >= 0)
 			ok = (err("Affine gaps cannot be set for non-affine methods"), false);
-		else if (o.gap_pen < 0)
+		else if (o->gap_pen < 0)
 			ok = (err("Missing required option: -p, --gap-penalty"), false);
 	} else if (ok) {
-		if (o.gap_pen >= 0)
+		if (o->gap_pen >= 0)
 			ok = (err("Gap penalty cannot be set for non-linear methods"), false);
-		else if (o.gap_open < 0 || o.gap_ext < 0)
+		else if (o->gap_open < 0 || o->gap_ext < 0)
 			ok = (err("Missing required option: -s, --gap-open and -e, --gap-extend"), false);
 	}
 	if (ok) {
-		sc.gap_pen = o.gap_pen >= 0 ? -(int32_t)o.gap_pen : 0;
-		sc.gap_opn = o.gap_open >= 0 ? -(int32_t)o.gap_open : 0;
-		sc.gap_ext = o.gap_ext >= 0 ? -(int32_t)o.gap_ext : 0;
-		if (sc.method == SA_METHOD_GA && sc.gap_opn == sc.gap_ext &&
+		sc->gap_pen = o->gap_pen >= 0 ? -(int32_t)o->gap_pen : 0;
+		sc->gap_opn = o->gap_open >= 0 ? -(int32_t)o->gap_open : 0;
+		sc->gap_ext = o->gap_ext >= 0 ? -(int32_t)o->gap_ext : 0;
+		if (sc->method == SA_METHOD_GA && sc->gap_opn == sc->gap_ext &&
 		    ask("Equal affine gaps found, switch to Needleman-Wunsch?", true)) {
-			sc.method = SA_METHOD_NW;
-			sc.gap_pen = sc.gap_opn;
-			sc.gap_opn = sc.gap_ext = SA_SCORE_MIN;
+			sc->method = SA_METHOD_NW;
+			sc->gap_pen = sc->gap_opn;
+			sc->gap_opn = sc->gap_ext = SA_SCORE_MIN;
 		}
 	}
-	if (ok && o.no_device)
+	if (ok && o->no_device)
 		ok = (err("-C/--no-cuda: this build has no CPU alignment path (HIP device required)"), false);
-	if (ok && o.output && access(o.output, F_OK) == 0) {
+	if (ok && o->output && access(o->output, F_OK) == 0) {
 		if (!ask("Output file already exists. Do you want to DELETE it?", false))
 			ok = (err("Output file exists and will not be overwritten"), false);
-		else if (remove(o.output) != 0)
+		else if (remove(o->output) != 0)
 			ok = (err("Failed to delete existing output file"), false);
 	}
 	if (!ok) {
-		fprintf(stderr, "Use %s -h, --help for usage information\n", argv[0]);
+		fprintf(stderr, "Use %s -h, --help for usage information\n", r->argv0);
 		return 1;
 	}
-
 	/* -T: host threads (validate_threads, src/system/os.c:466-473).  The alignment itself runs on the device; the
 	 * host's parallel loops are the triangular->full expansion of the HDF5 writer and the CPU filter */
-	if (o.threads > 0)
-		omp_set_num_threads(o.threads);
+	if (o->threads > 0)
+		omp_set_num_threads(o->threads);
+	return 0;
+}
 
+static void banner(const struct run *r)
+{
+	const struct options *o = &r->o;
 	info("SEQUENCE ALIGNER (MI355X / HIP)");
-	info("Input: %s", o.input);
-	if (o.output)
-		info("Output: %s", o.output);
-	info("Matrix: %s", o.matrix);
-	info("Method: %s", sa_method_name(sc.method));
-	if (sc.method == SA_METHOD_NW)
-		info("Gap penalty: %d", sc.gap_pen);
+	info("Input: %s", o->input);
+	if (o->output)
+		info("Output: %s", o->output);
+	info("Matrix: %s", o->matrix);
+	info("Method: %s", sa_method_name(r->sc.method));
+	if (r->sc.method == SA_METHOD_NW)
+		info("Gap penalty: %d", r->sc.gap_pen);
 	else
-		info("Gap open: %d, extend: %d", sc.gap_opn, sc.gap_ext);
-	if (o.filter > 0.0f)
-		info("Filter threshold: %.1f%%", (double)o.filter * 100.0);
-	if (o.neighbors)
-		info("Neighbors: %d per sequence%s", o.neighbors, o.neighbors_only ? " (no similarity matrix)" : "");
-	if (o.min_q >= 0)
-		info("Score graph: pairs that score at least the %g quantile of the scores%s", o.quantiles[o.min_q],
-		     o.edges_only ? " (no similarity matrix)" : "");
-	else if (o.has_min_score)
-		info("Score graph: pairs that score at least %d%s", o.min_score, o.edges_only ? " (no similarity matrix)" : "");
+		info("Gap open: %d, extend: %d", r->sc.gap_opn, r->sc.gap_ext);
+	if (o->filter > 0.0f)
+		info("Filter threshold: %.1f%%", (double)o->filter * 100.0);
+	if (o->neighbors)
+		info("Neighbors: %d per sequence%s", o->neighbors, o->neighbors_only ? " (no similarity matrix)" : "");
+	if (o->min_q >= 0)
+		info("Score graph: pairs that score at least the %g quantile of the scores%s", o->quantiles[o->min_q],
+		     o->edges_only ? " (no similarity matrix)" : "");
+	else if (o->has_min_score)
+		info("Score graph: pairs that score at least %d%s", o->min_score, o->edges_only ? " (no similarity matrix)" : "");
+	if (o->linkage)
+		info("Single-linkage tree%s", o->linkage_only ? " (no similarity matrix)" : "");
+	if (o->clusters_q >= 0)
+		info("Clusters: connected components of the pairs that score at least the %g quantile of the scores", o->quantiles[o->clusters_q]);
+	else if (o->has_clusters)
+		info("Clusters: connected components of the pairs that score at least %d", o->clusters_at);
+	if (o->nquant)
+		info("Score quantiles: %d, selected on the device", o->nquant);
+	if (o->normalize)
+		info("Normalization: %s, in parts per million (the similarity matrix stays raw)", o->norm_name);
+	if (o->identity)
+		info("Percent identity over %s, in parts per million (the similarity matrix stays raw)", o->pid_name);
+}
 
-	if (o.linkage)
-		info("Single-linkage tree%s", o.linkage_only ? " (no similarity matrix)" : "");
-	if (o.clusters_q >= 0)
-		info("Clusters: connected components of the pairs that score at least the %g quantile of the scores", o.quantiles[o.clusters_q]);
-	else if (o.has_clusters)
-		info("Clusters: connected components of the pairs that score at least %d", o.clusters_at);
-	if (o.nquant)
-		info("Score quantiles: %d, selected on the device", o.nquant);
-	if (o.normalize)
-		info("Normalization: %s, in parts per million (the similarity matrix stays raw)", o.norm_name);
-
-	if (o.identity)
-		info("Percent identity over %s, in parts per million (the similarity matrix stays raw)", o.pid_name);
-
-	double t_in = 0, t_filter = 0, t_align = 0, t_out = 0, t_select = 0, t_edges = 0, t_linkage = 0, t0;
-	stamp("options parsed");
-	struct sa_host_store store;
-	t0 = now();
-	if (sa_host_load(o.input, sc.lut, sc.gap_pen, o.dsv_column, o.dsv_has_header, &store)) {
-		err("%s", sa_host_error());
-		return 1;
-	}
-	t_in = now() - t0;
+/* the sequences, filtered, and what the selections need once their number is known: the ranks of the fractions, the quantity, room
+ * for the neighbours */
+static bool load_and_filter(struct run *r)
+{
+	struct options *o = &r->o;
+	struct sa_host_store *store = &r->store;
+	double t0 = now();
+	if (sa_host_load(o->input, r->sc.lut, r->sc.gap_pen, o->dsv_column, o->dsv_has_header, store))
+		return failed(sa_host_error());
+	r->t_in = now() - t0;
 	stamp("input loaded");
 	t0 = now();
-	const int32_t before = store.in.num;
-	if (o.filter > 0.0f) { /* similarity relation on the device, greedy keep/drop in sequence order (filter.c:14-89) */
-		uint8_t *keep = malloc((size_t)store.in.num);
-		if (!keep || sa_hip_filter(store.in, o.filter, keep) < 0) {
-			err("%s", keep ? sa_last_error() : "Out of memory during sequence filtering");
-			return 1;
-		}
-		if (sa_host_compact(&store, keep) < 0) {
-			err("%s", sa_host_error());
-			return 1;
-		}
+	const int32_t before = store->in.num;
+	if (o->filter > 0.0f) { /* similarity relation on the device, greedy keep/drop in sequence order (filter.c:14-89) */
+		uint8_t *keep = malloc((size_t)store->in.num);
+		if (!keep || sa_hip_filter(store->in, o->filter, keep) < 0)
+			return failed(keep ? sa_last_error() : "Out of memory during sequence filtering");
+		if (sa_host_compact(store, keep) < 0)
+			return failed(sa_host_error());
 		free(keep);
 	}
-	t_filter = now() - t0;
-	if (o.filter > 0.0f)
-		info("Filtered out %d sequences", before - store.in.num);
-	info("Loaded %d sequences", store.in.num);
-	info("Average sequence length: %.2f", (double)store.blob_bytes / (double)store.in.num - 1.0);
+	r->t_filter = now() - t0;
+	if (o->filter > 0.0f)
+		info("Filtered out %d sequences", before - store->in.num);
+	info("Loaded %d sequences", store->in.num);
+	info("Average sequence length: %.2f", (double)store->blob_bytes / (double)store->in.num - 1.0);
+	r->n = (size_t)store->in.num;
+	r->npairs = (long long)r->n * ((long long)r->n - 1) / 2;
 
-	if (o.neighbors && (long long)o.neighbors > (long long)store.in.num - 1) {
-		err("Neighbor count %d exceeds the %d other sequences", o.neighbors, store.in.num - 1);
-		fprintf(stderr, "Use %s -h, --help for usage information\n", argv[0]);
-		return 1;
+	if (o->neighbors && (long long)o->neighbors > (long long)store->in.num - 1) {
+		err("Neighbor count %d exceeds the %d other sequences", o->neighbors, store->in.num - 1);
+		fprintf(stderr, "Use %s -h, --help for usage information\n", r->argv0);
+		return false;
 	}
-	/* the ranks of the fractions: P is known now.  One select call answers all of them (q_done), where the matrix is */
-	int64_t q_ranks[SA_HIP_SELECT_MAX], q_below[SA_HIP_SELECT_MAX];
-	int32_t q_values[SA_HIP_SELECT_MAX];
-	bool q_done = false, q_second_pass = false;
-	double t_quant = 0;
-	for (int t = 0; t < o.nquant; t++) {
-		q_ranks[t] = sa_score_rank((int64_t)store.in.num * ((int64_t)store.in.num - 1) / 2, o.quantiles[t]);
-		if (q_ranks[t] < 0) {
-			err("Score quantiles need at least two sequences");
-			return 1;
-		}
+	for (int t = 0; t < o->nquant; t++) { /* the ranks of the fractions: P is known now */
+		r->qt.ranks[t] = sa_score_rank((int64_t)r->npairs, o->quantiles[t]);
+		if (r->qt.ranks[t] < 0)
+			return failed("Score quantiles need at least two sequences");
 	}
-	int32_t *nb_index = NULL, *nb_score = NULL;
-	bool nb_done = false, nb_second_pass = false;
-	sa_edges *edges = NULL;
-	bool eg_second_pass = false;
-	sa_linkage *tree = NULL;
-	bool lk_second_pass = false;
-	int lk_rounds = 0;
-	/* --normalize: every selection below goes the normalised way -- the tile job through sa_zjob_normalize, the rest through the
-	 * *_norm calls, which with norm == NULL are their namesakes */
-	struct sa_norm norm_spec = { o.norm_source, o.norm_rule, NULL };
-	const struct sa_norm *norm = NULL;
-	double t_norm = 0;
-	if (o.normalize) {
-		norm_spec.denominators = malloc(sizeof(int32_t) * (size_t)store.in.num);
-		if (!norm_spec.denominators) {
-			err("Out of memory allocating normalization denominators");
-			return 1;
-		}
-		norm = &norm_spec;
+	/* --normalize: every selection goes the normalised way -- the tile job through sa_zjob_normalize, the rest through the *_norm
+	 * calls; --identity: the same, through sa_zjob_identity and the *_pid calls */
+	r->norm_spec = (struct sa_norm){ o->norm_source, o->norm_rule, NULL };
+	if (o->normalize) {
+		r->norm_spec.denominators = malloc(sizeof(int32_t) * r->n);
+		if (!r->norm_spec.denominators)
+			return failed("Out of memory allocating normalization denominators");
+		r->q.norm = &r->norm_spec;
 	}
-	/* --identity: the same, through sa_zjob_identity and the *_pid calls */
-	const int32_t *pid = o.identity ? &o.pid_denom : NULL;
-	double t_pid = 0;
-	if (o.neighbors) {
-		nb_index = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
-		nb_score = malloc(sizeof(int32_t) * (size_t)store.in.num * (size_t)o.neighbors);
-		if (!nb_index || !nb_score) {
-			err("Out of memory allocating neighbor data");
-			return 1;
-		}
+	r->q.pid = o->identity ? &o->pid_denom : NULL;
+	if (o->neighbors) {
+		r->nb.index = malloc(sizeof(int32_t) * r->n * (size_t)o->neighbors);
+		r->nb.score = malloc(sizeof(int32_t) * r->n * (size_t)o->neighbors);
+		if (!r->nb.index || !r->nb.score)
+			return failed("Out of memory allocating neighbor data");
 	}
+	return true;
+}
 
-	/* output_load (src/io/output.c:35-55): a full matrix that exceeds 3/4 of the available RAM goes to temporary
-	 * file storage and is stored triangular; so is one the device(s) cannot hold */
-	const size_t n = (size_t)store.in.num;
-	struct sa_output out = { NULL, NULL, n, false };
-	bool pinned = false;
+/* Where the matrix goes.  output_load (src/io/output.c:35-55): a full matrix that exceeds 3/4 of the available RAM goes to temporary
+ * file storage and is stored triangular; so is one the device(s) cannot hold */
+static bool plan_output(struct run *r)
+{
+	const struct options *o = &r->o;
+	const size_t n = r->n;
+	r->out = (struct sa_output){ NULL, NULL, n, false };
 	/* -z on a chunked dataset: the tiles are deflated on the device, from the packed scores where they were computed
 	 * (include/seqalign_hip.h: sa_hip_tiles_begin / sa_zjob_next) -- no host matrix at all.  libhdf5's filter in the
 	 * one writing thread (what flush_hdf5 leaves to H5Dwrite, src/io/format/hdf5.c:148-194) takes 41 CPU-minutes for config 5.
 	 * SA_HOST_CPU_DEFLATE=1 keeps zlib at exactly the level asked for (all cores, sa_host_write_hdf5). */
-	const long long npairs = (long long)n * ((long long)n - 1) / 2;
-	const size_t zchunk = sa_host_hdf5_chunk_dim(n);
-	const bool no_matrix = o.neighbors_only || o.edges_only || o.linkage_only; /* the matrix never leaves the device */
-	bool device_deflate = !o.no_write && !no_matrix && n > 256 && !getenv("SA_HOST_MATRIX") &&
-			      (o.compression > 0 ? !getenv("SA_HOST_CPU_DEFLATE") && !getenv("SA_HOST_SERIAL_DEFLATE")
-						 /* without -z the same walk returns the tiles as they are: H5Dwrite_chunk instead of H5Dwrite's
-						  * gather of every tile out of N-wide rows.  On several devices the plain path stays with sa_hip_align
-						  * (tiles dealt by DP work, RCCL all-gather: the whole matrix on every device and in host memory);
-						  * with -z the walk itself runs on all of them (sa_hip_tiles_begin: block b -> device b mod n) */
-						 : sa_hip_device_count() == 1);
-	if (device_deflate) {
+	r->zchunk = sa_host_hdf5_chunk_dim(n);
+	r->no_matrix = o->neighbors_only || o->edges_only || o->linkage_only; /* the matrix never leaves the device */
+	r->device_deflate = !o->no_write && !r->no_matrix && n > 256 && !getenv("SA_HOST_MATRIX") &&
+			    (o->compression > 0 ? !getenv("SA_HOST_CPU_DEFLATE") && !getenv("SA_HOST_SERIAL_DEFLATE")
+						/* without -z the same walk returns the tiles as they are: H5Dwrite_chunk instead of H5Dwrite's
+						 * gather of every tile out of N-wide rows.  On several devices the plain path stays with sa_hip_align
+						 * (tiles dealt by DP work, RCCL all-gather: the whole matrix on every device and in host memory);
+						 * with -z the walk itself runs on all of them (sa_hip_tiles_begin: block b -> device b mod n) */
+						: sa_hip_device_count() == 1);
+	if (r->device_deflate) {
 		/* the packed scores + one tile row: raw, or raw + worst-case slots and streams (1 + 2 x 2.02 x the row's raw bytes); the
 		 * pair parse (-z 7..9) keeps two more bytes per element: what its match finder leaves for the encoder */
-		const size_t row_raw = ((n + zchunk - 1) / zchunk) * zchunk * zchunk * sizeof(int32_t);
-		device_deflate = sa_hip_memory(sizeof(int32_t) * (size_t)npairs + (o.compression ? 6 : 1) * row_raw +
-					       (o.compression >= SA_HIP_Z_PAIR_LEVEL ? row_raw / 2 : 0));
+		const size_t row_raw = ((n + r->zchunk - 1) / r->zchunk) * r->zchunk * r->zchunk * sizeof(int32_t);
+		r->device_deflate = sa_hip_memory(sizeof(int32_t) * (size_t)r->npairs + (o->compression ? 6 : 1) * row_raw +
+						  (o->compression >= SA_HIP_Z_PAIR_LEVEL ? row_raw / 2 : 0));
 		stamp("device memory probed (runtime up)");
 	}
-	if (!o.no_write && !device_deflate && !no_matrix) {
-		const size_t full_bytes = sizeof(int32_t) * n * n;
-		const bool tmpf = sa_host_matrix_needs_file(n);
-		out.triangular = tmpf || !sa_hip_memory(full_bytes);
-		stamp("device memory probed (runtime up)");
-		info("Similarity Matrix dimensions: %zu x %zu%s", n, n, out.triangular ? " (stored triangular)" : "");
-		if (tmpf)
-			info("Similarity Matrix size exceeds memory limits, creating temporary file storage");
-		t0 = now();
-		out.matrix = sa_host_matrix_alloc(n, out.triangular, tmpf);
-		if (!out.matrix) {
-			err("%s", sa_host_error());
-			return 1;
-		}
-		stamp("matrix allocated");
-		/* page-lock it for the device->host copies while it is being set up (a file-backed matrix is larger than
-		 * RAM by definition and stays pageable: the library stages those copies) */
-		if (!tmpf) {
-			const size_t bytes = sizeof(int32_t) * (out.triangular ? n * (n - 1) / 2 : n * n);
-			/* (the library's own rule, sa_ctx_align_host: never lock more than half of what is available -- a
-			 * registration of 70 % of free RAM thrashes or meets the OOM killer instead of failing cleanly) */
-			const size_t avail = sa_host_available_memory();
-			pinned = bytes && (!avail || bytes <= avail / 2) && sa_hip_host_register(out.matrix, bytes) == 0;
-		}
-		t_out += now() - t0;
-		stamp("matrix page-locked");
+	if (o->no_write || r->device_deflate || r->no_matrix)
+		return true;
+	const bool tmpf = sa_host_matrix_needs_file(n);
+	r->out.triangular = tmpf || !sa_hip_memory(sizeof(int32_t) * n * n);
+	stamp("device memory probed (runtime up)");
+	info("Similarity Matrix dimensions: %zu x %zu%s", n, n, r->out.triangular ? " (stored triangular)" : "");
+	if (tmpf)
+		info("Similarity Matrix size exceeds memory limits, creating temporary file storage");
+	const double t0 = now();
+	r->out.matrix = sa_host_matrix_alloc(n, r->out.triangular, tmpf);
+	if (!r->out.matrix)
+		return failed(sa_host_error());
+	stamp("matrix allocated");
+	/* page-lock it for the device->host copies while it is being set up (a file-backed matrix is larger than
+	 * RAM by definition and stays pageable: the library stages those copies) */
+	if (!tmpf) {
+		const size_t bytes = sizeof(int32_t) * (r->out.triangular ? n * (n - 1) / 2 : n * n);
+		/* (the library's own rule, sa_ctx_align_host: never lock more than half of what is available -- a
+		 * registration of 70 % of free RAM thrashes or meets the OOM killer instead of failing cleanly) */
+		const size_t avail = sa_host_available_memory();
+		r->pinned = bytes && (!avail || bytes <= avail / 2) && sa_hip_host_register(r->out.matrix, bytes) == 0;
 	}
+	r->t_out += now() - t0;
+	stamp("matrix page-locked");
+	return true;
+}
 
-	const long long pairs = npairs;
-	info("Performing %lld pairwise alignments", pairs);
+/* what a finished tile job answered from its matrix, and what it left to the second passes, under -V */
+static void job_says(bool got, const char *what, const char *how)
+{
+	if (got)
+		verb("%s %s from the device's finished matrix (no second alignment)", what, how);
+	else
+		verb("%s: %s", what, sa_last_error());
+}
+
+/* The tile job: the alignment runs on the device while the finished tiles are written: the tiles whose larger tile index is b
+ * need exactly column block b (include/seqalign_hip.h: sa_hip_tiles_begin).  The reference's phases (src/main.c:31-34,
+ * bench_align / bench_io) overlap here: "Alignment" is the device's alignment time, "Output" the rest of the wall time of
+ * this section.  The finished matrix is still on the device afterwards: what the job can answer from it is not aligned twice, what
+ * it cannot (a message under -V) is left to the second passes. */
+static bool run_tile_job(struct run *r)
+{
+	struct options *o = &r->o;
+	info("Similarity Matrix dimensions: %zu x %zu (%s on the device, tile by tile)", r->n, r->n, o->compression ? "deflated" : "tiled");
+	double t0 = now();
+	sa_zjob *job = sa_hip_tiles_begin(r->store.in, &r->sc, r->zchunk, (int)o->compression);
+	if (!job)
+		return failed(sa_last_error());
+	r->t_setup = now() - t0;
+	stamp("sa_hip_tiles_begin returned");
+	t0 = now();
+	struct tile_feed feed = { job, sa_zjob_tiles_per_row(job), r->show_progress };
+	if (sa_host_write_hdf5_streams(o->output, &r->store, o->compression, next_tiles, &feed)) {
+		err("%s (%s)", sa_host_error(), sa_last_error());
+		return false;
+	}
+	finish_progress(r);
+	r->t_align = sa_zjob_align_seconds(job);
+	const double section = now() - t0;
+	r->t_out += section > r->t_align ? section - r->t_align : 0.0;
+	double enc_ms = 0, copy_ms = 0;
+	uint64_t raw = 0, outb = 0;
+	sa_zjob_stats(job, &enc_ms, &copy_ms, &raw, &outb);
+	verb("%s on the device: %.2f GB -> %.2f GB (%.2f : 1); the writer waited %.0f ms for the encoder, %.0f ms for gather + copy",
+	     o->compression ? "Deflated" : "Tiled", (double)raw / 1e9, (double)outb / 1e9, outb ? (double)raw / (double)outb : 0.0, enc_ms,
+	     copy_ms);
+	/* --normalize / --identity: every tile is written, raw; the device's matrix is rewritten in place for what is selected from it.
+	 * A job that cannot (the matrix dealt over several jobs) answers nothing below */
+	bool job_answers = true;
+	if (r->q.norm || r->q.pid) {
+		job_answers = (r->q.norm ? sa_zjob_normalize(job, r->q.norm) : sa_zjob_identity(job, *r->q.pid)) == 0;
+		if (!job_answers)
+			verb("%s: %s", r->q.norm ? "Normalization" : "Identity", sa_last_error());
+		else
+			verb("%s in place on the device (the tiles written are raw)", r->q.norm ? "Scores normalised" : "Percent identity");
+		r->t_quantity = job_answers ? last_quantity_seconds(r->q) : 0;
+	}
+	if (o->neighbors && job_answers) {
+		r->nb.done = sa_zjob_neighbors(job, o->neighbors, r->nb.index, r->nb.score) == 0;
+		r->nb.seconds = sa_hip_last_neighbors_seconds();
+		job_says(r->nb.done, "Neighbors", "selected");
+	}
+	if (o->nquant && job_answers) { /* first: the cut of what follows */
+		const bool got = sa_zjob_select(job, r->qt.ranks, o->nquant, r->qt.values, r->qt.below) == 0;
+		if (got)
+			quantiles_answered(r);
+		job_says(got, "Score quantiles", "selected");
+	}
+	if (o->has_min_score && (o->min_q < 0 || r->qt.done) && job_answers)
+		job_says(take_edges(r, sa_zjob_edges(job, o->min_score)), "Score graph", "built");
+	if (o->linkage && job_answers)
+		job_says(take_tree(r, sa_zjob_linkage(job)), "Single-linkage tree", "built");
+	sa_zjob_destroy(job);
+	stamp("HDF5 written");
+	return true;
+}
+
+/* --linkage-only, --edges-only, --neighbors-only: no host matrix, no tiles, no matrix transfer: align into device memory, select
+ * there, copy back the selection (12 (N - 1) bytes, 8 N + 8 E bytes, 2 N K ints).  Set-up is the call less its two device times. */
+static bool run_only(struct run *r)
+{
+	const struct options *o = &r->o;
+	if (o->linkage_only)
+		info("Similarity Matrix stays on the device: the single-linkage tree is built there");
+	else if (o->edges_only && o->min_q >= 0)
+		info("Similarity Matrix stays on the device: the cut and the pairs at or above it are selected there");
+	else if (o->edges_only)
+		info("Similarity Matrix stays on the device: the pairs that score at least %d are selected there", o->min_score);
+	else
+		info("Similarity Matrix stays on the device: %d neighbors per sequence are selected there", o->neighbors);
+	const double t0 = now();
+	bool got = true;
+	if (o->neighbors_only) {
+		got = r->nb.done = sel_neighbors(r->store.in, &r->sc, o->neighbors, r->nb.index, r->nb.score, r->q);
+	} else if (o->nquant) { /* with the graph or the tree from one alignment where that serves; further fractions of a graph in a pass of their own */
+		const enum q_call served = answer_quantiles(r, o->linkage_only);
+		if (served == Q_FAILED)
+			return false;
+		r->qt.second_pass = served == Q_SELECT;
+	}
+	if (got && o->edges_only && !r->eg.edges)
+		got = take_edges(r, sel_edges(r->store.in, &r->sc, o->min_score, r->q));
+	if (got && o->linkage_only && !r->lk.tree)
+		got = take_tree(r, sel_linkage(r->store.in, &r->sc, r->q));
+	if (!got)
+		return failed(sa_last_error());
+	const double call = now() - t0;
+	stamp(o->linkage_only ? "sa_hip_linkage returned" : o->edges_only ? "sa_hip_edges returned" : "sa_hip_neighbors returned");
+	finish_progress(r);
+	r->t_align = sa_hip_last_align_seconds();
+	const double t_sel = o->linkage_only ? r->lk.seconds : o->edges_only ? r->eg.seconds : (r->nb.seconds = sa_hip_last_neighbors_seconds());
+	r->t_setup = call > r->t_align + t_sel ? call - r->t_align - t_sel : 0.0;
+	return true;
+}
+
+/* the matrix into host memory, then the file from there */
+static bool run_host_matrix(struct run *r)
+{
+	const double t0 = now();
+	if (!sa_hip_align(r->store.in, r->out, &r->sc))
+		return failed(sa_last_error());
+	r->t_align = now() - t0;
+	stamp("sa_hip_align returned");
+	finish_progress(r);
+	/* the reference times the launch/copy loop only (bench_align_start..end inside cuda_align,
+	 * src/interface/seqalign_cuda.c:182,292): device set-up and uploads are not part of "Alignment" */
+	r->t_setup = r->t_align - sa_hip_last_align_seconds();
+	r->t_align = sa_hip_last_align_seconds();
+	r->schedule = sa_hip_last_align_path();
+	return WRITE_OUT(r, sa_host_write_hdf5(r->o.output, &r->store, r->out.matrix, r->out.triangular, r->o.compression), "HDF5 written");
+}
+
+/* ---- the second passes: what the first pass left unanswered.  Its paths other than a tile job on one device (N <= 256, SA_HOST_*
+ * switches, -W, several devices, a walk dealt over several jobs) no longer hold the matrix on one device: a second pass aligns into
+ * device memory again and selects there ---- */
+#define SECOND_PASS "%s: a second alignment pass into device memory (the matrix of the first is not on one device any more)"
+
+static bool passed(bool got, bool *second_pass, const char *what)
+{
+	if (!got)
+		return failed(sa_last_error());
+	*second_pass = true;
+	stamp(what);
+	return true;
+}
+
+static bool pass_neighbors(struct run *r)
+{
+	if (!r->o.neighbors || r->nb.done)
+		return true;
+	verb(SECOND_PASS, "Neighbors");
+	r->nb.done = sel_neighbors(r->store.in, &r->sc, r->o.neighbors, r->nb.index, r->nb.score, r->q);
+	r->nb.seconds = sa_hip_last_neighbors_seconds();
+	return passed(r->nb.done, &r->nb.second_pass, "sa_hip_neighbors returned");
+}
+
+/* the fractions -- with what the cut feeds where one alignment can serve both, by itself otherwise -- and what they make of the cuts */
+static bool pass_quantiles(struct run *r)
+{
+	struct options *o = &r->o;
+	if (o->nquant && !r->qt.done) {
+		verb(SECOND_PASS, "Score quantiles");
+		const enum q_call call = answer_quantiles(r, true);
+		if (call == Q_FAILED)
+			return false;
+		r->qt.second_pass = true;
+		r->eg.second_pass = call == Q_EDGES_AT_RANK;
+		r->lk.second_pass = call == Q_LINKAGE_WITH_RANKS;
+		stamp("score quantiles returned");
+	}
+	if (!r->qt.done)
+		return true;
+	if (o->min_q >= 0) {
+		o->min_score = r->qt.values[o->min_q];
+		info("Score graph: T = %d, the score at rank %lld of %lld: %lld pairs score at least T", o->min_score, (long long)r->qt.ranks[o->min_q],
+		     r->npairs, r->npairs - (long long)r->qt.below[o->min_q]);
+	}
+	if (o->clusters_q >= 0) {
+		o->clusters_at = r->qt.values[o->clusters_q];
+		info("Clusters: T = %d, the score at rank %lld of %lld: %lld pairs score at least T", o->clusters_at,
+		     (long long)r->qt.ranks[o->clusters_q], r->npairs, r->npairs - (long long)r->qt.below[o->clusters_q]);
+	}
+	return true;
+}
+
+static bool pass_edges(struct run *r)
+{
+	if (!r->o.has_min_score || r->eg.edges)
+		return true;
+	verb(SECOND_PASS, "Score graph");
+	return passed(take_edges(r, sel_edges(r->store.in, &r->sc, r->o.min_score, r->q)), &r->eg.second_pass, "sa_hip_edges returned");
+}
+
+static bool pass_linkage(struct run *r)
+{
+	if (!r->o.linkage || r->lk.tree)
+		return true;
+	verb(SECOND_PASS, "Single-linkage tree");
+	return passed(take_tree(r, sel_linkage(r->store.in, &r->sc, r->q)), &r->lk.second_pass, "sa_hip_linkage returned");
+}
+
+/* ---- writing the selections: each into the file the matrix made, or into one of its own when there is no matrix ---- */
+static bool write_neighbors(struct run *r)
+{
+	return !r->o.neighbors || WRITE_OUT(r, sa_host_write_neighbors(r->o.output, &r->store, r->o.neighbors, r->nb.index, r->nb.score,
+									 r->o.neighbors_only ? 1 : 0), "neighbors written");
+}
+
+/* --alignments: the N x K pairs (r, neighbor_indices[r][t]), row-major: traced back on the device (include/seqalign_hip.h), written */
+static bool trace_alignments(struct run *r)
+{
+	const struct options *o = &r->o;
+	if (!o->alignments)
+		return true;
+	const size_t np = r->n * (size_t)o->neighbors;
+	int32_t *pa = malloc(sizeof(int32_t) * np);
+	if (!pa)
+		return failed("Out of memory allocating alignment pairs");
+	for (size_t t = 0; t < np; t++)
+		pa[t] = (int32_t)(t / (size_t)o->neighbors);
+	sa_alns *alns = sa_hip_alignments(r->store.in, &r->sc, pa, r->nb.index, (int64_t)np);
+	free(pa);
+	if (!alns)
+		return failed(sa_last_error());
+	r->trace.seconds = sa_hip_last_alignments_seconds(); /* (reported by itself: the Alignment phase stays the all-vs-all scores) */
+	stamp("sa_hip_alignments returned");
+	int64_t runs = 0;
+	const uint32_t *cigar = sa_alns_cigar(alns, &runs);
+	r->trace.runs = (long long)runs;
+	if (!WRITE_OUT(r, sa_host_write_alignments(o->output, &r->store, o->neighbors, sa_alns_records(alns), cigar, runs), "alignments written"))
+		return false;
+	sa_alns_destroy(alns);
+	return true;
+}
+
+static bool write_edges(struct run *r)
+{
+	if (!r->eg.edges)
+		return true;
+	int64_t count = 0;
+	const int32_t *index = sa_edges_index(r->eg.edges, &count);
+	r->eg.count = (long long)count;
+	if (!WRITE_OUT(r, sa_host_write_edges(r->o.output, &r->store, sa_edges_offsets(r->eg.edges, NULL), index, sa_edges_score(r->eg.edges),
+					      r->o.edges_only ? 1 : 0), "edges written"))
+		return false;
+	sa_edges_destroy(r->eg.edges);
+	return true;
+}
+
+/* the tree, and with --clusters the labels it gives at the cut */
+static bool write_linkage(struct run *r)
+{
+	const struct options *o = &r->o;
+	if (!r->lk.tree)
+		return true;
+	const int32_t *pairs = sa_linkage_pairs(r->lk.tree, &r->lk.merges), *score = sa_linkage_score(r->lk.tree);
+	int32_t *labels = NULL;
+	if (o->has_clusters) {
+		labels = malloc(sizeof(int32_t) * r->n);
+		if (!labels)
+			return failed("Out of memory allocating cluster labels");
+		r->lk.clusters = sa_linkage_labels(pairs, score, r->store.in.num, o->clusters_at, labels);
+		if (r->lk.clusters < 0)
+			return failed(sa_last_error());
+		verb("Clusters: %d at score >= %d", r->lk.clusters, o->clusters_at);
+	}
+	if (!WRITE_OUT(r, sa_host_write_linkage(o->output, &r->store, pairs, score, labels, o->linkage_only ? 1 : 0), "linkage written"))
+		return false;
+	free(labels);
+	sa_linkage_destroy(r->lk.tree);
+	return true;
+}
+
+/* last: whatever was asked for beside them has made the file by now.  The quantiles, then what says which quantity all of it was
+ * selected from: the denominators came back with whichever call normalised */
+static bool write_quantiles_and_quantity(struct run *r)
+{
+	const struct options *o = &r->o;
+	if (r->qt.done && !WRITE_OUT(r, sa_host_write_quantiles(o->output, &r->store, o->quantiles, r->qt.values, r->qt.below, o->nquant,
+								 o->min_q >= 0 ? &o->min_score : NULL, o->clusters_q >= 0 ? &o->clusters_at : NULL, 0),
+				     "quantiles written"))
+		return false;
+	if (r->q.norm && !WRITE_OUT(r, sa_host_write_normalization(o->output, &r->store, r->norm_spec.denominators, r->norm_spec.source,
+								    r->norm_spec.rule), "normalization written"))
+		return false;
+	if (r->q.pid && !WRITE_OUT(r, sa_host_write_identity(o->output, *r->q.pid), "identity rule written"))
+		return false;
+	if ((r->q.pid || r->q.norm) && r->t_quantity == 0)
+		r->t_quantity = last_quantity_seconds(r->q); /* (the *_pid / *_norm calls: the last of them) */
+	return true;
+}
+
+/* -B: src/util/benchmark.c:50-64 */
+static void report(const struct run *r)
+{
+	const struct options *o = &r->o;
+	static const char AGAIN[] = ", after a second alignment pass into device memory";
+	printf("Timing breakdown:\n  Input: %.3f sec\n  Filter: %.3f sec\n  Alignment: %.3f sec\n  Output: %.3f sec\n"
+	       "  Total: %.3f sec\n",
+	       r->t_in, r->t_filter, r->t_align, r->t_out, r->t_in + r->t_filter + r->t_align + r->t_out);
+	printf("  (device set-up and upload, outside the phases as in the reference: %.3f sec)\n", r->t_setup);
+	printf("  (schedule: %s)\n", r->device_deflate ? (o->compression ? "column blocks into device memory, their tiles deflated on the device and written meanwhile"
+									  : "column blocks into device memory, their tiles delivered as HDF5 chunks meanwhile")
+			       : o->linkage_only ? "the packed matrix stays in device memory, only the single-linkage tree comes back"
+			       : o->edges_only ? "the packed matrix stays in device memory, only the edges come back"
+			       : o->neighbors_only ? "the packed matrix stays in device memory, only the neighbors come back"
+			       : r->schedule == 2 ? "tiles dealt over the devices, RCCL all-gather of the dense shares, placement on every device"
+						  : "every device delivers its slice of the packed index straight into the host matrix");
+	if (o->neighbors)
+		printf("  (neighbor selection on the device, K = %d: %.6f sec%s)\n", o->neighbors, r->nb.seconds, r->nb.second_pass ? AGAIN : "");
+	if (o->alignments)
+		printf("  (alignments of the %lld neighbor pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
+		       (long long)r->store.in.num * o->neighbors, r->trace.seconds, r->trace.runs);
+	if (o->nquant)
+		printf("  (Score quantiles on the device: %d ranks of %lld pairs, %.6f sec%s)\n", o->nquant, r->npairs, r->qt.seconds,
+		       r->qt.second_pass ? AGAIN : "");
+	if (o->has_min_score)
+		printf("  (score graph on the device, min score = %d: %lld edges, %.6f sec%s)\n", o->min_score, r->eg.count, r->eg.seconds,
+		       r->eg.second_pass ? AGAIN : "");
+	if (o->linkage)
+		printf("  (single-linkage tree on the device: %d merges, %d rounds, %.6f sec%s)\n", r->lk.merges, r->lk.rounds, r->lk.seconds,
+		       r->lk.second_pass ? AGAIN : "");
+	if (o->has_clusters)
+		printf("  (clusters at score >= %d: %d)\n", o->clusters_at, r->lk.clusters);
+	if (r->q.norm)
+		printf("  (Normalisation on the device, %s: denominators + sweep over %lld pairs, %.6f sec)\n", o->norm_name, r->npairs, r->t_quantity);
+	if (r->q.pid)
+		printf("  (Percent identity on the device, over %s: one sweep over %lld pairs, %.6f sec)\n", o->pid_name, r->npairs, r->t_quantity);
+	printf("Alignments per second: %.2f\n", r->t_align > 0 ? (double)r->npairs / r->t_align : 0.0);
+}
+
+static void release(struct run *r)
+{
+	if (r->pinned)
+		sa_hip_host_unregister(r->out.matrix);
+	sa_host_matrix_free(r->out.matrix, r->n, r->out.triangular);
+	free(r->nb.index);
+	free(r->nb.score);
+	free(r->norm_spec.denominators);
+	sa_host_store_free(&r->store);
+	stamp("released");
+}
+
+int main(int argc, char **argv)
+{
+	t_process0 = now();
+	static struct run run;
+	struct run *r = &run;
+	r->argv0 = argv[0];
+	const int rc = set_up(argc, argv, r);
+	if (rc)
+		return rc == 2 ? 0 : 1;
+	banner(r);
+	stamp("options parsed");
+	if (!load_and_filter(r) || !plan_output(r))
+		return 1;
+
+	info("Performing %lld pairwise alignments", r->npairs);
 	/* progress (ppercent / pproportc in the reference's launch loop, src/interface/seqalign_cuda.c:181,286-289,293) */
-	const bool show_progress = !no_progress && !quiet;
-	if (show_progress) {
+	r->show_progress = !no_progress && !quiet;
+	if (r->show_progress) {
 		sa_hip_set_progress(progress_line, NULL);
 		progress_line(0.0, NULL);
 	}
 	verb("Devices: %d (%s)", sa_hip_device_count(), sa_hip_device_name(0) ? sa_hip_device_name(0) : "none");
-	double t_setup = 0;
-	int schedule = 0;
-	if (device_deflate) {
-		info("Similarity Matrix dimensions: %zu x %zu (%s on the device, tile by tile)", n, n, o.compression ? "deflated" : "tiled");
-		/* the alignment runs on the device while the finished tiles are written: the tiles whose larger tile index is b
-		 * need exactly column block b (include/seqalign_hip.h: sa_hip_tiles_begin).  The reference's phases (src/main.c:31-34,
-		 * bench_align / bench_io) overlap here: "Alignment" below is the device's alignment time, "Output" the rest of
-		 * the wall time of this section. */
-		t0 = now();
-		sa_zjob *job = sa_hip_tiles_begin(store.in, &sc, zchunk, (int)o.compression);
-		if (!job) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		t_setup = now() - t0;
-		stamp("sa_hip_tiles_begin returned");
-		t0 = now();
-		struct tile_feed feed = { job, sa_zjob_tiles_per_row(job), show_progress };
-		if (sa_host_write_hdf5_streams(o.output, &store, o.compression, next_tiles, &feed)) {
-			err("%s (%s)", sa_host_error(), sa_last_error());
-			return 1;
-		}
-		if (show_progress) {
-			progress_line(1.0, NULL);
-			fputc('\n', stderr);
-			sa_hip_set_progress(NULL, NULL);
-		}
-		t_align = sa_zjob_align_seconds(job);
-		const double section = now() - t0;
-		t_out += section > t_align ? section - t_align : 0.0;
-		double enc_ms = 0, copy_ms = 0;
-		uint64_t raw = 0, outb = 0;
-		sa_zjob_stats(job, &enc_ms, &copy_ms, &raw, &outb);
-		verb("%s on the device: %.2f GB -> %.2f GB (%.2f : 1); the writer waited %.0f ms for the encoder, %.0f ms for gather + copy",
-		     o.compression ? "Deflated" : "Tiled", (double)raw / 1e9, (double)outb / 1e9, outb ? (double)raw / (double)outb : 0.0, enc_ms,
-		     copy_ms);
-		/* --normalize: every tile is written, raw; the device's matrix is normalised in place for what is selected from it.  A job
-		 * that cannot (the matrix dealt over several jobs) answers nothing below: the second passes take over */
-		bool job_answers = true;
-		if (norm) {
-			if (sa_zjob_normalize(job, norm) == 0) {
-				t_norm = sa_hip_last_normalize_seconds();
-				verb("Scores normalised in place on the device (the tiles written are raw)");
-			} else {
-				job_answers = false;
-				verb("Normalization: %s", sa_last_error());
-			}
-		}
-		/* --identity: likewise; the device's matrix is overwritten with percent identity by one more sweep */
-		if (pid) {
-			if (sa_zjob_identity(job, *pid) == 0) {
-				t_pid = sa_hip_last_identity_seconds();
-				verb("Percent identity in place on the device (the tiles written are raw)");
-			} else {
-				job_answers = false;
-				verb("Identity: %s", sa_last_error());
-			}
-		}
-		/* the finished matrix is still on the device: the neighbours come from it, nothing is aligned twice */
-		if (o.neighbors && job_answers) {
-			if (sa_zjob_neighbors(job, o.neighbors, nb_index, nb_score) == 0) {
-				nb_done = true;
-				t_select = sa_hip_last_neighbors_seconds();
-				verb("Neighbors selected from the device's finished matrix (no second alignment)");
-			} else {
-				verb("Neighbors: %s", sa_last_error());
-			}
-		}
-		if (o.nquant && job_answers) { /* first: the cut of what follows */
-			if (sa_zjob_select(job, q_ranks, o.nquant, q_values, q_below) == 0) {
-				q_done = true;
-				t_quant = sa_hip_last_select_seconds();
-				if (o.min_q >= 0)
-					o.min_score = q_values[o.min_q];
-				verb("Score quantiles selected from the device's finished matrix (no second alignment)");
-			} else {
-				verb("Score quantiles: %s", sa_last_error());
-			}
-		}
-		if (o.has_min_score && (o.min_q < 0 || q_done) && job_answers) {
-			edges = sa_zjob_edges(job, o.min_score);
-			if (edges) {
-				t_edges = sa_hip_last_edges_seconds();
-				verb("Score graph built from the device's finished matrix (no second alignment)");
-			} else {
-				verb("Score graph: %s", sa_last_error());
-			}
-		}
-		if (o.linkage && job_answers) {
-			tree = sa_zjob_linkage(job);
-			if (tree) {
-				t_linkage = sa_hip_last_linkage_seconds();
-				lk_rounds = sa_hip_last_linkage_rounds();
-				verb("Single-linkage tree built from the device's finished matrix (no second alignment)");
-			} else {
-				verb("Single-linkage tree: %s", sa_last_error());
-			}
-		}
-		sa_zjob_destroy(job);
-		stamp("HDF5 written");
-	} else if (o.linkage_only) {
-		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the tree there, copy back 12 (N - 1) bytes */
-		info("Similarity Matrix stays on the device: the single-linkage tree is built there");
-		t0 = now();
-		tree = o.nquant ? sel_linkage_with_ranks(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm, pid) : sel_linkage(store.in, &sc, norm, pid);
-		if (!tree) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		if (o.nquant) {
-			q_done = true;
-			t_quant = sa_hip_last_select_seconds();
-		}
-		const double call = now() - t0;
-		stamp("sa_hip_linkage returned");
-		if (show_progress) {
-			progress_line(1.0, NULL);
-			fputc('\n', stderr);
-			sa_hip_set_progress(NULL, NULL);
-		}
-		t_align = sa_hip_last_align_seconds();
-		t_linkage = sa_hip_last_linkage_seconds();
-		lk_rounds = sa_hip_last_linkage_rounds();
-		t_setup = call > t_align + t_linkage ? call - t_align - t_linkage : 0.0;
-	} else if (o.edges_only) {
-		/* no host matrix, no tiles, no matrix transfer: align into device memory, build the graph there, copy back 8 N + 8 E bytes */
-		if (o.min_q >= 0)
-			info("Similarity Matrix stays on the device: the cut and the pairs at or above it are selected there");
-		else
-			info("Similarity Matrix stays on the device: the pairs that score at least %d are selected there", o.min_score);
-		t0 = now();
-		if (o.min_q >= 0 && o.nquant == 1) { /* one alignment: the cut and the graph from the same device matrix */
-			edges = sel_edges_at_rank(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0], norm, pid);
-		} else {
-			if (o.nquant) { /* further fractions: one select call for all of them, in a pass of its own */
-				if (!sel_select(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm, pid)) {
-					err("%s", sa_last_error());
-					return 1;
-				}
-				q_second_pass = true;
-			}
-			if (o.min_q >= 0)
-				o.min_score = q_values[o.min_q];
-			edges = sel_edges(store.in, &sc, o.min_score, norm, pid);
-		}
-		if (edges && o.nquant) {
-			q_done = true;
-			t_quant = sa_hip_last_select_seconds();
-			if (o.min_q >= 0)
-				o.min_score = q_values[o.min_q];
-		}
-		if (!edges) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		const double call = now() - t0;
-		stamp("sa_hip_edges returned");
-		if (show_progress) {
-			progress_line(1.0, NULL);
-			fputc('\n', stderr);
-			sa_hip_set_progress(NULL, NULL);
-		}
-		t_align = sa_hip_last_align_seconds();
-		t_edges = sa_hip_last_edges_seconds();
-		t_setup = call > t_align + t_edges ? call - t_align - t_edges : 0.0;
-	} else if (o.neighbors_only) {
-		/* no host matrix, no tiles, no matrix transfer: align into device memory, select there, copy back 2 N K ints */
-		info("Similarity Matrix stays on the device: %d neighbors per sequence are selected there", o.neighbors);
-		t0 = now();
-		if (!sel_neighbors(store.in, &sc, o.neighbors, nb_index, nb_score, norm, pid)) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		const double call = now() - t0;
-		stamp("sa_hip_neighbors returned");
-		if (show_progress) {
-			progress_line(1.0, NULL);
-			fputc('\n', stderr);
-			sa_hip_set_progress(NULL, NULL);
-		}
-		nb_done = true;
-		t_align = sa_hip_last_align_seconds();
-		t_select = sa_hip_last_neighbors_seconds();
-		t_setup = call > t_align + t_select ? call - t_align - t_select : 0.0;
-	} else {
-		t0 = now();
-		if (!sa_hip_align(store.in, out, &sc)) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		t_align = now() - t0;
-		stamp("sa_hip_align returned");
-		if (show_progress) {
-			progress_line(1.0, NULL);
-			fputc('\n', stderr);
-			sa_hip_set_progress(NULL, NULL);
-		}
-		/* the reference times the launch/copy loop only (bench_align_start..end inside cuda_align,
-		 * src/interface/seqalign_cuda.c:182,292): device set-up and uploads are not part of "Alignment" */
-		t_setup = t_align - sa_hip_last_align_seconds();
-		t_align = sa_hip_last_align_seconds();
-		schedule = sa_hip_last_align_path();
-
-		if (!o.no_write) {
-			t0 = now();
-			if (sa_host_write_hdf5(o.output, &store, out.matrix, out.triangular, o.compression)) {
-				err("%s", sa_host_error());
-				return 1;
-			}
-			t_out += now() - t0;
-			stamp("HDF5 written");
-		}
-	}
-	if (o.neighbors && !nb_done) {
-		/* the other paths (N <= 256, SA_HOST_* switches, -W, several devices, a walk dealt over several jobs) no longer hold
-		 * the matrix on one device: a second pass aligns into device memory again and selects there */
-		verb("Neighbors: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		if (!sel_neighbors(store.in, &sc, o.neighbors, nb_index, nb_score, norm, pid)) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		nb_done = nb_second_pass = true;
-		t_select = sa_hip_last_neighbors_seconds();
-		stamp("sa_hip_neighbors returned");
-	}
-	if (o.neighbors && !o.no_write) {
-		t0 = now();
-		if (sa_host_write_neighbors(o.output, &store, o.neighbors, nb_index, nb_score, o.neighbors_only ? 1 : 0)) {
-			err("%s", sa_host_error());
-			return 1;
-		}
-		t_out += now() - t0;
-		stamp("neighbors written");
-	}
-	double t_trace = 0.0;
-	long long trace_runs = 0;
-	if (o.alignments) {
-		/* the N x K pairs (r, neighbor_indices[r][t]), row-major: traced back on the device (include/seqalign_hip.h) */
-		const size_t np = (size_t)store.in.num * (size_t)o.neighbors;
-		int32_t *pa = malloc(sizeof(int32_t) * np);
-		if (!pa) {
-			err("Out of memory allocating alignment pairs");
-			return 1;
-		}
-		for (size_t t = 0; t < np; t++)
-			pa[t] = (int32_t)(t / (size_t)o.neighbors);
-		sa_alns *alns = sa_hip_alignments(store.in, &sc, pa, nb_index, (int64_t)np);
-		free(pa);
-		if (!alns) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		t_trace = sa_hip_last_alignments_seconds(); /* (reported by itself: the Alignment phase stays the all-vs-all scores) */
-		stamp("sa_hip_alignments returned");
-		int64_t runs = 0;
-		const uint32_t *cigar = sa_alns_cigar(alns, &runs);
-		trace_runs = (long long)runs;
-		if (!o.no_write) {
-			t0 = now();
-			if (sa_host_write_alignments(o.output, &store, o.neighbors, sa_alns_records(alns), cigar, runs)) {
-				err("%s", sa_host_error());
-				return 1;
-			}
-			t_out += now() - t0;
-			stamp("alignments written");
-		}
-		sa_alns_destroy(alns);
-	}
-	if (o.nquant && !q_done) {
-		/* as for the neighbours: the matrix of the first pass is not on one device any more.  With what the cut feeds where one
-		 * alignment can serve both, by itself otherwise */
-		verb("Score quantiles: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		bool got;
-		if (o.min_q >= 0 && o.nquant == 1 && !edges) {
-			edges = sel_edges_at_rank(store.in, &sc, q_ranks[0], &q_values[0], &q_below[0], norm, pid);
-			got = edges != NULL;
-			if (got) {
-				eg_second_pass = true;
-				t_edges = sa_hip_last_edges_seconds();
-			}
-		} else if (o.linkage && !tree) {
-			tree = sel_linkage_with_ranks(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm, pid);
-			got = tree != NULL;
-			if (got) {
-				lk_second_pass = true;
-				t_linkage = sa_hip_last_linkage_seconds();
-				lk_rounds = sa_hip_last_linkage_rounds();
-			}
-		} else {
-			got = sel_select(store.in, &sc, q_ranks, o.nquant, q_values, q_below, norm, pid);
-		}
-		if (!got) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		q_done = q_second_pass = true;
-		t_quant = sa_hip_last_select_seconds();
-		stamp("score quantiles returned");
-	}
-	if (q_done) {
-		if (o.min_q >= 0) {
-			o.min_score = q_values[o.min_q];
-			info("Score graph: T = %d, the score at rank %lld of %lld: %lld pairs score at least T", o.min_score, (long long)q_ranks[o.min_q],
-			     npairs, npairs - (long long)q_below[o.min_q]);
-		}
-		if (o.clusters_q >= 0) {
-			o.clusters_at = q_values[o.clusters_q];
-			info("Clusters: T = %d, the score at rank %lld of %lld: %lld pairs score at least T", o.clusters_at,
-			     (long long)q_ranks[o.clusters_q], npairs, npairs - (long long)q_below[o.clusters_q]);
-		}
-	}
-	if (o.has_min_score && !edges) {
-		/* as for the neighbours: the matrix of the first pass is not on one device any more */
-		verb("Score graph: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		edges = sel_edges(store.in, &sc, o.min_score, norm, pid);
-		if (!edges) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		eg_second_pass = true;
-		t_edges = sa_hip_last_edges_seconds();
-		stamp("sa_hip_edges returned");
-	}
-	long long edge_count = 0;
-	if (edges) {
-		int64_t count = 0;
-		const int32_t *eg_index = sa_edges_index(edges, &count);
-		edge_count = (long long)count;
-		if (!o.no_write) {
-			t0 = now();
-			if (sa_host_write_edges(o.output, &store, sa_edges_offsets(edges, NULL), eg_index, sa_edges_score(edges), o.edges_only ? 1 : 0)) {
-				err("%s", sa_host_error());
-				return 1;
-			}
-			t_out += now() - t0;
-			stamp("edges written");
-		}
-		sa_edges_destroy(edges);
-	}
-	if (o.linkage && !tree) {
-		/* as for the neighbours: the matrix of the first pass is not on one device any more */
-		verb("Single-linkage tree: a second alignment pass into device memory (the matrix of the first is not on one device any more)");
-		tree = sel_linkage(store.in, &sc, norm, pid);
-		if (!tree) {
-			err("%s", sa_last_error());
-			return 1;
-		}
-		lk_second_pass = true;
-		t_linkage = sa_hip_last_linkage_seconds();
-		lk_rounds = sa_hip_last_linkage_rounds();
-		stamp("sa_hip_linkage returned");
-	}
-	int32_t lk_merges = 0, cluster_count = 0;
-	if (tree) {
-		const int32_t *lk_pairs = sa_linkage_pairs(tree, &lk_merges), *lk_score = sa_linkage_score(tree);
-		int32_t *labels = NULL;
-		if (o.has_clusters) {
-			labels = malloc(sizeof(int32_t) * (size_t)store.in.num);
-			if (!labels) {
-				err("Out of memory allocating cluster labels");
-				return 1;
-			}
-			cluster_count = sa_linkage_labels(lk_pairs, lk_score, store.in.num, o.clusters_at, labels);
-			if (cluster_count < 0) {
-				err("%s", sa_last_error());
-				return 1;
-			}
-			verb("Clusters: %d at score >= %d", cluster_count, o.clusters_at);
-		}
-		if (!o.no_write) {
-			t0 = now();
-			if (sa_host_write_linkage(o.output, &store, lk_pairs, lk_score, labels, o.linkage_only ? 1 : 0)) {
-				err("%s", sa_host_error());
-				return 1;
-			}
-			t_out += now() - t0;
-			stamp("linkage written");
-		}
-		free(labels);
-		sa_linkage_destroy(tree);
-	}
-	if (q_done && !o.no_write) {
-		/* last: whatever was asked for beside the quantiles has made the file by now */
-		t0 = now();
-		if (sa_host_write_quantiles(o.output, &store, o.quantiles, q_values, q_below, o.nquant, o.min_q >= 0 ? &o.min_score : NULL,
-					    o.clusters_q >= 0 ? &o.clusters_at : NULL, 0)) {
-			err("%s", sa_host_error());
-			return 1;
-		}
-		t_out += now() - t0;
-		stamp("quantiles written");
-	}
-	if (norm && !o.no_write) {
-		/* last, like the quantiles: the denominators came back with whichever call normalised */
-		t0 = now();
-		if (sa_host_write_normalization(o.output, &store, norm_spec.denominators, norm_spec.source, norm_spec.rule)) {
-			err("%s", sa_host_error());
-			return 1;
-		}
-		t_out += now() - t0;
-		stamp("normalization written");
-	}
-	if (pid && !o.no_write) {
-		t0 = now();
-		if (sa_host_write_identity(o.output, *pid)) {
-			err("%s", sa_host_error());
-			return 1;
-		}
-		t_out += now() - t0;
-		stamp("identity rule written");
-	}
-	if (pid && t_pid == 0)
-		t_pid = sa_hip_last_identity_seconds(); /* (the *_pid calls: the last of them) */
-	if (norm && t_norm == 0)
-		t_norm = sa_hip_last_normalize_seconds(); /* (the *_norm calls: the last of them) */
-	if (o.benchmark) { /* -B: src/util/benchmark.c:50-64 */
-		const double total = t_in + t_filter + t_align + t_out;
-		printf("Timing breakdown:\n  Input: %.3f sec\n  Filter: %.3f sec\n  Alignment: %.3f sec\n  Output: %.3f sec\n"
-		       "  Total: %.3f sec\n",
-		       t_in, t_filter, t_align, t_out, total);
-		printf("  (device set-up and upload, outside the phases as in the reference: %.3f sec)\n", t_setup);
-		printf("  (schedule: %s)\n", device_deflate ? (o.compression ? "column blocks into device memory, their tiles deflated on the device and written meanwhile"
-								       : "column blocks into device memory, their tiles delivered as HDF5 chunks meanwhile")
-				       : o.linkage_only ? "the packed matrix stays in device memory, only the single-linkage tree comes back"
-				       : o.edges_only ? "the packed matrix stays in device memory, only the edges come back"
-				       : o.neighbors_only ? "the packed matrix stays in device memory, only the neighbors come back"
-			       : schedule == 2
-					       ? "tiles dealt over the devices, RCCL all-gather of the dense shares, placement on every device"
-					       : "every device delivers its slice of the packed index straight into the host matrix");
-		if (o.neighbors)
-			printf("  (neighbor selection on the device, K = %d: %.6f sec%s)\n", o.neighbors, t_select,
-			       nb_second_pass ? ", after a second alignment pass into device memory" : "");
-		if (o.alignments)
-			printf("  (alignments of the %lld neighbor pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
-			       (long long)store.in.num * o.neighbors, t_trace, trace_runs);
-		if (o.nquant)
-			printf("  (Score quantiles on the device: %d ranks of %lld pairs, %.6f sec%s)\n", o.nquant, npairs, t_quant,
-			       q_second_pass ? ", after a second alignment pass into device memory" : "");
-		if (o.has_min_score)
-			printf("  (score graph on the device, min score = %d: %lld edges, %.6f sec%s)\n", o.min_score, edge_count, t_edges,
-			       eg_second_pass ? ", after a second alignment pass into device memory" : "");
-		if (o.linkage)
-			printf("  (single-linkage tree on the device: %d merges, %d rounds, %.6f sec%s)\n", lk_merges, lk_rounds, t_linkage,
-			       lk_second_pass ? ", after a second alignment pass into device memory" : "");
-		if (o.has_clusters)
-			printf("  (clusters at score >= %d: %d)\n", o.clusters_at, cluster_count);
-		if (norm)
-			printf("  (Normalisation on the device, %s: denominators + sweep over %lld pairs, %.6f sec)\n", o.norm_name, npairs, t_norm);
-		if (pid)
-			printf("  (Percent identity on the device, over %s: one sweep over %lld pairs, %.6f sec)\n", o.pid_name, npairs, t_pid);
-		printf("Alignments per second: %.2f\n", t_align > 0 ? (double)pairs / t_align : 0.0);
-	}
-	if (pinned)
-		sa_hip_host_unregister(out.matrix);
-	sa_host_matrix_free(out.matrix, n, out.triangular);
-	free(nb_index);
-	free(nb_score);
-	free(norm_spec.denominators);
-	sa_host_store_free(&store);
-	stamp("released");
+	if (!(r->device_deflate ? run_tile_job(r) : r->no_matrix ? run_only(r) : run_host_matrix(r)))
+		return 1;
+	if (!pass_neighbors(r) || !write_neighbors(r) || !trace_alignments(r) || !pass_quantiles(r) || !pass_edges(r) || !write_edges(r) ||
+	    !pass_linkage(r) || !write_linkage(r) || !write_quantiles_and_quantity(r))
+		return 1;
+	if (r->o.benchmark)
+		report(r);
+	release(r);
 	/* everything is written and closed: leave without the runtime's teardown (device reset, queue and signal
 	 * destruction: ~0.15 s that nothing waits for) */
 	fflush(NULL);

@@ -618,30 +618,35 @@ def last_identity_seconds() -> float:
     return float(load_library().sa_hip_last_identity_seconds())
 
 
+def _quantity(base: str, norm: Optional[Norm], pid: Optional[int], n: int):
+    """What a selection reads -- the scores (`base`), the scores normalised under `norm` (`base`_norm) or percent identity in
+    parts per million under the denominator `pid` (`base`_pid): the library function, its trailing arguments, and what the
+    result gains behind the plain tuple: the n denominators for a norm, nothing otherwise"""
+    lib = load_library()
+    if pid is not None:
+        if norm is not None:
+            raise AlignError("norm and pid exclude each other")
+        return getattr(lib, base + "_pid"), (_denom(pid),), ()
+    if norm is not None:
+        cn, den = norm._as_c(n)
+        return getattr(lib, base + "_norm"), (C.byref(cn),), (den[:n],)
+    return getattr(lib, base), (), ()
+
+
 def hip_neighbors(store: SequenceStore, scoring: Scoring, k: int, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_neighbors: the k best partners of every sequence, selected on the device -- (index, score), two (N, k) int32
     arrays; row r lists the c != r by score descending, then index ascending.  The matrix never leaves the device.
-    1 <= k <= min(N - 1, NEIGHBORS_MAX)."""
+    1 <= k <= min(N - 1, NEIGHBORS_MAX).  With a norm: (index, score, denominators)."""
     n, k = store.num, int(k)
     if not -2**31 <= k < 2**31:
         raise AlignError(f"k = {k} is not an int32")
     rows = max(n, 1) * max(min(k, NEIGHBORS_MAX), 1)
     index, score = np.empty(rows, np.int32), np.empty(rows, np.int32)
     sc = scoring._as_c()
-    if pid is not None:  # percent identity under the denominator `pid`, in parts per million: (index, score)
-        if norm is not None:
-            raise AlignError("norm and pid exclude each other")
-        if not load_library().sa_hip_neighbors_pid(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data, _denom(pid)):
-            raise AlignError(_err())
-        return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k)
-    if norm is not None:  # normalised scores: (index, score, denominators)
-        cn, den = norm._as_c(n)
-        if not load_library().sa_hip_neighbors_norm(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data, C.byref(cn)):
-            raise AlignError(_err())
-        return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k), den[:n]
-    if not load_library().sa_hip_neighbors(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data):
+    fn, tail, den = _quantity("sa_hip_neighbors", norm, pid, n)
+    if not fn(store._as_c(), C.byref(sc), k, index.ctypes.data, score.ctypes.data, *tail):
         raise AlignError(_err())
-    return index[:n * k].reshape(n, k), score[:n * k].reshape(n, k)
+    return (index[:n * k].reshape(n, k), score[:n * k].reshape(n, k)) + den
 
 
 def last_neighbors_seconds() -> float:
@@ -677,15 +682,11 @@ def _take_edges(lib, handle) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
 def hip_edges(store: SequenceStore, scoring: Scoring, min_score: int, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_edges: every pair that scores at least min_score, as the symmetric adjacency in CSR form, built on the device --
     (offsets int64[N + 1], index int32[E], score int32[E]); row r's columns are index[offsets[r]:offsets[r + 1]], ascending.
-    The matrix never leaves the device.  Any int32 threshold is valid."""
-    lib = load_library()
-    sc = scoring._as_c()
-    if pid is not None:  # min_score in parts per million of identity
-        return _take_edges(lib, lib.sa_hip_edges_pid(store._as_c(), C.byref(sc), _min_score(min_score), _denom(pid)))
-    if norm is not None:  # min_score in parts per million: (offsets, index, score, denominators)
-        cn, den = norm._as_c(store.num)
-        return _take_edges(lib, lib.sa_hip_edges_norm(store._as_c(), C.byref(sc), _min_score(min_score), C.byref(cn))) + (den[:store.num],)
-    return _take_edges(lib, lib.sa_hip_edges(store._as_c(), C.byref(sc), _min_score(min_score)))
+    The matrix never leaves the device.  Any int32 threshold is valid; with a norm or a pid it is in parts per million, and
+    with a norm the result is (offsets, index, score, denominators)."""
+    sc, t = scoring._as_c(), _min_score(min_score)
+    fn, tail, den = _quantity("sa_hip_edges", norm, pid, store.num)
+    return _take_edges(load_library(), fn(store._as_c(), C.byref(sc), t, *tail)) + den
 
 
 def last_edges_seconds() -> float:
@@ -712,15 +713,10 @@ def _take_linkage(lib, handle) -> tuple[np.ndarray, np.ndarray]:
 def hip_linkage(store: SequenceStore, scoring: Scoring, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_linkage: the single-linkage tree (the maximum spanning tree of the score matrix), built on the device --
     (pairs int32 (N - 1, 2) with lo < hi, score int32 (N - 1,)), sorted by score descending, then packed index ascending: the
-    order in which single linkage joins clusters.  The matrix never leaves the device."""
-    lib = load_library()
+    order in which single linkage joins clusters.  The matrix never leaves the device.  With a norm: (pairs, score, denominators)."""
     sc = scoring._as_c()
-    if pid is not None:  # the tree of percent identity
-        return _take_linkage(lib, lib.sa_hip_linkage_pid(store._as_c(), C.byref(sc), _denom(pid)))
-    if norm is not None:  # the tree of the normalised scores: (pairs, score, denominators)
-        cn, den = norm._as_c(store.num)
-        return _take_linkage(lib, lib.sa_hip_linkage_norm(store._as_c(), C.byref(sc), C.byref(cn))) + (den[:store.num],)
-    return _take_linkage(lib, lib.sa_hip_linkage(store._as_c(), C.byref(sc)))
+    fn, tail, den = _quantity("sa_hip_linkage", norm, pid, store.num)
+    return _take_linkage(load_library(), fn(store._as_c(), C.byref(sc), *tail)) + den
 
 
 def linkage_scratch_bytes(n: int) -> int:
@@ -782,64 +778,37 @@ def select_scratch_bytes(m: int) -> int:
 def hip_select(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_select: for each rank k (up to 16, any order, duplicates allowed) into the ascending order of the N (N - 1) / 2
     pair scores, (values int32 (m,), below int64 (m,)): the k-th smallest score and the number of pairs strictly below it,
-    selected on the device.  The matrix never leaves the device."""
-    lib = load_library()
+    selected on the device.  The matrix never leaves the device.  With a norm: (values, below, denominators)."""
     sc = scoring._as_c()
     r = _ranks(ranks)
     value, below = _select_room(len(r))
-    if pid is not None:  # order statistics of percent identity
-        if not lib.sa_hip_select_pid(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data, _denom(pid)):
-            raise AlignError(_err())
-        return value[:len(r)].copy(), below[:len(r)].copy()
-    if norm is not None:  # order statistics of the normalised scores: (values, below, denominators)
-        cn, den = norm._as_c(store.num)
-        if not lib.sa_hip_select_norm(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data, C.byref(cn)):
-            raise AlignError(_err())
-        return value[:len(r)].copy(), below[:len(r)].copy(), den[:store.num]
-    if not lib.sa_hip_select(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data):
+    fn, tail, den = _quantity("sa_hip_select", norm, pid, store.num)
+    if not fn(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data, *tail):
         raise AlignError(_err())
-    return value[:len(r)].copy(), below[:len(r)].copy()
+    return (value[:len(r)].copy(), below[:len(r)].copy()) + den
 
 
 def hip_edges_at_rank(store: SequenceStore, scoring: Scoring, rank: int, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_edges_at_rank: one alignment, the score T at `rank` and the score graph at T from the same device matrix --
-    (offsets, index, score) as hip_edges returns them, then min_score = T and below = the pairs under T; E = 2 (P - below)"""
-    lib = load_library()
+    (offsets, index, score) as hip_edges returns them, then min_score = T and below = the pairs under T; E = 2 (P - below).
+    With a norm the denominators follow."""
     sc = scoring._as_c()
     cut, below = C.c_int32(0), C.c_int64(0)
     (rank,) = _ranks([rank])
-    if pid is not None:  # all over percent identity
-        offsets, index, score = _take_edges(lib, lib.sa_hip_edges_at_rank_pid(store._as_c(), C.byref(sc), int(rank), C.byref(cut),
-                                                                              C.byref(below), _denom(pid)))
-        return offsets, index, score, int(cut.value), int(below.value)
-    if norm is not None:  # (offsets, index, score, min_score, below, denominators), all over the normalised scores
-        cn, den = norm._as_c(store.num)
-        offsets, index, score = _take_edges(lib, lib.sa_hip_edges_at_rank_norm(store._as_c(), C.byref(sc), int(rank), C.byref(cut),
-                                                                               C.byref(below), C.byref(cn)))
-        return offsets, index, score, int(cut.value), int(below.value), den[:store.num]
-    offsets, index, score = _take_edges(lib, lib.sa_hip_edges_at_rank(store._as_c(), C.byref(sc), int(rank), C.byref(cut), C.byref(below)))
-    return offsets, index, score, int(cut.value), int(below.value)
+    fn, tail, den = _quantity("sa_hip_edges_at_rank", norm, pid, store.num)
+    edges = _take_edges(load_library(), fn(store._as_c(), C.byref(sc), int(rank), C.byref(cut), C.byref(below), *tail))
+    return edges + (int(cut.value), int(below.value)) + den
 
 
 def hip_linkage_with_ranks(store: SequenceStore, scoring: Scoring, ranks, norm: Optional[Norm] = None, pid: Optional[int] = None):
     """sa_hip_linkage_with_ranks: one alignment, then hip_select's (values, below) for `ranks` and hip_linkage's (pairs, score)
-    from the same device matrix -- (pairs, score, values, below)"""
-    lib = load_library()
+    from the same device matrix -- (pairs, score, values, below); with a norm the denominators follow"""
     sc = scoring._as_c()
     r = _ranks(ranks)
     value, below = _select_room(len(r))
-    if pid is not None:  # all over percent identity
-        pairs, score = _take_linkage(lib, lib.sa_hip_linkage_with_ranks_pid(store._as_c(), C.byref(sc), r.ctypes.data, len(r),
-                                                                             value.ctypes.data, below.ctypes.data, _denom(pid)))
-        return pairs, score, value[:len(r)].copy(), below[:len(r)].copy()
-    if norm is not None:  # (pairs, score, values, below, denominators), all over the normalised scores
-        cn, den = norm._as_c(store.num)
-        pairs, score = _take_linkage(lib, lib.sa_hip_linkage_with_ranks_norm(store._as_c(), C.byref(sc), r.ctypes.data, len(r),
-                                                                              value.ctypes.data, below.ctypes.data, C.byref(cn)))
-        return pairs, score, value[:len(r)].copy(), below[:len(r)].copy(), den[:store.num]
-    pairs, score = _take_linkage(lib, lib.sa_hip_linkage_with_ranks(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data,
-                                                                     below.ctypes.data))
-    return pairs, score, value[:len(r)].copy(), below[:len(r)].copy()
+    fn, tail, den = _quantity("sa_hip_linkage_with_ranks", norm, pid, store.num)
+    tree = _take_linkage(load_library(), fn(store._as_c(), C.byref(sc), r.ctypes.data, len(r), value.ctypes.data, below.ctypes.data, *tail))
+    return tree + (value[:len(r)].copy(), below[:len(r)].copy()) + den
 
 
 def last_select_seconds() -> float:

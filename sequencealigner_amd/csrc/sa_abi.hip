@@ -422,6 +422,15 @@ extern "C" bool sa_hip_align(struct sa_input in, struct sa_output out, const str
 }
 
 /* ---- sa_hip_neighbors, sa_hip_edges: align into device memory, select there, return the selection ------------------------- */
+/* what a selection reads: the scores, the scores normalised under *norm, or percent identity under *denom */
+struct Quantity {
+	const struct sa_norm *norm = nullptr;
+	const int32_t *denom = nullptr;
+	/* the entry point's name in messages (SA_ENTRY); a *_norm call without a norm is its plain namesake and says so */
+	const char *entry(const char *plain, const char *normed, const char *pid) const { return denom ? pid : norm ? normed : plain; }
+};
+#define SA_ENTRY(q, base) (q).entry(base, base "_norm", base "_pid")
+
 /* the whole packed matrix of `in` in the first device's memory, aligned on a stream of its own between two events */
 struct DeviceRun { /* (released whatever way the caller is left) */
 	sa_ctx *ctx = nullptr;
@@ -443,19 +452,19 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 			sa_ctx_destroy(ctx);
 	}
 	/* the alignment is in order on `stream` when this returns true; `who` names the entry point in messages */
-	/* norm != nullptr: denominators + sweep follow the alignment on the stream, in place (sa_normalize.hip), and the stream is
+	/* q.norm != nullptr: denominators + sweep follow the alignment on the stream, in place (sa_normalize.hip), and the stream is
 	 * synchronised once here; what the caller selects next reads normalised scores */
-	/* denom != nullptr, the second way to fill d_packed: the identity sweep (sa_identity.hip) writes pid under *denom for every
+	/* q.denom != nullptr, the second way to fill d_packed: the identity sweep (sa_identity.hip) writes pid under *denom for every
 	 * pair, no score alignment runs, and the stream is synchronised once here; what the caller selects next reads parts per
 	 * million of identity */
 	bool pid_run = false;
-	bool begin(const char *who, struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm = nullptr, const int32_t *denom = nullptr)
+	bool begin(const char *who, struct sa_input in, const struct sa_scoring *sc, Quantity q)
 	{
-		if (norm && !sa_norm_check(who, norm)) /* (before the alignment is launched) */
+		if (q.norm && !sa_norm_check(who, q.norm)) /* (before the alignment is launched) */
 			return false;
-		if (denom && !sa_identity_denom_check(who, *denom)) /* (before a device is looked for) */
+		if (q.denom && !sa_identity_denom_check(who, *q.denom)) /* (before a device is looked for) */
 			return false;
-		pid_run = denom != nullptr;
+		pid_run = q.denom != nullptr;
 		if (sa_hip_device_count() <= 0) {
 			sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
 			return false;
@@ -475,15 +484,13 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 		SA_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), return false);
 		SA_HIP_CHECK(hipEventCreate(&e0), return false);
 		SA_HIP_CHECK(hipEventCreate(&e1), return false);
-		if (denom)
-			return sa_identity_in_place(who, ctx, d_packed, *denom, stream);
+		if (q.denom)
+			return sa_identity_in_place(who, ctx, d_packed, *q.denom, stream);
 		SA_HIP_CHECK(hipEventRecord(e0, stream), return false);
 		if (sa_ctx_align_range(ctx, 0, pairs, d_packed, stream) != 0)
 			return false;
 		SA_HIP_CHECK(hipEventRecord(e1, stream), return false);
-		if (norm && !sa_normalize_in_place(who, ctx, d_packed, norm, stream))
-			return false;
-		return true;
+		return !q.norm || sa_normalize_in_place(who, ctx, d_packed, q.norm, stream);
 	}
 	/* after the stream has been synchronised: the alignment's device time goes to sa_hip_last_align_seconds */
 	bool finish()
@@ -495,18 +502,27 @@ struct DeviceRun { /* (released whatever way the caller is left) */
 		g_last_align_seconds.store((double)ms * 1e-3);
 		return true;
 	}
+	/* a result object handed out only from a run that finished */
+	template <class T> T *finished(T *res, void (*destroy)(T *))
+	{
+		if (res && !finish()) {
+			destroy(res);
+			res = nullptr;
+		}
+		return res;
+	}
 };
 
-static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm, const int32_t *denom = nullptr)
+static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, Quantity q)
 {
-	const char *who = denom ? "sa_hip_neighbors_pid" : norm ? "sa_hip_neighbors_norm" : "sa_hip_neighbors";
+	const char *who = SA_ENTRY(q, "sa_hip_neighbors");
 	if (!sc || !index || !score) {
 		sa_set_error("%s: null argument", who);
 		return false;
 	}
-	if (norm && !sa_norm_check(who, norm))
+	if (q.norm && !sa_norm_check(who, q.norm))
 		return false;
-	if (denom && (!sa_identity_denom_check(who, *denom) || !sa_neighbors_check(who, in.num, k)))
+	if (q.denom && (!sa_identity_denom_check(who, *q.denom) || !sa_neighbors_check(who, in.num, k)))
 		return false;
 	if (sa_hip_device_count() <= 0) {
 		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
@@ -515,7 +531,7 @@ static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int3
 	if (!sa_neighbors_check(who, in.num, k))
 		return false;
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm, denom))
+	if (!run.begin(who, in, sc, q))
 		return false;
 	if (!sa_neighbors_to_host(run.d_packed, in.num, k, index, score, run.stream))
 		return false;
@@ -524,74 +540,64 @@ static bool neighbors_impl(struct sa_input in, const struct sa_scoring *sc, int3
 
 extern "C" bool sa_hip_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score)
 {
-	return sa_guard("sa_hip_neighbors", false, [&] { return neighbors_impl(in, sc, k, index, score, nullptr); });
+	return sa_guard("sa_hip_neighbors", false, [&] { return neighbors_impl(in, sc, k, index, score, Quantity{}); });
 }
 
 extern "C" bool sa_hip_neighbors_norm(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, const struct sa_norm *norm)
 {
-	return sa_guard("sa_hip_neighbors_norm", false, [&] { return neighbors_impl(in, sc, k, index, score, norm); });
+	return sa_guard("sa_hip_neighbors_norm", false, [&] { return neighbors_impl(in, sc, k, index, score, Quantity{ norm }); });
 }
 
-static sa_edges *edges_impl(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm, const int32_t *denom = nullptr)
+static sa_edges *edges_impl(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, Quantity q)
 {
-	const char *who = denom ? "sa_hip_edges_pid" : norm ? "sa_hip_edges_norm" : "sa_hip_edges";
+	const char *who = SA_ENTRY(q, "sa_hip_edges");
 	if (!sc) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
 	}
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm, denom))
+	if (!run.begin(who, in, sc, q))
 		return nullptr;
-	sa_edges *res = sa_edges_to_host(who, run.d_packed, in.num, min_score, run.stream);
-	if (res && !run.finish()) {
-		sa_edges_destroy(res);
-		res = nullptr;
-	}
-	return res;
+	return run.finished(sa_edges_to_host(who, run.d_packed, in.num, min_score, run.stream), sa_edges_destroy);
 }
 
 extern "C" sa_edges *sa_hip_edges(struct sa_input in, const struct sa_scoring *sc, int32_t min_score)
 {
-	return sa_guard("sa_hip_edges", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, nullptr); });
+	return sa_guard("sa_hip_edges", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, Quantity{}); });
 }
 
 extern "C" sa_edges *sa_hip_edges_norm(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, const struct sa_norm *norm)
 {
-	return sa_guard("sa_hip_edges_norm", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, norm); });
+	return sa_guard("sa_hip_edges_norm", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, Quantity{ norm }); });
 }
 
-static sa_linkage *linkage_impl(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm, const int32_t *denom = nullptr)
+static sa_linkage *linkage_impl(struct sa_input in, const struct sa_scoring *sc, Quantity q)
 {
-	const char *who = denom ? "sa_hip_linkage_pid" : norm ? "sa_hip_linkage_norm" : "sa_hip_linkage";
+	const char *who = SA_ENTRY(q, "sa_hip_linkage");
 	if (!sc) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
 	}
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm, denom))
+	if (!run.begin(who, in, sc, q))
 		return nullptr;
-	sa_linkage *res = sa_linkage_to_host(who, run.d_packed, in.num, run.stream);
-	if (res && !run.finish()) {
-		sa_linkage_destroy(res);
-		res = nullptr;
-	}
-	return res;
+	return run.finished(sa_linkage_to_host(who, run.d_packed, in.num, run.stream), sa_linkage_destroy);
 }
 
 extern "C" sa_linkage *sa_hip_linkage(struct sa_input in, const struct sa_scoring *sc)
 {
-	return sa_guard("sa_hip_linkage", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, nullptr); });
+	return sa_guard("sa_hip_linkage", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, Quantity{}); });
 }
 
 extern "C" sa_linkage *sa_hip_linkage_norm(struct sa_input in, const struct sa_scoring *sc, const struct sa_norm *norm)
 {
-	return sa_guard("sa_hip_linkage_norm", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, norm); });
+	return sa_guard("sa_hip_linkage_norm", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, Quantity{ norm }); });
 }
 
 /* ---- order statistics of the matrix, alone and as the cut of what follows them on the same device matrix -------------------- */
-static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below, const struct sa_norm *norm, const int32_t *denom = nullptr)
+static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below, Quantity q)
 {
-	const char *who = denom ? "sa_hip_select_pid" : norm ? "sa_hip_select_norm" : "sa_hip_select";
+	const char *who = SA_ENTRY(q, "sa_hip_select");
 	if (!sc || !ranks || !value || !below) {
 		sa_set_error("%s: null argument", who);
 		return false;
@@ -599,7 +605,7 @@ static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const i
 	if (!sa_select_check(who, in.num, ranks, m)) /* (before the alignment: P follows from in.num) */
 		return false;
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm, denom))
+	if (!run.begin(who, in, sc, q))
 		return false;
 	if (!sa_select_to_host(who, run.d_packed, in.num, ranks, m, value, below, run.stream))
 		return false;
@@ -608,17 +614,17 @@ static bool select_impl(struct sa_input in, const struct sa_scoring *sc, const i
 
 extern "C" bool sa_hip_select(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below)
 {
-	return sa_guard("sa_hip_select", false, [&] { return select_impl(in, sc, ranks, m, value, below, nullptr); });
+	return sa_guard("sa_hip_select", false, [&] { return select_impl(in, sc, ranks, m, value, below, Quantity{}); });
 }
 
 extern "C" bool sa_hip_select_norm(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below, const struct sa_norm *norm)
 {
-	return sa_guard("sa_hip_select_norm", false, [&] { return select_impl(in, sc, ranks, m, value, below, norm); });
+	return sa_guard("sa_hip_select_norm", false, [&] { return select_impl(in, sc, ranks, m, value, below, Quantity{ norm }); });
 }
 
-static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below, const struct sa_norm *norm, const int32_t *denom = nullptr)
+static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below, Quantity q)
 {
-	const char *who = denom ? "sa_hip_edges_at_rank_pid" : norm ? "sa_hip_edges_at_rank_norm" : "sa_hip_edges_at_rank";
+	const char *who = SA_ENTRY(q, "sa_hip_edges_at_rank");
 	if (!sc || !min_score || !below) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
@@ -626,17 +632,13 @@ static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring 
 	if (!sa_select_check(who, in.num, &rank, 1))
 		return nullptr;
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm, denom))
+	if (!run.begin(who, in, sc, q))
 		return nullptr;
 	int32_t cut = 0;
 	int64_t under = 0;
 	if (!sa_select_to_host(who, run.d_packed, in.num, &rank, 1, &cut, &under, run.stream))
 		return nullptr;
-	sa_edges *res = sa_edges_to_host(who, run.d_packed, in.num, cut, run.stream);
-	if (res && !run.finish()) {
-		sa_edges_destroy(res);
-		res = nullptr;
-	}
+	sa_edges *res = run.finished(sa_edges_to_host(who, run.d_packed, in.num, cut, run.stream), sa_edges_destroy);
 	if (res) {
 		*min_score = cut;
 		*below = under;
@@ -646,18 +648,18 @@ static sa_edges *edges_at_rank_impl(struct sa_input in, const struct sa_scoring 
 
 extern "C" sa_edges *sa_hip_edges_at_rank(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below)
 {
-	return sa_guard("sa_hip_edges_at_rank", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, nullptr); });
+	return sa_guard("sa_hip_edges_at_rank", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, Quantity{}); });
 }
 
 extern "C" sa_edges *sa_hip_edges_at_rank_norm(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below, const struct sa_norm *norm)
 {
-	return sa_guard("sa_hip_edges_at_rank_norm", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, norm); });
+	return sa_guard("sa_hip_edges_at_rank_norm", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, Quantity{ norm }); });
 }
 
 static sa_linkage *linkage_with_ranks_impl(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value,
-					   int64_t *below, const struct sa_norm *norm, const int32_t *denom = nullptr)
+					   int64_t *below, Quantity q)
 {
-	const char *who = denom ? "sa_hip_linkage_with_ranks_pid" : norm ? "sa_hip_linkage_with_ranks_norm" : "sa_hip_linkage_with_ranks";
+	const char *who = SA_ENTRY(q, "sa_hip_linkage_with_ranks");
 	if (!sc || !ranks || !value || !below) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
@@ -665,17 +667,13 @@ static sa_linkage *linkage_with_ranks_impl(struct sa_input in, const struct sa_s
 	if (!sa_select_check(who, in.num, ranks, m))
 		return nullptr;
 	DeviceRun run;
-	if (!run.begin(who, in, sc, norm, denom))
+	if (!run.begin(who, in, sc, q))
 		return nullptr;
 	int32_t cut[SA_HIP_SELECT_MAX];
 	int64_t under[SA_HIP_SELECT_MAX];
 	if (!sa_select_to_host(who, run.d_packed, in.num, ranks, m, cut, under, run.stream))
 		return nullptr;
-	sa_linkage *res = sa_linkage_to_host(who, run.d_packed, in.num, run.stream);
-	if (res && !run.finish()) {
-		sa_linkage_destroy(res);
-		res = nullptr;
-	}
+	sa_linkage *res = run.finished(sa_linkage_to_host(who, run.d_packed, in.num, run.stream), sa_linkage_destroy);
 	if (res)
 		for (int32_t t = 0; t < m; t++) {
 			value[t] = cut[t];
@@ -688,49 +686,49 @@ extern "C" sa_linkage *sa_hip_linkage_with_ranks(struct sa_input in, const struc
 						 int32_t *value, int64_t *below)
 {
 	return sa_guard("sa_hip_linkage_with_ranks", (sa_linkage *)nullptr,
-			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, nullptr); });
+			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, Quantity{}); });
 }
 
 extern "C" sa_linkage *sa_hip_linkage_with_ranks_norm(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
 						 int32_t *value, int64_t *below, const struct sa_norm *norm)
 {
 	return sa_guard("sa_hip_linkage_with_ranks_norm", (sa_linkage *)nullptr,
-			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, norm); });
+			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, Quantity{ norm }); });
 }
 
 /* ---- the same selections over percent identity: the identity sweep fills the device triangle (DeviceRun::begin) ---------------- */
 extern "C" bool sa_hip_neighbors_pid(struct sa_input in, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, int32_t denom)
 {
-	return sa_guard("sa_hip_neighbors_pid", false, [&] { return neighbors_impl(in, sc, k, index, score, nullptr, &denom); });
+	return sa_guard("sa_hip_neighbors_pid", false, [&] { return neighbors_impl(in, sc, k, index, score, Quantity{ nullptr, &denom }); });
 }
 
 extern "C" sa_edges *sa_hip_edges_pid(struct sa_input in, const struct sa_scoring *sc, int32_t min_score, int32_t denom)
 {
-	return sa_guard("sa_hip_edges_pid", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, nullptr, &denom); });
+	return sa_guard("sa_hip_edges_pid", (sa_edges *)nullptr, [&] { return edges_impl(in, sc, min_score, Quantity{ nullptr, &denom }); });
 }
 
 extern "C" sa_linkage *sa_hip_linkage_pid(struct sa_input in, const struct sa_scoring *sc, int32_t denom)
 {
-	return sa_guard("sa_hip_linkage_pid", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, nullptr, &denom); });
+	return sa_guard("sa_hip_linkage_pid", (sa_linkage *)nullptr, [&] { return linkage_impl(in, sc, Quantity{ nullptr, &denom }); });
 }
 
 extern "C" bool sa_hip_select_pid(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below,
 				  int32_t denom)
 {
-	return sa_guard("sa_hip_select_pid", false, [&] { return select_impl(in, sc, ranks, m, value, below, nullptr, &denom); });
+	return sa_guard("sa_hip_select_pid", false, [&] { return select_impl(in, sc, ranks, m, value, below, Quantity{ nullptr, &denom }); });
 }
 
 extern "C" sa_edges *sa_hip_edges_at_rank_pid(struct sa_input in, const struct sa_scoring *sc, int64_t rank, int32_t *min_score, int64_t *below,
 					      int32_t denom)
 {
-	return sa_guard("sa_hip_edges_at_rank_pid", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, nullptr, &denom); });
+	return sa_guard("sa_hip_edges_at_rank_pid", (sa_edges *)nullptr, [&] { return edges_at_rank_impl(in, sc, rank, min_score, below, Quantity{ nullptr, &denom }); });
 }
 
 extern "C" sa_linkage *sa_hip_linkage_with_ranks_pid(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m,
 						     int32_t *value, int64_t *below, int32_t denom)
 {
 	return sa_guard("sa_hip_linkage_with_ranks_pid", (sa_linkage *)nullptr,
-			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, nullptr, &denom); });
+			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, Quantity{ nullptr, &denom }); });
 }
 
 extern "C" int sa_hip_last_align_path(void) { return g_last_align_path.load(); }

@@ -736,8 +736,7 @@ struct sa_zjob {
 	bool pairs = false;  /* levels SA_Z_PAIR_LEVEL .. 9: the pair parse */
 	const int32_t *d_packed = nullptr, *d_full = nullptr;
 	int32_t *d_owned = nullptr; /* the packed matrix, when the job made it (sa_hip_tiles_begin) */
-	bool normalized = false;    /* sa_zjob_normalize has rewritten it in place */
-	bool identity = false;      /* sa_zjob_identity has rewritten it in place  */
+	enum { SCORES, NORMALISED, IDENTITY } holds = SCORES; /* what sa_zjob_normalize / sa_zjob_identity have made of it in place */
 	sa_ctx *ctx = nullptr;
 	uint32_t *d_slots = nullptr, *d_seg = nullptr; /* d_seg: bytes, s1, s2, offset, [nc * nseg] each */
 	uint32_t *d_ghist = nullptr, *d_tile_adler = nullptr;
@@ -1257,9 +1256,27 @@ extern "C" double sa_zjob_align_seconds(const sa_zjob *z)
 	});
 }
 
-/* The k best partners of every sequence from the job's packed matrix (sa_neighbors.hip), in order behind whatever the job
- * has on its stream.  Only a job that holds the WHOLE matrix on one device can answer: a walk dealt over several jobs
- * (several devices, SA_HIP_TILES_SPLIT) has every column block on its own device, and a d_full job has no packed index. */
+/* ---- what is selected from a finished job's matrix ---------------------------------------------------------------------------- */
+/* The gate of every sa_zjob_* selection, in the one order all of them refuse.  Only a job that holds the WHOLE matrix on one
+ * device can answer: a walk dealt over several jobs (several devices, SA_HIP_TILES_SPLIT) has every column block on its own device,
+ * and a d_full job has no packed index.  `reader` is what reads the matrix: the selection, the tree, or the sweep -- and a sweep
+ * rewrites the matrix, so the job must own it (`rewrites`).  The calls run in order behind whatever the job has on its stream. */
+static bool zjob_gate(const sa_zjob *z, const char *who, const char *reader, bool rewrites = false)
+{
+	if (!z->peers.empty())
+		sa_set_error("%s: the matrix is dealt over %zu jobs, none of which holds all of it", who, z->peers.size() + 1);
+	else if (!z->d_packed)
+		sa_set_error("%s: the job walks a full matrix; the %s reads the packed index", who, reader);
+	else if (rewrites && (!z->d_owned || !z->ctx || z->d_owned != z->d_packed))
+		sa_set_error("%s: the job walks the caller's matrix, which is const; only a sa_hip_tiles_begin job owns its matrix", who);
+	else if (z->shells && z->next_batch < zjob_batches(z))
+		sa_set_error("%s: the walk is not finished (sa_zjob_next has not returned 0 yet)", who);
+	else
+		return true;
+	return false;
+}
+
+/* The k best partners of every sequence from the job's packed matrix (sa_neighbors.hip). */
 extern "C" int sa_zjob_neighbors(sa_zjob *z, int32_t k, int32_t *index, int32_t *score)
 {
 	return sa_guard("sa_zjob_neighbors", 1, [&]() -> int {
@@ -1267,27 +1284,14 @@ extern "C" int sa_zjob_neighbors(sa_zjob *z, int32_t k, int32_t *index, int32_t 
 			sa_set_error("sa_zjob_neighbors: null argument");
 			return 1;
 		}
-		if (!z->peers.empty()) {
-			sa_set_error("sa_zjob_neighbors: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
-			return 1;
-		}
-		if (!z->d_packed) {
-			sa_set_error("sa_zjob_neighbors: the job walks a full matrix; the selection reads the packed index");
-			return 1;
-		}
-		if (z->shells && z->next_batch < zjob_batches(z)) {
-			sa_set_error("sa_zjob_neighbors: the walk is not finished (sa_zjob_next has not returned 0 yet)");
-			return 1;
-		}
-		if (!sa_neighbors_check("sa_zjob_neighbors", z->num, k))
+		if (!zjob_gate(z, "sa_zjob_neighbors", "selection") || !sa_neighbors_check("sa_zjob_neighbors", z->num, k))
 			return 1;
 		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
 		return sa_neighbors_to_host(z->d_packed, z->num, k, index, score, z->stream) ? 0 : 1;
 	});
 }
 
-/* The score graph of the job's packed matrix (sa_edges.hip), in order behind whatever the job has on its stream.  Refuses what
- * sa_zjob_neighbors refuses, for the same reasons. */
+/* The score graph of the job's packed matrix (sa_edges.hip). */
 extern "C" sa_edges *sa_zjob_edges(sa_zjob *z, int32_t min_score)
 {
 	return sa_guard("sa_zjob_edges", (sa_edges *)nullptr, [&]() -> sa_edges * {
@@ -1295,25 +1299,14 @@ extern "C" sa_edges *sa_zjob_edges(sa_zjob *z, int32_t min_score)
 			sa_set_error("sa_zjob_edges: null argument");
 			return nullptr;
 		}
-		if (!z->peers.empty()) {
-			sa_set_error("sa_zjob_edges: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+		if (!zjob_gate(z, "sa_zjob_edges", "selection"))
 			return nullptr;
-		}
-		if (!z->d_packed) {
-			sa_set_error("sa_zjob_edges: the job walks a full matrix; the selection reads the packed index");
-			return nullptr;
-		}
-		if (z->shells && z->next_batch < zjob_batches(z)) {
-			sa_set_error("sa_zjob_edges: the walk is not finished (sa_zjob_next has not returned 0 yet)");
-			return nullptr;
-		}
 		SA_HIP_CHECK(hipSetDevice(z->device), return nullptr);
 		return sa_edges_to_host("sa_zjob_edges", z->d_packed, z->num, min_score, z->stream);
 	});
 }
 
-/* Order statistics of the job's packed matrix (sa_select.hip), in order behind whatever the job has on its stream.  Refuses what
- * sa_zjob_edges refuses, with the same wording. */
+/* Order statistics of the job's packed matrix (sa_select.hip). */
 extern "C" int sa_zjob_select(sa_zjob *z, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below)
 {
 	return sa_guard("sa_zjob_select", 1, [&] {
@@ -1321,27 +1314,14 @@ extern "C" int sa_zjob_select(sa_zjob *z, const int64_t *ranks, int32_t m, int32
 			sa_set_error("sa_zjob_select: null argument");
 			return 1;
 		}
-		if (!z->peers.empty()) {
-			sa_set_error("sa_zjob_select: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
-			return 1;
-		}
-		if (!z->d_packed) {
-			sa_set_error("sa_zjob_select: the job walks a full matrix; the selection reads the packed index");
-			return 1;
-		}
-		if (z->shells && z->next_batch < zjob_batches(z)) {
-			sa_set_error("sa_zjob_select: the walk is not finished (sa_zjob_next has not returned 0 yet)");
-			return 1;
-		}
-		if (!sa_select_check("sa_zjob_select", z->num, ranks, m))
+		if (!zjob_gate(z, "sa_zjob_select", "selection") || !sa_select_check("sa_zjob_select", z->num, ranks, m))
 			return 1;
 		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
 		return sa_select_to_host("sa_zjob_select", z->d_packed, z->num, ranks, m, value, below, z->stream) ? 0 : 1;
 	});
 }
 
-/* The single-linkage tree of the job's packed matrix (sa_linkage.hip), in order behind whatever the job has on its stream.
- * Refuses what sa_zjob_edges refuses, for the same reasons. */
+/* The single-linkage tree of the job's packed matrix (sa_linkage.hip). */
 extern "C" sa_linkage *sa_zjob_linkage(sa_zjob *z)
 {
 	return sa_guard("sa_zjob_linkage", (sa_linkage *)nullptr, [&]() -> sa_linkage * {
@@ -1349,26 +1329,15 @@ extern "C" sa_linkage *sa_zjob_linkage(sa_zjob *z)
 			sa_set_error("sa_zjob_linkage: null argument");
 			return nullptr;
 		}
-		if (!z->peers.empty()) {
-			sa_set_error("sa_zjob_linkage: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+		if (!zjob_gate(z, "sa_zjob_linkage", "tree"))
 			return nullptr;
-		}
-		if (!z->d_packed) {
-			sa_set_error("sa_zjob_linkage: the job walks a full matrix; the tree reads the packed index");
-			return nullptr;
-		}
-		if (z->shells && z->next_batch < zjob_batches(z)) {
-			sa_set_error("sa_zjob_linkage: the walk is not finished (sa_zjob_next has not returned 0 yet)");
-			return nullptr;
-		}
 		SA_HIP_CHECK(hipSetDevice(z->device), return nullptr);
 		return sa_linkage_to_host("sa_zjob_linkage", z->d_packed, z->num, z->stream);
 	});
 }
 
-/* Normalises the job's own packed matrix in place (sa_normalize.hip), in order behind whatever the job has on its stream: every
- * tile has been encoded and handed out by then, so the tiles stay raw and what is selected afterwards is normalised.  Refuses what
- * sa_zjob_edges refuses, with the same wording, and a matrix that is not the job's to rewrite. */
+/* Normalises the job's own packed matrix in place (sa_normalize.hip): every tile has been encoded and handed out by then, so the
+ * tiles stay raw and what is selected afterwards is normalised.  Refuses a matrix that is not the job's to rewrite, or not scores. */
 extern "C" int sa_zjob_normalize(sa_zjob *z, const struct sa_norm *norm)
 {
 	return sa_guard("sa_zjob_normalize", 1, [&] {
@@ -1376,27 +1345,13 @@ extern "C" int sa_zjob_normalize(sa_zjob *z, const struct sa_norm *norm)
 			sa_set_error("sa_zjob_normalize: null argument");
 			return 1;
 		}
-		if (!z->peers.empty()) {
-			sa_set_error("sa_zjob_normalize: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+		if (!zjob_gate(z, "sa_zjob_normalize", "sweep", true))
 			return 1;
-		}
-		if (!z->d_packed) {
-			sa_set_error("sa_zjob_normalize: the job walks a full matrix; the sweep reads the packed index");
-			return 1;
-		}
-		if (!z->d_owned || !z->ctx || z->d_owned != z->d_packed) {
-			sa_set_error("sa_zjob_normalize: the job walks the caller's matrix, which is const; only a sa_hip_tiles_begin job owns its matrix");
-			return 1;
-		}
-		if (z->shells && z->next_batch < zjob_batches(z)) {
-			sa_set_error("sa_zjob_normalize: the walk is not finished (sa_zjob_next has not returned 0 yet)");
-			return 1;
-		}
-		if (z->normalized) {
+		if (z->holds == sa_zjob::NORMALISED) {
 			sa_set_error("sa_zjob_normalize: the job's matrix has been normalised already");
 			return 1;
 		}
-		if (z->identity) {
+		if (z->holds == sa_zjob::IDENTITY) {
 			sa_set_error("sa_zjob_normalize: the job's matrix holds percent identity (sa_zjob_identity), not scores");
 			return 1;
 		}
@@ -1405,14 +1360,13 @@ extern "C" int sa_zjob_normalize(sa_zjob *z, const struct sa_norm *norm)
 		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
 		if (!sa_normalize_in_place("sa_zjob_normalize", z->ctx, z->d_owned, norm, z->stream))
 			return 1;
-		z->normalized = true;
+		z->holds = sa_zjob::NORMALISED;
 		return 0;
 	});
 }
 
-/* Overwrites the job's own packed matrix with percent identity (sa_identity.hip), in order behind whatever the job has on its
- * stream: every tile has been encoded and handed out by then, so the tiles stay raw and what is selected afterwards reads parts
- * per million of identity.  Refuses what sa_zjob_normalize refuses, with the same wording, and a matrix that is normalised. */
+/* Overwrites the job's own packed matrix with percent identity (sa_identity.hip): as above, the tiles stay raw and what is selected
+ * afterwards reads parts per million of identity.  Refuses what sa_zjob_normalize refuses. */
 extern "C" int sa_zjob_identity(sa_zjob *z, int32_t denom)
 {
 	return sa_guard("sa_zjob_identity", 1, [&] {
@@ -1420,27 +1374,13 @@ extern "C" int sa_zjob_identity(sa_zjob *z, int32_t denom)
 			sa_set_error("sa_zjob_identity: null argument");
 			return 1;
 		}
-		if (!z->peers.empty()) {
-			sa_set_error("sa_zjob_identity: the matrix is dealt over %zu jobs, none of which holds all of it", z->peers.size() + 1);
+		if (!zjob_gate(z, "sa_zjob_identity", "sweep", true))
 			return 1;
-		}
-		if (!z->d_packed) {
-			sa_set_error("sa_zjob_identity: the job walks a full matrix; the sweep reads the packed index");
-			return 1;
-		}
-		if (!z->d_owned || !z->ctx || z->d_owned != z->d_packed) {
-			sa_set_error("sa_zjob_identity: the job walks the caller's matrix, which is const; only a sa_hip_tiles_begin job owns its matrix");
-			return 1;
-		}
-		if (z->shells && z->next_batch < zjob_batches(z)) {
-			sa_set_error("sa_zjob_identity: the walk is not finished (sa_zjob_next has not returned 0 yet)");
-			return 1;
-		}
-		if (z->identity) {
+		if (z->holds == sa_zjob::IDENTITY) {
 			sa_set_error("sa_zjob_identity: the job's matrix has been overwritten with percent identity already");
 			return 1;
 		}
-		if (z->normalized) {
+		if (z->holds == sa_zjob::NORMALISED) {
 			sa_set_error("sa_zjob_identity: the job's matrix has been normalised already");
 			return 1;
 		}
@@ -1449,7 +1389,7 @@ extern "C" int sa_zjob_identity(sa_zjob *z, int32_t denom)
 		SA_HIP_CHECK(hipSetDevice(z->device), return 1);
 		if (!sa_identity_in_place("sa_zjob_identity", z->ctx, z->d_owned, denom, z->stream))
 			return 1;
-		z->identity = true;
+		z->holds = sa_zjob::IDENTITY;
 		return 0;
 	});
 }

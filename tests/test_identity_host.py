@@ -137,8 +137,12 @@ def test_bad_arguments_are_refused_with_nothing_written(sa):
 
 def test_the_binding_refuses_norm_and_pid_together(sa):
     store, scoring = small_case(sa)
-    with pytest.raises(sa.AlignError, match="exclude each other"):
-        sa.hip_neighbors(store, scoring, 2, norm=sa.Norm(), pid=0)
+    both = dict(norm=sa.Norm(), pid=0)
+    for call in (lambda: sa.hip_neighbors(store, scoring, 2, **both), lambda: sa.hip_edges(store, scoring, 0, **both),
+                 lambda: sa.hip_linkage(store, scoring, **both), lambda: sa.hip_select(store, scoring, [0], **both),
+                 lambda: sa.hip_edges_at_rank(store, scoring, 0, **both), lambda: sa.hip_linkage_with_ranks(store, scoring, [0], **both)):
+        with pytest.raises(sa.AlignError, match="norm and pid exclude each other"):
+            call()
     with pytest.raises(sa.AlignError, match="int32"):
         sa.hip_linkage(store, scoring, pid=2**31)
 
