@@ -917,6 +917,18 @@ int sa_host_write_identity(const char *path, int32_t denom)
 	return write_side_sets(path, NULL, 0, false, sets, 2);
 }
 
+/* --linkage-method: /linkage_method 1 I32LE (0 single, SA_AGGLO_COMPLETE, SA_AGGLO_AVERAGE of include/seqalign_hip.h), added to the
+ * finished file at `path`.  The arguments are checked before anything is opened. */
+int sa_host_write_linkage_method(const char *path, int32_t method)
+{
+	if (!path)
+		return fail("Linkage method data missing");
+	if (method != 0 && method != SA_AGGLO_COMPLETE && method != SA_AGGLO_AVERAGE)
+		return fail("Linkage method %d is none of single (0), complete (%d), average (%d)", method, (int)SA_AGGLO_COMPLETE, (int)SA_AGGLO_AVERAGE);
+	const struct side_set sets[1] = { { "/linkage_method", 1, { 1 }, SIDE_I32, &method, false } };
+	return write_side_sets(path, NULL, 0, false, sets, 1);
+}
+
 /* Output whose tiles arrive finished (sa_zjob_tile_row of include/seqalign_hip.h): zlib streams from the device-side encoder
  * when `compression` > 0, the raw tiles when 0.  Same file, dataset, chunk shape and filter pipeline as sa_host_write_hdf5 --
  * the tiles go to H5Dwrite_chunk as they are, tile row after tile row. */

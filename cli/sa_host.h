@@ -109,6 +109,9 @@ int sa_host_write_normalization(const char *path, const struct sa_host_store *s,
 /* --identity: /identity_rule (1 I32LE: the denominator, SA_PID_* of include/seqalign_hip.h) and /identity_scale (1 I32LE:
  * SA_NORM_SCALE), added to the finished file at `path`, whose other datasets stay as they are.  0 on success. */
 int sa_host_write_identity(const char *path, int32_t denom);
+/* --linkage-method: /linkage_method (1 I32LE: 0 single, SA_AGGLO_COMPLETE, SA_AGGLO_AVERAGE of include/seqalign_hip.h), added to
+ * the finished file at `path`, whose other datasets stay as they are.  0 on success. */
+int sa_host_write_linkage_method(const char *path, int32_t method);
 
 #ifdef __cplusplus
 }

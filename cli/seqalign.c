@@ -16,6 +16,8 @@
  *             --linkage  --clusters T  --linkage-only   (the single-linkage tree, built on the device: /linkage_pairs and
  *             /linkage_scores; with --clusters also /cluster_labels, the connected components of the pairs that score at least T;
  *             with --linkage-only no /similarity_matrix at all)
+ *             --linkage-method single|complete|average   (which hierarchy that tree is: complete and average linkage are built on the
+ *             device from the whole matrix; /linkage_method says which, /cluster_labels are then the clusters merged at T or above)
  *             --min-quantile Q  --clusters-quantile Q  --quantiles Q1,Q2,...   (the cut as a fraction of the score distribution:
  *             the score at rank min(P - 1, floor(Q P)) of the P pair scores in ascending order, selected on the device by one
  *             sa_*_select call for all of them: /score_quantiles, /score_quantile_values, /score_quantile_below)
@@ -115,6 +117,10 @@ struct options {
 	int32_t min_score;
 	bool linkage, linkage_only, has_clusters; /* --linkage: the single-linkage tree; --clusters T: its labels at T as well */
 	int32_t clusters_at;
+	/* --linkage-method NAME: which hierarchy the tree is (0 single, SA_AGGLO_COMPLETE, SA_AGGLO_AVERAGE); without the option:
+	 * single, and the output is what it was before the option existed */
+	bool has_method;
+	int32_t method;
 	/* --min-quantile Q, --clusters-quantile Q, --quantiles Q1,...: the fractions as given, one select call for all of them;
 	 * min_q / clusters_q: which of them sets min_score / clusters_at (-1: none) */
 	double quantiles[SA_HIP_SELECT_MAX];
@@ -174,7 +180,17 @@ static void usage(const char *argv0)
 	       "                           component of the pairs that score at least T (any 32-bit integer)\n"
 	       "      --linkage-only       The tree, and no /similarity_matrix: the matrix never leaves the device\n"
 	       "                           (not together with -k or --min-score)\n"
-	       "      --min-quantile Q     --min-score at T = the score at rank min(P - 1, floor(Q P)) of the P pair scores in\n"
+	       "      --linkage-method NAME  The hierarchy of --linkage, --clusters, --clusters-quantile and --linkage-only, and\n"
+	       "                           needs one of them: single (the default) | complete | average.  complete: the similarity\n"
+	       "                           of two clusters is their LOWEST cross pair, so with --clusters T every pair inside a\n"
+	       "                           cluster scores at least T (single linkage promises that of one chain of pairs only);\n"
+	       "                           average: the mean of their cross pairs (UPGMA), exact, /linkage_scores its floor.\n"
+	       "                           Both are built on the device from the whole matrix, in the order the merges are made\n"
+	       "                           (score non-increasing; a cluster is named by its smallest member), and need a square\n"
+	       "                           working matrix beside the scores (4 N^2 bytes, average 8 N^2).  /cluster_labels: the\n"
+	       "                           smallest index in each sequence's cluster after the merges at T or above.  Writes\n"
+	       "                           /linkage_method (0 = single, 1 = complete, 2 = average)\n"
+	       "      --min-quantile Q    --min-score at T = the score at rank min(P - 1, floor(Q P)) of the P pair scores in\n"
 	       "                           ascending order, 0 <= Q <= 1: at least the best (1 - Q) of the pairs (0.99: the best\n"
 	       "                           1 %%).  T is selected on the device and written as /edge_min_score; works with\n"
 	       "                           --edges-only; not together with --min-score\n"
@@ -266,7 +282,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "min-score", 5, true }, { "edges-only", 6, false }, { "linkage", 7, false }, { "clusters", 8, true },
 		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
 		     { "quantiles", 12, true }, { "normalize", 13, true }, { "identity", 14, true },
-		     { NULL, 0, false } };
+		     { "linkage-method", 15, true }, { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -460,6 +476,23 @@ static int parse_args(int argc, char **argv, struct options *o)
 				}
 				break;
 			}
+			case 15: {
+				static const char *const METHODS[] = { "single", "complete", "average" }; /* 0, SA_AGGLO_COMPLETE, SA_AGGLO_AVERAGE */
+				if (o->has_method) {
+					err("Option --linkage-method given twice");
+					return 1;
+				}
+				for (int32_t t = 0; t < 3; t++)
+					if (!strcmp(val, METHODS[t])) {
+						o->has_method = true;
+						o->method = t;
+					}
+				if (!o->has_method) {
+					err("Linkage method must be one of single, complete, average: %s", val);
+					return 1;
+				}
+				break;
+			}
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -522,8 +555,11 @@ static sa_edges *sel_edges(struct sa_input in, const struct sa_scoring *sc, int3
 	return q.pid ? sa_hip_edges_pid(in, sc, min_score, *q.pid) : sa_hip_edges_norm(in, sc, min_score, q.norm);
 }
 
-static sa_linkage *sel_linkage(struct sa_input in, const struct sa_scoring *sc, struct quantity q)
+/* (method: 0 the single-linkage tree, otherwise SA_AGGLO_COMPLETE / SA_AGGLO_AVERAGE -- the same result object) */
+static sa_linkage *sel_linkage(struct sa_input in, const struct sa_scoring *sc, int32_t method, struct quantity q)
 {
+	if (method)
+		return sa_hip_agglomerate(in, sc, method, q.norm, q.pid);
 	return q.pid ? sa_hip_linkage_pid(in, sc, *q.pid) : sa_hip_linkage_norm(in, sc, q.norm);
 }
 
@@ -537,9 +573,11 @@ static sa_edges *sel_edges_at_rank(struct sa_input in, const struct sa_scoring *
 	return q.pid ? sa_hip_edges_at_rank_pid(in, sc, rank, min_score, below, *q.pid) : sa_hip_edges_at_rank_norm(in, sc, rank, min_score, below, q.norm);
 }
 
-static sa_linkage *sel_linkage_with_ranks(struct sa_input in, const struct sa_scoring *sc, const int64_t *ranks, int32_t m, int32_t *value,
-					  int64_t *below, struct quantity q)
+static sa_linkage *sel_linkage_with_ranks(struct sa_input in, const struct sa_scoring *sc, int32_t method, const int64_t *ranks, int32_t m,
+					  int32_t *value, int64_t *below, struct quantity q)
 {
+	if (method)
+		return sa_hip_agglomerate_with_ranks(in, sc, method, q.norm, q.pid, ranks, m, value, below);
 	return q.pid ? sa_hip_linkage_with_ranks_pid(in, sc, ranks, m, value, below, *q.pid)
 		     : sa_hip_linkage_with_ranks_norm(in, sc, ranks, m, value, below, q.norm);
 }
@@ -572,8 +610,22 @@ struct run {
 		double seconds;
 	} qt;
 	struct { sa_edges *edges; bool second_pass; double seconds; long long count; } eg;
-	struct { sa_linkage *tree; bool second_pass; double seconds; int rounds; int32_t merges, clusters; } lk;
+	struct { sa_linkage *tree; bool second_pass; double seconds; int rounds; long long rescans; int32_t merges, clusters; } lk;
 };
+
+/* the tree's name in the messages: "single-linkage", "complete-linkage", "average-linkage"; capital: at the head of a line */
+static const char *tree_name(const struct options *o, bool capital)
+{
+	static const char *const NAMES[3][2] = { { "single-linkage", "Single-linkage" }, { "complete-linkage", "Complete-linkage" },
+						 { "average-linkage", "Average-linkage" } };
+	return NAMES[o->method][capital ? 1 : 0];
+}
+
+static const char *tree_title(const struct options *o)
+{
+	static const char *const TITLES[3] = { "Single-linkage tree", "Complete-linkage tree", "Average-linkage tree" };
+	return TITLES[o->method];
+}
 
 /* the end of a phase that cannot go on: the message (sa_last_error(), sa_host_error(), or the tool's own), and false */
 static bool failed(const char *message)
@@ -614,8 +666,13 @@ static bool take_edges(struct run *r, sa_edges *edges)
 static bool take_tree(struct run *r, sa_linkage *tree)
 {
 	r->lk.tree = tree;
-	r->lk.seconds = sa_hip_last_linkage_seconds();
-	r->lk.rounds = sa_hip_last_linkage_rounds();
+	if (r->o.method) {
+		r->lk.seconds = sa_hip_last_agglomerate_seconds();
+		r->lk.rescans = (long long)sa_hip_last_agglomerate_rescans();
+	} else {
+		r->lk.seconds = sa_hip_last_linkage_seconds();
+		r->lk.rounds = sa_hip_last_linkage_rounds();
+	}
 	return tree != NULL;
 }
 
@@ -646,7 +703,7 @@ static enum q_call answer_quantiles(struct run *r, bool with_tree)
 		got = take_edges(r, sel_edges_at_rank(r->store.in, &r->sc, r->qt.ranks[0], &r->qt.values[0], &r->qt.below[0], r->q));
 	} else if (with_tree && o->linkage && !r->lk.tree) {
 		call = Q_LINKAGE_WITH_RANKS;
-		got = take_tree(r, sel_linkage_with_ranks(r->store.in, &r->sc, r->qt.ranks, o->nquant, r->qt.values, r->qt.below, r->q));
+		got = take_tree(r, sel_linkage_with_ranks(r->store.in, &r->sc, o->method, r->qt.ranks, o->nquant, r->qt.values, r->qt.below, r->q));
 	} else {
 		call = Q_SELECT;
 		got = sel_select(r->store.in, &r->sc, r->qt.ranks, o->nquant, r->qt.values, r->qt.below, r->q);
@@ -711,6 +768,8 @@ static int set_up(int argc, char **argv, struct run *r)
 		ok = (err("Options --linkage-only and -k, --neighbors conflict: the neighbors need a pass of their own (use --linkage without --linkage-only)"), false);
 	if (ok && o->linkage_only && o->has_min_score)
 		ok = (err("Options --linkage-only and --min-score conflict: the score graph needs a pass of its own (use --linkage without --linkage-only)"), false);
+	if (ok && o->has_method && !o->linkage)
+		ok = (err("Option --linkage-method requires a tree: --linkage, --clusters, --clusters-quantile or --linkage-only"), false);
 	if (ok && o->normalize && !o->neighbors && !o->has_min_score && !o->linkage && !o->nquant)
 		ok = (err("Option --normalize requires something selected from the scores: -k, --min-score, --min-quantile, --linkage, --clusters, "
 			  "--clusters-quantile or --quantiles (the similarity matrix itself stays raw)"), false);
@@ -789,8 +848,12 @@ static void banner(const struct run *r)
 	else if (o->has_min_score)
 		info("Score graph: pairs that score at least %d%s", o->min_score, o->edges_only ? " (no similarity matrix)" : "");
 	if (o->linkage)
-		info("Single-linkage tree%s", o->linkage_only ? " (no similarity matrix)" : "");
-	if (o->clusters_q >= 0)
+		info("%s tree%s", tree_name(o, true), o->linkage_only ? " (no similarity matrix)" : "");
+	if (o->method && o->clusters_q >= 0)
+		info("Clusters: the %s clusters merged at or above the %g quantile of the scores", tree_name(o, false), o->quantiles[o->clusters_q]);
+	else if (o->method && o->has_clusters)
+		info("Clusters: the %s clusters merged at or above %d", tree_name(o, false), o->clusters_at);
+	else if (o->clusters_q >= 0)
 		info("Clusters: connected components of the pairs that score at least the %g quantile of the scores", o->quantiles[o->clusters_q]);
 	else if (o->has_clusters)
 		info("Clusters: connected components of the pairs that score at least %d", o->clusters_at);
@@ -980,7 +1043,7 @@ static bool run_tile_job(struct run *r)
 	if (o->has_min_score && (o->min_q < 0 || r->qt.done) && job_answers)
 		job_says(take_edges(r, sa_zjob_edges(job, o->min_score)), "Score graph", "built");
 	if (o->linkage && job_answers)
-		job_says(take_tree(r, sa_zjob_linkage(job)), "Single-linkage tree", "built");
+		job_says(take_tree(r, o->method ? sa_zjob_agglomerate(job, o->method) : sa_zjob_linkage(job)), tree_title(o), "built");
 	sa_zjob_destroy(job);
 	stamp("HDF5 written");
 	return true;
@@ -992,7 +1055,7 @@ static bool run_only(struct run *r)
 {
 	const struct options *o = &r->o;
 	if (o->linkage_only)
-		info("Similarity Matrix stays on the device: the single-linkage tree is built there");
+		info("Similarity Matrix stays on the device: the %s tree is built there", tree_name(o, false));
 	else if (o->edges_only && o->min_q >= 0)
 		info("Similarity Matrix stays on the device: the cut and the pairs at or above it are selected there");
 	else if (o->edges_only)
@@ -1012,11 +1075,11 @@ static bool run_only(struct run *r)
 	if (got && o->edges_only && !r->eg.edges)
 		got = take_edges(r, sel_edges(r->store.in, &r->sc, o->min_score, r->q));
 	if (got && o->linkage_only && !r->lk.tree)
-		got = take_tree(r, sel_linkage(r->store.in, &r->sc, r->q));
+		got = take_tree(r, sel_linkage(r->store.in, &r->sc, o->method, r->q));
 	if (!got)
 		return failed(sa_last_error());
 	const double call = now() - t0;
-	stamp(o->linkage_only ? "sa_hip_linkage returned" : o->edges_only ? "sa_hip_edges returned" : "sa_hip_neighbors returned");
+	stamp(o->linkage_only ? o->method ? "sa_hip_agglomerate returned" : "sa_hip_linkage returned" : o->edges_only ? "sa_hip_edges returned" : "sa_hip_neighbors returned");
 	finish_progress(r);
 	r->t_align = sa_hip_last_align_seconds();
 	const double t_sel = o->linkage_only ? r->lk.seconds : o->edges_only ? r->eg.seconds : (r->nb.seconds = sa_hip_last_neighbors_seconds());
@@ -1106,8 +1169,9 @@ static bool pass_linkage(struct run *r)
 {
 	if (!r->o.linkage || r->lk.tree)
 		return true;
-	verb(SECOND_PASS, "Single-linkage tree");
-	return passed(take_tree(r, sel_linkage(r->store.in, &r->sc, r->q)), &r->lk.second_pass, "sa_hip_linkage returned");
+	verb(SECOND_PASS, tree_title(&r->o));
+	return passed(take_tree(r, sel_linkage(r->store.in, &r->sc, r->o.method, r->q)), &r->lk.second_pass,
+		      r->o.method ? "sa_hip_agglomerate returned" : "sa_hip_linkage returned");
 }
 
 /* ---- writing the selections: each into the file the matrix made, or into one of its own when there is no matrix ---- */
@@ -1170,12 +1234,14 @@ static bool write_linkage(struct run *r)
 		labels = malloc(sizeof(int32_t) * r->n);
 		if (!labels)
 			return failed("Out of memory allocating cluster labels");
-		r->lk.clusters = sa_linkage_labels(pairs, score, r->store.in.num, o->clusters_at, labels);
+		r->lk.clusters = (o->method ? sa_agglo_labels : sa_linkage_labels)(pairs, score, r->store.in.num, o->clusters_at, labels);
 		if (r->lk.clusters < 0)
 			return failed(sa_last_error());
 		verb("Clusters: %d at score >= %d", r->lk.clusters, o->clusters_at);
 	}
 	if (!WRITE_OUT(r, sa_host_write_linkage(o->output, &r->store, pairs, score, labels, o->linkage_only ? 1 : 0), "linkage written"))
+		return false;
+	if (o->has_method && !WRITE_OUT(r, sa_host_write_linkage_method(o->output, o->method), "linkage method written"))
 		return false;
 	free(labels);
 	sa_linkage_destroy(r->lk.tree);
@@ -1212,6 +1278,8 @@ static void report(const struct run *r)
 	printf("  (device set-up and upload, outside the phases as in the reference: %.3f sec)\n", r->t_setup);
 	printf("  (schedule: %s)\n", r->device_deflate ? (o->compression ? "column blocks into device memory, their tiles deflated on the device and written meanwhile"
 									  : "column blocks into device memory, their tiles delivered as HDF5 chunks meanwhile")
+			       : o->linkage_only && o->method == SA_AGGLO_COMPLETE ? "the packed matrix stays in device memory, only the complete-linkage tree comes back"
+			       : o->linkage_only && o->method == SA_AGGLO_AVERAGE ? "the packed matrix stays in device memory, only the average-linkage tree comes back"
 			       : o->linkage_only ? "the packed matrix stays in device memory, only the single-linkage tree comes back"
 			       : o->edges_only ? "the packed matrix stays in device memory, only the edges come back"
 			       : o->neighbors_only ? "the packed matrix stays in device memory, only the neighbors come back"
@@ -1228,7 +1296,10 @@ static void report(const struct run *r)
 	if (o->has_min_score)
 		printf("  (score graph on the device, min score = %d: %lld edges, %.6f sec%s)\n", o->min_score, r->eg.count, r->eg.seconds,
 		       r->eg.second_pass ? AGAIN : "");
-	if (o->linkage)
+	if (o->linkage && o->method)
+		printf("  (%s tree on the device: %d merges, %lld row rescans, %.6f sec%s)\n", tree_name(o, false), r->lk.merges, r->lk.rescans,
+		       r->lk.seconds, r->lk.second_pass ? AGAIN : "");
+	else if (o->linkage)
 		printf("  (single-linkage tree on the device: %d merges, %d rounds, %.6f sec%s)\n", r->lk.merges, r->lk.rounds, r->lk.seconds,
 		       r->lk.second_pass ? AGAIN : "");
 	if (o->has_clusters)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -571,6 +571,65 @@ sa_linkage *sa_hip_linkage_with_ranks_pid(struct sa_input in, const struct sa_sc
 					  int32_t *value, int64_t *below, int32_t denom);
 /* device time (seconds) of the identity sweep in the last successful sa_hip_identity / *_pid / sa_zjob_identity call */
 double sa_hip_last_identity_seconds(void);
+
+/* ---- complete and average linkage: the two other hierarchies of the device matrix ------------------------------------------
+ * No reference counterpart.  The flat clusters of single linkage are connected components, and on protein families connected
+ * components chain: one bridging sequence joins two unrelated groups.  Complete linkage promises that EVERY pair inside a
+ * cluster scores at least T; average linkage (UPGMA) is the classical guide tree.  Both need the whole matrix between merges,
+ * not a spanning tree -- and the whole matrix is on the device when the alignment ends (csrc/sa_agglo.hip).
+ * Input: the packed triangle of N sequences, pair i < j at p(i, j) = j (j - 1) / 2 + i, int32, any contents.  Method:
+ * SA_AGGLO_COMPLETE or SA_AGGLO_AVERAGE; 0 is reserved for single linkage and refused here (sa_ctx_linkage builds it).
+ * Clusters: a cluster is named by its smallest member; at first every sequence is a cluster.
+ * Similarity of two clusters A, B:
+ *   complete  the minimum of score(a, b) over a in A, b in B (int32)
+ *   average   the exact rational S(A, B) / (|A| |B|), S the int64 sum of those scores; no floating point anywhere
+ * Total order (part of the contract; the single-linkage order lifted to clusters): cluster pair e = (A, B) with names a < b has
+ * p(e) = b (b - 1) / 2 + a; e comes BEFORE f iff sim(e) > sim(f), or the similarities are equal and p(e) < p(f).  Two averages
+ * are equal iff S1 n2 == S2 n1 in 128 bits.
+ * Step t = 0 .. N - 2: the first pair in that order among all pairs of active clusters is merged; the union keeps the name a;
+ * its similarity to every other cluster C is min(sim(A, C), sim(B, C)) (complete) or S(A, C) + S(B, C) with size |A| + |B|
+ * (average).
+ *   pairs  int32[2 (N - 1)]; pairs[2 t] = a < pairs[2 t + 1] = b, in the order the merges are made
+ *   score  int32[N - 1]; complete: the minimum; average: floor(S / (|A| |B|)), rounded towards minus infinity as sa_norm_value
+ * The shape of the single-linkage tree: sa_linkage_pairs, sa_linkage_score, sa_linkage_destroy and sa_linkage_merges serve
+ * unchanged.  score is non-increasing (the floors of the averages too), and the pairs form a spanning tree with lo < hi; so
+ * sa_linkage_merges gives the merge table in scipy's convention, and for an integer T "merged at similarity >= T" is
+ * score[t] >= T.  Equal scores need NOT be in ascending p, so sa_linkage_labels may rightly refuse such a tree;
+ * sa_agglo_labels reads it.  On a matrix without ties the merge table and the heights equal
+ * scipy.cluster.hierarchy.linkage(-scores, 'complete' | 'average').
+ * Range: average needs |S| <= 2^31 N^2 / 4 inside int64, so N <= 131072; complete N <= 2^30; a larger N is refused before
+ * anything is launched.  "No candidate" is never a score value: INT32_MIN and INT32_MAX are scores.  The same store, scoring
+ * and method give the same bytes run after run. */
+#define SA_AGGLO_COMPLETE 1
+#define SA_AGGLO_AVERAGE 2
+/* host only: the scratch memory sa_ctx_agglomerate needs -- the square working matrix, 4 N^2 + O(N) bytes (complete) or
+ * 8 N^2 + O(N) (average); 0 for a bad method, num < 2 or an N outside the method's range */
+size_t sa_agglo_scratch_bytes(int32_t num, int32_t method);
+/* device-resident, asynchronous on `stream`, no host synchronisation, no allocation: d_packed = whole packed matrix of ctx's
+ * store, read only; d_pairs 2 (N - 1) int32, d_score N - 1 int32, d_scratch sa_agglo_scratch_bytes(N, method) bytes (8-byte
+ * aligned), contents ignored.  2 N launches are enqueued: two small kernels per merge. */
+int sa_ctx_agglomerate(sa_ctx *ctx, const int32_t *d_packed, int32_t method, int32_t *d_pairs, int32_t *d_score, void *d_scratch,
+		       void *stream);
+/* one call, host in / host out, one device (the first): align into device memory, tree, copy back.  norm and pid_denom both
+ * NULL: the scores; norm: the normalised scores, as sa_hip_linkage_norm; pid_denom: percent identity under *pid_denom, as
+ * sa_hip_linkage_pid; both: refused.  A bad method, both quantities and an N out of range are refused before a device is
+ * looked for.  NULL + sa_last_error, naming the bytes needed, when matrix + scratch do not fit; the process goes on working. */
+sa_linkage *sa_hip_agglomerate(struct sa_input in, const struct sa_scoring *sc, int32_t method, const struct sa_norm *norm,
+			       const int32_t *pid_denom);
+/* one alignment, the order statistics and the tree from the same device matrix, as sa_hip_linkage_with_ranks; a bad rank is
+ * refused before the alignment */
+sa_linkage *sa_hip_agglomerate_with_ranks(struct sa_input in, const struct sa_scoring *sc, int32_t method, const struct sa_norm *norm,
+					  const int32_t *pid_denom, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below);
+/* on a finished tile job: answers when sa_zjob_linkage can, refuses in the same cases with the same wording */
+sa_linkage *sa_zjob_agglomerate(sa_zjob *job, int32_t method);
+/* host only, no device: applies the merges t with score[t] >= min_score (a prefix); labels[r] = the smallest index in r's
+ * cluster; returns the number of clusters.  < 0 through sa_last_error with nothing written for a null argument, pairs that are
+ * not a tree (an index out of range, lo >= hi, a cycle) and scores that increase. */
+int32_t sa_agglo_labels(const int32_t *pairs, const int32_t *score, int32_t num, int32_t min_score, int32_t *labels);
+/* device time (seconds) of the last successful sa_hip_agglomerate* / sa_zjob_agglomerate call */
+double sa_hip_last_agglomerate_seconds(void);
+/* ... and the rows that call scanned again after a merge took their cached partner (a diagnostic; 0 on an all-equal matrix) */
+int64_t sa_hip_last_agglomerate_rescans(void);
 
 /* ---- pair-space planning (host only, no device needed) -------------------
  * DP cells (sum of len_i*len_j) of the packed pair range [start, start+count),

@@ -68,6 +68,8 @@ ABI_SYMBOLS = (
     "sa_hip_linkage_with_ranks", "sa_hip_last_select_seconds",
     "sa_pid_value", "sa_ctx_identity_range", "sa_hip_identity", "sa_zjob_identity", "sa_hip_neighbors_pid", "sa_hip_edges_pid",
     "sa_hip_linkage_pid", "sa_hip_select_pid", "sa_hip_edges_at_rank_pid", "sa_hip_linkage_with_ranks_pid", "sa_hip_last_identity_seconds",
+    "sa_agglo_scratch_bytes", "sa_ctx_agglomerate", "sa_hip_agglomerate", "sa_hip_agglomerate_with_ranks", "sa_zjob_agglomerate",
+    "sa_agglo_labels", "sa_hip_last_agglomerate_seconds", "sa_hip_last_agglomerate_rescans",
 )
 
 
@@ -316,6 +318,20 @@ def load_library() -> C.CDLL:
     lib.sa_hip_linkage_with_ranks_pid.argtypes = lib.sa_hip_linkage_with_ranks.argtypes + [C.c_int32]
     lib.sa_hip_linkage_with_ranks_pid.restype = C.c_void_p
     lib.sa_hip_last_identity_seconds.restype = C.c_double
+    lib.sa_agglo_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.sa_agglo_scratch_bytes.restype = C.c_size_t
+    lib.sa_ctx_agglomerate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_agglomerate.restype = C.c_int
+    lib.sa_hip_agglomerate.argtypes = [_Input, C.POINTER(_Scoring), C.c_int32, C.POINTER(_Norm), C.POINTER(C.c_int32)]
+    lib.sa_hip_agglomerate.restype = C.c_void_p
+    lib.sa_hip_agglomerate_with_ranks.argtypes = lib.sa_hip_agglomerate.argtypes + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_hip_agglomerate_with_ranks.restype = C.c_void_p
+    lib.sa_zjob_agglomerate.argtypes = [C.c_void_p, C.c_int32]
+    lib.sa_zjob_agglomerate.restype = C.c_void_p
+    lib.sa_agglo_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.sa_agglo_labels.restype = C.c_int32
+    lib.sa_hip_last_agglomerate_seconds.restype = C.c_double
+    lib.sa_hip_last_agglomerate_rescans.restype = C.c_int64
     _lib = lib
     return lib
 
@@ -827,6 +843,80 @@ def linkage_labels(pairs, score, n: int, min_score: int) -> tuple[np.ndarray, in
     return labels, int(clusters)
 
 
+AGGLO_COMPLETE, AGGLO_AVERAGE = 1, 2  # SA_AGGLO_COMPLETE, SA_AGGLO_AVERAGE
+_AGGLO_NAMES = {"complete": AGGLO_COMPLETE, "average": AGGLO_AVERAGE}
+
+
+def _agglo_method(method) -> int:
+    """"complete" / "average" or a number; which numbers are valid is the library's to say"""
+    if isinstance(method, str):
+        if method not in _AGGLO_NAMES:
+            raise AlignError(f"linkage method {method!r} is neither 'complete' nor 'average' (single linkage: hip_linkage)")
+        return _AGGLO_NAMES[method]
+    m = int(method)
+    if not -2**31 <= m < 2**31:
+        raise AlignError(f"method = {m} is not an int32")
+    return m
+
+
+def _agglo_quantity(norm: Optional[Norm], pid: Optional[int], n: int):
+    """the norm / pid_denom arguments of sa_hip_agglomerate* (both may be given: the library refuses that) and what the
+    result gains behind the plain tuple: the n denominators for a norm"""
+    cn, den = norm._as_c(n) if norm is not None else (None, None)
+    return (C.byref(cn) if cn is not None else None, C.byref(C.c_int32(_denom(pid))) if pid is not None else None,
+            (den[:n],) if den is not None else ())
+
+
+def hip_agglomerate(store: SequenceStore, scoring: Scoring, method, norm: Optional[Norm] = None, pid: Optional[int] = None):
+    """sa_hip_agglomerate: the complete-linkage ("complete", 1) or average-linkage / UPGMA ("average", 2) tree, built on the
+    device -- (pairs int32 (N - 1, 2) with lo < hi, score int32 (N - 1,)) in the order the merges are made; a cluster is
+    named by its smallest member, score is the minimum over the merged clusters' cross pairs, or the floor of their average.
+    The matrix never leaves the device.  With a norm: (pairs, score, denominators)."""
+    sc, m = scoring._as_c(), _agglo_method(method)
+    cn, cd, den = _agglo_quantity(norm, pid, store.num)
+    lib = load_library()
+    return _take_linkage(lib, lib.sa_hip_agglomerate(store._as_c(), C.byref(sc), m, cn, cd)) + den
+
+
+def hip_agglomerate_with_ranks(store: SequenceStore, scoring: Scoring, method, ranks, norm: Optional[Norm] = None, pid: Optional[int] = None):
+    """sa_hip_agglomerate_with_ranks: one alignment, then hip_select's (values, below) for `ranks` and hip_agglomerate's
+    (pairs, score) from the same device matrix -- (pairs, score, values, below); with a norm the denominators follow"""
+    sc, m = scoring._as_c(), _agglo_method(method)
+    r = _ranks(ranks)
+    value, below = _select_room(len(r))
+    cn, cd, den = _agglo_quantity(norm, pid, store.num)
+    lib = load_library()
+    tree = _take_linkage(lib, lib.sa_hip_agglomerate_with_ranks(store._as_c(), C.byref(sc), m, cn, cd, r.ctypes.data, len(r),
+                                                                value.ctypes.data, below.ctypes.data))
+    return tree + (value[:len(r)].copy(), below[:len(r)].copy()) + den
+
+
+def agglo_scratch_bytes(n: int, method) -> int:
+    """sa_agglo_scratch_bytes: the device scratch memory Context.agglomerate needs for n sequences (0: a bad method or n)"""
+    return int(load_library().sa_agglo_scratch_bytes(int(n), _agglo_method(method)))
+
+
+def last_agglomerate_seconds() -> float:
+    """device time of the last hip_agglomerate* / DeflateJob.agglomerate call"""
+    return float(load_library().sa_hip_last_agglomerate_seconds())
+
+
+def last_agglomerate_rescans() -> int:
+    """the rows the last hip_agglomerate* / DeflateJob.agglomerate call scanned again after a merge took their cached partner"""
+    return int(load_library().sa_hip_last_agglomerate_rescans())
+
+
+def agglo_labels(pairs, score, n: int, min_score: int) -> tuple[np.ndarray, int]:
+    """sa_agglo_labels (host only): (labels int32 (N,), clusters) after the merges with score >= min_score -- labels[r] is the
+    smallest index in r's cluster.  For a complete-linkage tree every pair inside a cluster scores at least min_score."""
+    n, pairs, score = _tree_arrays(pairs, score, n)
+    labels = np.empty(n, np.int32)
+    clusters = load_library().sa_agglo_labels(pairs.ctypes.data, score.ctypes.data, n, _min_score(min_score), labels.ctypes.data)
+    if clusters < 0:
+        raise AlignError(_err())
+    return labels, int(clusters)
+
+
 def linkage_merges(pairs, n: int) -> np.ndarray:
     """sa_linkage_merges (host only): int32 (N - 1, 3), rows (left, right, size) in the convention of scipy.cluster.hierarchy:
     ids below N are sequences, id N + u is the cluster made by merge u"""
@@ -1102,6 +1192,14 @@ class Context:
                                     C.c_void_p(d_scratch_ptr), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def agglomerate(self, d_packed_ptr: int, method, d_pairs_ptr: int, d_score_ptr: int, d_scratch_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_agglomerate: from the whole packed device matrix of this store, the complete- or average-linkage tree into the
+        device arrays d_pairs (2 (N - 1) int32) / d_score (N - 1 int32), asynchronously on `stream`; d_scratch:
+        agglo_scratch_bytes(N, method) bytes, 8-byte aligned, contents ignored"""
+        if self._lib.sa_ctx_agglomerate(self._h, C.c_void_p(d_packed_ptr), _agglo_method(method), C.c_void_p(d_pairs_ptr),
+                                        C.c_void_p(d_score_ptr), C.c_void_p(d_scratch_ptr), C.c_void_p(stream)):
+            raise AlignError(_err())
+
     def select(self, d_packed_ptr: int, ranks, d_value_ptr: int, d_below_ptr: int, d_scratch_ptr: int, stream: int = 0) -> None:
         """sa_ctx_select: from the whole packed device matrix of this store (any 4-byte-aligned device pointer), the scores at
         `ranks` (host values, up to 16) into d_value (m int32) and the pairs below each into d_below (m int64), asynchronously on
@@ -1227,6 +1325,11 @@ class DeflateJob:
         """sa_zjob_linkage: (pairs, score) as hip_linkage returns them, from the finished packed matrix this job's device
         holds -- after next() has returned [] for a begin() job; raises when the matrix is dealt over several jobs"""
         return _take_linkage(self._lib, self._lib.sa_zjob_linkage(self._h))
+
+    def agglomerate(self, method) -> tuple[np.ndarray, np.ndarray]:
+        """sa_zjob_agglomerate: (pairs, score) as hip_agglomerate returns them, from the finished packed matrix this job's
+        device holds -- after next() has returned [] for a begin() job; raises when the matrix is dealt over several jobs"""
+        return _take_linkage(self._lib, self._lib.sa_zjob_agglomerate(self._h, _agglo_method(method)))
 
     def select(self, ranks) -> tuple[np.ndarray, np.ndarray]:
         """sa_zjob_select: (values, below) as hip_select returns them, from the finished packed matrix this job's device

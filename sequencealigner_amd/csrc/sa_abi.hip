@@ -731,6 +731,77 @@ extern "C" sa_linkage *sa_hip_linkage_with_ranks_pid(struct sa_input in, const s
 			[&] { return linkage_with_ranks_impl(in, sc, ranks, m, value, below, Quantity{ nullptr, &denom }); });
 }
 
+/* ---- complete / average linkage (sa_agglo.hip) over the scores, the normalised scores or percent identity ----------------------- */
+/* norm and pid_denom both given is refused; the method and N are checked before a device is looked for */
+static bool agglomerate_quantity(const char *who, struct sa_input in, const struct sa_scoring *sc, int32_t method, const struct sa_norm *norm,
+				 const int32_t *pid_denom)
+{
+	if (!sc) {
+		sa_set_error("%s: null argument", who);
+		return false;
+	}
+	if (norm && pid_denom) {
+		sa_set_error("%s: norm and pid_denom exclude each other", who);
+		return false;
+	}
+	return sa_agglo_check(who, in.num, method);
+}
+
+static sa_linkage *agglomerate_impl(struct sa_input in, const struct sa_scoring *sc, int32_t method, Quantity q)
+{
+	const char *who = "sa_hip_agglomerate";
+	DeviceRun run;
+	if (!run.begin(who, in, sc, q))
+		return nullptr;
+	return run.finished(sa_agglomerate_to_host(who, run.d_packed, in.num, method, run.stream), sa_linkage_destroy);
+}
+
+extern "C" sa_linkage *sa_hip_agglomerate(struct sa_input in, const struct sa_scoring *sc, int32_t method, const struct sa_norm *norm,
+					  const int32_t *pid_denom)
+{
+	return sa_guard("sa_hip_agglomerate", (sa_linkage *)nullptr, [&]() -> sa_linkage * {
+		if (!agglomerate_quantity("sa_hip_agglomerate", in, sc, method, norm, pid_denom))
+			return nullptr;
+		return agglomerate_impl(in, sc, method, Quantity{ norm, pid_denom });
+	});
+}
+
+static sa_linkage *agglomerate_with_ranks_impl(struct sa_input in, const struct sa_scoring *sc, int32_t method, const int64_t *ranks, int32_t m,
+					       int32_t *value, int64_t *below, Quantity q)
+{
+	const char *who = "sa_hip_agglomerate_with_ranks";
+	if (!ranks || !value || !below) {
+		sa_set_error("%s: null argument", who);
+		return nullptr;
+	}
+	if (!sa_select_check(who, in.num, ranks, m))
+		return nullptr;
+	DeviceRun run;
+	if (!run.begin(who, in, sc, q))
+		return nullptr;
+	int32_t cut[SA_HIP_SELECT_MAX];
+	int64_t under[SA_HIP_SELECT_MAX];
+	if (!sa_select_to_host(who, run.d_packed, in.num, ranks, m, cut, under, run.stream))
+		return nullptr;
+	sa_linkage *res = run.finished(sa_agglomerate_to_host(who, run.d_packed, in.num, method, run.stream), sa_linkage_destroy);
+	if (res)
+		for (int32_t t = 0; t < m; t++) {
+			value[t] = cut[t];
+			below[t] = under[t];
+		}
+	return res;
+}
+
+extern "C" sa_linkage *sa_hip_agglomerate_with_ranks(struct sa_input in, const struct sa_scoring *sc, int32_t method, const struct sa_norm *norm,
+						     const int32_t *pid_denom, const int64_t *ranks, int32_t m, int32_t *value, int64_t *below)
+{
+	return sa_guard("sa_hip_agglomerate_with_ranks", (sa_linkage *)nullptr, [&]() -> sa_linkage * {
+		if (!agglomerate_quantity("sa_hip_agglomerate_with_ranks", in, sc, method, norm, pid_denom))
+			return nullptr;
+		return agglomerate_with_ranks_impl(in, sc, method, ranks, m, value, below, Quantity{ norm, pid_denom });
+	});
+}
+
 extern "C" int sa_hip_last_align_path(void) { return g_last_align_path.load(); }
 
 extern "C" int sa_hip_last_align_breakdown(double *ms, int n)

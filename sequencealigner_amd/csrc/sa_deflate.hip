@@ -1336,6 +1336,21 @@ extern "C" sa_linkage *sa_zjob_linkage(sa_zjob *z)
 	});
 }
 
+/* The complete- or average-linkage tree of the job's packed matrix (sa_agglo.hip). */
+extern "C" sa_linkage *sa_zjob_agglomerate(sa_zjob *z, int32_t method)
+{
+	return sa_guard("sa_zjob_agglomerate", (sa_linkage *)nullptr, [&]() -> sa_linkage * {
+		if (!z) {
+			sa_set_error("sa_zjob_agglomerate: null argument");
+			return nullptr;
+		}
+		if (!zjob_gate(z, "sa_zjob_agglomerate", "tree") || !sa_agglo_check("sa_zjob_agglomerate", z->num, method))
+			return nullptr;
+		SA_HIP_CHECK(hipSetDevice(z->device), return nullptr);
+		return sa_agglomerate_to_host("sa_zjob_agglomerate", z->d_packed, z->num, method, z->stream);
+	});
+}
+
 /* Normalises the job's own packed matrix in place (sa_normalize.hip): every tile has been encoded and handed out by then, so the
  * tiles stay raw and what is selected afterwards is normalised.  Refuses a matrix that is not the job's to rewrite, or not scores. */
 extern "C" int sa_zjob_normalize(sa_zjob *z, const struct sa_norm *norm)

@@ -127,6 +127,13 @@ sa_edges *sa_edges_to_host(const char *who, const int32_t *d_packed, int32_t num
 struct sa_linkage;
 sa_linkage *sa_linkage_to_host(const char *who, const int32_t *d_packed, int32_t num, hipStream_t s);
 
+/* complete / average linkage (sa_agglo.hip).  sa_agglo_check: the method and N, before anything is launched or a device is
+ * looked for.  sa_agglomerate_to_host: the tree of a packed device matrix into host memory, in order on `s`, which is
+ * synchronised; the device time goes to sa_hip_last_agglomerate_seconds, the row rescans to sa_hip_last_agglomerate_rescans.
+ * nullptr + sa_set_error on failure, a working matrix that does not fit the device included. */
+bool sa_agglo_check(const char *who, int32_t num, int32_t method);
+sa_linkage *sa_agglomerate_to_host(const char *who, const int32_t *d_packed, int32_t num, int32_t method, hipStream_t s);
+
 /* order statistics of the score distribution (sa_select.hip).  sa_select_check: m, N and the ranks, before anything is launched.
  * sa_select_to_host: value / below of the m ranks of a packed device matrix into host memory, in order on `s`, which is
  * synchronised; the device time goes to sa_hip_last_select_seconds.  false + sa_set_error on failure, nothing written. */
