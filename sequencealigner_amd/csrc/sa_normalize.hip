@@ -4,11 +4,11 @@
  * variants).  No reference counterpart: the reference delivers raw scores, which grow with length, and leaves the division
  * to whoever holds the N x N matrix on the host.  The contract and the arithmetic are in sa_normalize_core.h.
  *
- *   sa_k_self<METHOD>     one wavefront per sequence k: the anti-diagonal s32 sweep of sa_k_pair_per_wave (sa_generic.hip) for
- *                         the pair (k, k) -- the sequence is the row AND the column sequence, the table is indexed as for any
- *                         pair, the full DP runs (under an asymmetric table, or one whose diagonal is not the row maximum, the
- *                         self-score is not the sum of the diagonal entries).  64-column strips through the context's per-wave
- *                         strip-boundary scratch: any length the store accepts.
+ *   sa_k_self<METHOD>     one wavefront per sequence k: the anti-diagonal s32 sweep of sa_wave_sweep.inc, the one of
+ *                         sa_k_pair_per_wave, for the pair (k, k) -- the sequence is the row AND the column sequence, the
+ *                         table is indexed as for any pair, the full DP runs (under an asymmetric table, or one whose
+ *                         diagonal is not the row maximum, the self-score is not the sum of the diagonal entries).  64-column
+ *                         strips through the context's per-wave strip-boundary scratch: any length the store accepts.
  *   sa_k_lengths          d[k] = meta[k].len.
  *   sa_k_normalize<RULE>  one streaming pass, 4 P bytes in and 4 P bytes out.  A workgroup takes units of the deal of
  *                         sa_normalize_core.h -- the columns t and N - 1 - t, N - 1 entries together -- and walks each column's
@@ -24,6 +24,7 @@
 
 #include "sa_ctx.h"
 #include "sa_normalize_core.h"
+#include "sa_wave_sweep.h"
 
 static_assert(SA_NORM_SRC_SELF == SA_NORM_SELF && SA_NORM_SRC_LENGTH == SA_NORM_LENGTH, "sa_normalize_core.h and seqalign_hip.h disagree");
 static_assert(SA_NORM_RULE_MIN == SA_NORM_MIN && SA_NORM_RULE_MAX == SA_NORM_MAX && SA_NORM_RULE_MEAN == SA_NORM_MEAN,
@@ -32,22 +33,8 @@ static_assert(SA_NORM_PPM == SA_NORM_SCALE, "sa_normalize_core.h and seqalign_hi
 
 namespace {
 
-constexpr int32_t SCORE_MIN = INT32_MIN / 2; /* reference src/bio/align.h:19 */
 constexpr int NORM_THREADS = 256;
 constexpr int NORM_WGS_PER_CU = 8;
-
-__device__ __forceinline__ int32_t imax(int32_t a, int32_t b) { return a > b ? a : b; }
-
-/* value shifted in from lane - 1 (DPP wave_shr:1, bound_ctrl off: lane 0 keeps `v` and overrides it afterwards) */
-__device__ __forceinline__ int32_t from_left(int32_t v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
-
-__device__ __forceinline__ int32_t wave_max(int32_t v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1)
-		v = imax(v, __shfl_xor(v, d, 64));
-	return v;
-}
 
 struct SelfArgs {
 	SaSeqStore st;
@@ -58,7 +45,7 @@ struct SelfArgs {
 	int64_t scratch_stride; /* ints per wave = 2 * (max_len + 2) */
 };
 
-/* sa_k_pair_per_wave with i = j = k: lane l owns column 64 * strip + l + 1, rows enter at lane 0 and travel one lane per step */
+/* the pair (k, k): the sequence rides the sweep as its rows and as its columns */
 template <int METHOD>
 __global__ __launch_bounds__(256) void sa_k_self(SelfArgs A)
 {
@@ -66,99 +53,18 @@ __global__ __launch_bounds__(256) void sa_k_self(SelfArgs A)
 	for (int k = threadIdx.x; k < SA_SUB_DIM * SA_SUB_DIM; k += blockDim.x)
 		s_sub[k] = A.sub[k];
 	__syncthreads();
-
 	const int lane = threadIdx.x & 63;
 	const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
 	const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
 	int32_t *bndM = A.scratch + wave * A.scratch_stride;
 	int32_t *bndX = bndM + (A.scratch_stride >> 1);
-
 	const int32_t g = A.gap_pen, o = A.gap_opn, e = A.gap_ext;
-	/* closed forms of the reference's borders: NW nw.c:16-20: k g.  GA ga.c:26-38: B(1) = max(o, SCORE_MIN + e), then + max(o, e) */
-	const int32_t ga_b1 = imax(o, SCORE_MIN + e);
-	const int32_t ga_w = imax(o, e);
-	auto border = [&](int32_t k) -> int32_t {
-		if (METHOD == SA_METHOD_NW)
-			return k * g;
-		if (METHOD == SA_METHOD_GA)
-			return k == 0 ? 0 : ga_b1 + (k - 1) * ga_w;
-		return 0;
-	};
 
 	for (int64_t k = wave; k < A.st.num; k += nwaves) {
-		const int32_t m = A.st.meta[k].len; /* rows and columns */
-		const uint8_t *cs = A.st.codes + A.st.meta[k].off;
-		const int32_t nstrips = (m + 63) >> 6;
-		int32_t best = 0; /* SW running maximum, sw.c:33,57 */
-		int32_t h = 0;
-
-		for (int32_t s = 0; s < nstrips; s++) {
-			const int32_t c = (s << 6) + lane + 1;
-			const bool colvalid = c <= m;
-			const int32_t b = colvalid ? cs[c - 1] : 0;
-			const int32_t width = (m - (s << 6)) < 64 ? (m - (s << 6)) : 64;
-			const bool last_strip = s + 1 == nstrips;
-			h = border(c);
-			int32_t y = SCORE_MIN;
-			int32_t x = SCORE_MIN;
-			int32_t diag = border(c - 1);
-			const int32_t steps = m + width - 1;
-
-			for (int32_t t = 0; t < steps; t++) {
-				const int32_t r = t - lane + 1;
-				int32_t lm = from_left(h);
-				int32_t lx = SCORE_MIN;
-				if (METHOD != SA_METHOD_NW)
-					lx = from_left(x);
-				if (lane == 0) {
-					if (s == 0) {
-						lm = border(r);
-						lx = SCORE_MIN;
-					} else if (r <= m) { /* (r >= 1 in lane 0; bndM holds max_len + 2 ints) */
-						lm = bndM[r];
-						if (METHOD != SA_METHOD_NW)
-							lx = bndX[r];
-					}
-				}
-				const bool valid = colvalid && r >= 1 && r <= m;
-				const int32_t a = valid ? cs[r - 1] : 0;
-				int32_t nm, nx = SCORE_MIN, ny = SCORE_MIN;
-				if (METHOD == SA_METHOD_NW) {
-					/* nw.c:29-35: [code of row][code of column] */
-					const int32_t match = diag + s_sub[a * SA_SUB_DIM + b];
-					nm = imax(lm + g, imax(h + g, match));
-				} else {
-					/* ga.c:46-63 / sw.c:39-57: [code of column][code of row] */
-					const int32_t sd = diag + s_sub[b * SA_SUB_DIM + a];
-					nx = imax(lm + o, lx + e);
-					ny = imax(h + o, y + e);
-					nm = (METHOD == SA_METHOD_SW) ? imax(sd, 0) : sd;
-					nm = imax(nx, nm);
-					nm = imax(ny, nm);
-				}
-				diag = lm;
-				if (valid) {
-					h = nm;
-					x = nx;
-					y = ny;
-					if (METHOD == SA_METHOD_SW)
-						best = imax(best, nm);
-					if (lane == 63 && !last_strip) {
-						bndM[r] = nm;
-						if (METHOD != SA_METHOD_NW)
-							bndX[r] = nx;
-					}
-				}
-			}
-			if (!last_strip)
-				__threadfence_block(); /* boundary column visible to this wave's next strip */
-		}
-
-		int32_t score;
-		if (METHOD == SA_METHOD_SW)
-			score = wave_max(best);
-		else
-			score = __shfl(h, (m - 1) & 63, 64); /* M[m][m] sits in the lane owning column m */
+		const int32_t m = A.st.meta[k].len, n = m; /* rows and columns */
+		const uint8_t *ci = A.st.codes + A.st.meta[k].off, *cj = ci;
+#include "sa_wave_sweep.inc"
+		const int32_t score = METHOD == SA_METHOD_SW ? wave_max(best) : mn;
 		if (lane == 0)
 			A.den[k] = score;
 	}

@@ -2,7 +2,8 @@
 
 sa_k_pair_per_wave (sa_generic.hip), sa_k_self (sa_normalize.hip), sa_k_trace_fill / sa_k_trace_walk and sa_k_trace_compact
 (sa_traceback.hip) put one unit of work -- a pair, a sequence -- on one wavefront and run `for (q = wave; q < count; q +=
-nwaves)`.  They are launched with at most ctx->generic_blocks workgroups of four waves (the compaction with 2048), which
+nwaves)`; the first two include one sweep (sa_wave_sweep.inc) in that loop, the third keeps its own.  They are launched
+with at most ctx->generic_blocks workgroups of four waves (the compaction with 2048), which
 sa_context.hip sizes at eight workgroups per CU: W = resident_waves() = 8192 on a full MI355X.  A wave starts a second unit
 only when a call holds more than W of them, and what then decides the result -- the reset of best / best_r / best_c, h, the
 walk's window bounds and the run-length emitter, the boundary scratch line (bndM / bndX) reused by a later unit that is
