@@ -308,6 +308,8 @@ extern "C" void sa_ctx_destroy(sa_ctx *ctx)
 		(void)hipFree(ar.d_tok_off);
 		(void)hipFree(ar.d_mine);
 		(void)hipFree(ar.d_any);
+		for (auto &r : ar.rows)
+			(void)hipFree(r.d_rows);
 	}
 	(void)hipFree(ctx->d_codes);
 	(void)hipFree(ctx->d_meta);
@@ -381,7 +383,11 @@ bool sa_arranged_store(sa_ctx *ctx, const SaArrKey &key, const sa_ctx::Arranged 
 		SA_HIP_CHECK(hipMemcpy(ar.d_off, off_s.data(), sizeof(int32_t) * off_s.size(), hipMemcpyHostToDevice), break);
 		SA_HIP_CHECK(hipMemcpy(ar.d_rowmap, rowmap.data(), sizeof(int32_t) * rowmap.size(), hipMemcpyHostToDevice), break);
 		SA_HIP_CHECK(hipMemcpy(ar.d_posmap, posmap.data(), sizeof(int32_t) * posmap.size(), hipMemcpyHostToDevice), break);
-		ctx->arranged.push_back(ar);
+		/* (the host copy of the tokens stays: sa_arranged_rows scales it per row stride, when a class asks) */
+		ar.h_tok.streams = ts.streams;
+		ar.h_tok.tok = std::move(ts.tok);
+		ar.h_tok.tok_off = std::move(ts.tok_off);
+		ctx->arranged.push_back(std::move(ar));
 		ok = true;
 	} while (0);
 	if (!ok) {
@@ -396,6 +402,34 @@ bool sa_arranged_store(sa_ctx *ctx, const SaArrKey &key, const sa_ctx::Arranged 
 		return false;
 	}
 	*out = &ctx->arranged.back();
+	return true;
+}
+
+bool sa_arranged_rows(sa_ctx *ctx, const sa_ctx::Arranged *ar_in, uint32_t stride, const uint32_t **out)
+{
+	*out = nullptr;
+	sa_ctx::Arranged *ar = nullptr;
+	for (auto &a : ctx->arranged)
+		if (&a == ar_in)
+			ar = &a;
+	if (!ar || !ar->d_tok)
+		return true;
+	for (const auto &r : ar->rows)
+		if (r.stride == stride) {
+			*out = r.d_rows;
+			return true;
+		}
+	const auto t_arr = std::chrono::steady_clock::now();
+	std::vector<uint32_t> rows;
+	if (!sa_build_row_streams(ar->h_tok, ar->key.ng, stride, rows))
+		return false;
+	sa_ctx::Arranged::Rows r;
+	r.stride = stride;
+	SA_HIP_CHECK(hipMalloc(&r.d_rows, sizeof(uint32_t) * rows.size()), return false);
+	SA_HIP_CHECK(hipMemcpy(r.d_rows, rows.data(), sizeof(uint32_t) * rows.size(), hipMemcpyHostToDevice), (void)hipFree(r.d_rows); return false);
+	ar->rows.push_back(r);
+	ctx->setup.arrange += sa_ms_since(t_arr);
+	*out = r.d_rows;
 	return true;
 }
 

@@ -77,6 +77,14 @@ struct sa_ctx {
 		/* its token streams (sa_plan.h: SaTokenStreams); nullptr with SA_HIP_NO_TOKENS */
 		uint16_t *d_tok = nullptr, *d_mine = nullptr, *d_any = nullptr;
 		int32_t *d_tok_off = nullptr;
+		/* its row streams (sa_plan.h: sa_build_row_streams), one copy per row stride that a class of a plan has asked for
+		 * (sa_arranged_rows), made from the host copy of the tokens kept here for that */
+		struct Rows {
+			uint32_t stride = 0;
+			uint32_t *d_rows = nullptr;
+		};
+		std::vector<Rows> rows;
+		SaTokenStreams h_tok; /* tok and tok_off only */
 	};
 	std::deque<Arranged> arranged;
 	int64_t tok_lean = 0, tok_legacy = 0; /* packed tiles of the last launch: streaming pre-built tokens / deriving them (sa_ctx_token_tiles) */
@@ -146,6 +154,9 @@ static inline double sa_ms_since(std::chrono::steady_clock::time_point t0)
 bool sa_device_ready(int device);
 /* the arranged copy for `key` (built and uploaded on first use); *out = nullptr when the store has no full block */
 bool sa_arranged_store(sa_ctx *ctx, const SaArrKey &key, const sa_ctx::Arranged **out);
+/* the row streams of an arranged copy for one row stride, built and uploaded on first use; *out = nullptr: the copy has
+ * no token streams (SA_HIP_NO_TOKENS) */
+bool sa_arranged_rows(sa_ctx *ctx, const sa_ctx::Arranged *ar, uint32_t stride, const uint32_t **out);
 SaPlanInputs sa_plan_inputs(const sa_ctx *ctx);
 
 /* sa_launch.hip */

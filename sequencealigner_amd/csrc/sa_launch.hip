@@ -49,7 +49,8 @@ template <typename T> static bool upload(T *&dst, const std::vector<T> &v)
 }
 
 /* the arranged copies a class's tiles choose from, as the kernels see them (builds and uploads what is missing) */
-static bool resolve_levels(sa_ctx *ctx, const SaArrKey (&keys)[SA_PK_SORT_LEVELS], SaArranged (&lv)[SA_PK_SORT_LEVELS])
+/* row_stride: that of the class's profile where its lean way reads row streams (sa_pk_reg_tokens), else 0 */
+static bool resolve_levels(sa_ctx *ctx, const SaArrKey (&keys)[SA_PK_SORT_LEVELS], uint32_t row_stride, SaArranged (&lv)[SA_PK_SORT_LEVELS])
 {
 	for (int l = 0; l < SA_PK_SORT_LEVELS; l++) {
 		lv[l] = SaArranged{};
@@ -58,8 +59,12 @@ static bool resolve_levels(sa_ctx *ctx, const SaArrKey (&keys)[SA_PK_SORT_LEVELS
 		const sa_ctx::Arranged *ar = nullptr;
 		if (!sa_arranged_store(ctx, keys[l], &ar))
 			return false;
-		if (ar)
-			lv[l] = { ar->d_codes, ar->d_off, ar->d_rowmap, ar->d_posmap, ar->key.block, ar->d_tok, ar->d_tok_off, ar->d_mine, ar->d_any };
+		if (!ar)
+			continue;
+		const uint32_t *rowoff = nullptr;
+		if (row_stride && !sa_arranged_rows(ctx, ar, row_stride, &rowoff))
+			return false;
+		lv[l] = { ar->d_codes, ar->d_off, ar->d_rowmap, ar->d_posmap, ar->key.block, ar->d_tok, ar->d_tok_off, ar->d_mine, ar->d_any, rowoff };
 	}
 	return true;
 }
@@ -113,7 +118,7 @@ static bool plan_upload(sa_ctx *ctx, sa_ctx::Plan &pl)
 			const SaHostPkArgs &ha = b.args[x];
 			SaPkClassArgs &a = args[x];
 			a = SaPkClassArgs{};
-			if (!resolve_levels(ctx, ha.lv, a.lv))
+			if (!resolve_levels(ctx, ha.lv, sa_pk_reg_tokens(ctx->sc.method, b.g, ha.k) ? sa_pk_row_stride(ha.k) : 0u, a.lv))
 				return false;
 			const auto &d = pl.dc[(size_t)ha.cls_index];
 			a.jlist = d.d_jlist;

@@ -196,7 +196,39 @@ bool sa_build_tokens(const uint8_t *codes, const int32_t *off, int32_t num, cons
 	return true;
 }
 
-static const char *const TOO_LARGE = "packed range too large for one launch; split it into smaller ranges";
+bool sa_build_row_streams(const SaTokenStreams &ts, int ng, uint32_t stride, std::vector<uint32_t> &rows)
+{
+	rows.clear();
+	if (ts.streams <= 0)
+		return true;
+	if (ng <= 0 || 64 % ng != 0 || ts.streams % ng != 0 || ts.tok_off.size() != (size_t)ts.streams + 1 || stride == 0) {
+		sa_set_error("row streams: %d streams in slots of %d, stride %u", ts.streams, ng, stride);
+		return false;
+	}
+	const int g = 64 / ng;
+	const int64_t total = sa_row_stream_at(ts.tok_off[(size_t)ts.streams], ts.streams) - SA_ROW_FRONT;
+	if (total * 4 > (int64_t)1 << 31) { /* (the kernel addresses them with 32-bit byte offsets from the copy's base) */
+		sa_set_error("row streams: store too large for 32-bit byte offsets");
+		return false;
+	}
+	rows.assign((size_t)total, (uint32_t)SA_CODE_NOP * stride);
+	for (int32_t s = 0; s < ts.streams; s++) {
+		const int32_t at = ts.tok_off[(size_t)s], padded = ts.tok_off[(size_t)s + 1] - at;
+		const int64_t p0 = sa_row_stream_at(at, s); /* position 0 of the stream */
+		const int64_t lo = p0 - SA_ROW_FRONT, hi = sa_row_stream_at(ts.tok_off[(size_t)s + 1], s + 1) - SA_ROW_FRONT; /* its region */
+		/* the slot's streams are padded alike to 16 (nblk + 2) positions (sa_token_blocks) */
+		const int32_t nblk = padded / 16 - 2;
+		if (padded % 16 != 0 || nblk < 1 || p0 - (g - 1) < lo || p0 + 16 * (nblk + 1) + 15 >= hi || lo < 0 || hi > total) {
+			sa_set_error("row streams: the windows of stream %d (%d positions, %d-lane groups) leave its region", s, padded, g);
+			return false;
+		}
+		for (int32_t p = 0; p < padded; p++)
+			rows[(size_t)(p0 + p)] = (uint32_t)ts.tok[(size_t)at + (size_t)p] * stride;
+	}
+	return true;
+}
+
+static const char *const TOO_LARGE ="packed range too large for one launch; split it into smaller ranges";
 
 bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int world, bool share_host, SaHostPlan &plan)
 {

@@ -117,6 +117,19 @@ inline int32_t sa_token_blocks(int32_t smax, int g) { return ((smax + g - 1 + 15
 /* codes / off: the ARRANGED copy (position order, terminators included); false + sa_set_error when it does not fit 32-bit offsets */
 bool sa_build_tokens(const uint8_t *codes, const int32_t *off, int32_t num, const SaArrKey &key, SaTokenStreams &ts);
 
+/* Row streams of one arranged copy for one profile row stride (DESIGN 4.2 "row streams"): per stream position the BYTE
+ * OFFSET of its profile row, code x stride, as u32 -- what the lean way of a class adds to a lane's profile address, ready
+ * to be loaded into registers sixteen positions at a time.  SEP and NOP map to their rows like any other code.  Every
+ * stream keeps the tail padding of ts.tok and gets a front pad of SA_ROW_FRONT NOP positions, because lane `lig` of a group
+ * is `lig` positions behind its first lane and its window of block 0 starts at position -lig:
+ *   position p (>= -SA_ROW_FRONT) of stream s is rows[sa_row_stream_at(tok_off[s], s) + p]
+ * -- no second offset array, and `mine` / `any` of ts serve unchanged.  The windows the kernel loads are positions
+ * [16 b - lig, 16 b - lig + 15] for lig = 0..G-1 and b = 0..nblk + 1 (nblk blocks, the loads run a block ahead and the last
+ * step of a block reads the first position of the next); the builder checks every stream's against its region. */
+inline int64_t sa_row_stream_at(int32_t tok_off, int32_t stream) { return (int64_t)tok_off + (int64_t)SA_ROW_FRONT * (stream + 1); }
+/* ng: streams per wave slot (the key's); false + sa_set_error when a window would leave its stream's region */
+bool sa_build_row_streams(const SaTokenStreams &ts, int ng, uint32_t stride, std::vector<uint32_t> &rows);
+
 struct SaHostClass {
 	int cls = 0;
 	int32_t ncols = 0, ntiles = 0;

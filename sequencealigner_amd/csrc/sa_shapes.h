@@ -107,6 +107,16 @@ enum : int { SA_PK_CLASS0 = SA_SYS_NCLASSES + 1, SA_PK16_CLASS0 = SA_PK_CLASS0 +
  * profiles/r03a_*).  8-lane groups: KLO = 1, 9, 17; 16-lane groups: KLO = 13, 21, ... 61.  The registers of a bundle are
  * those of its largest K (K <= 16: <= 127 VGPRs for every method, four waves per SIMD as before). */
 #define SA_PK_BUNDLE 8
+/* Row streams (sa_plan.h: sa_build_row_streams): the lean way of a class takes its profile-row offsets from global memory
+ * straight into registers instead of through the LDS token ring (sa_systolic_pk.inc: do_block).  1: NW, 8-lane groups,
+ * K <= 16 (the bundles KLO = 1 and 9); 0: every class keeps the ring.  Host and kernel ask the same predicate: the host
+ * builds a class's row streams exactly where the kernel reads them. */
+#ifndef SA_PK_REG_TOKENS
+#define SA_PK_REG_TOKENS 1
+#endif
+SA_HD constexpr bool sa_pk_reg_tokens(int method, int g, int k) { return SA_PK_REG_TOKENS && method == SA_METHOD_NW && g == 8 && k <= 16; }
+#define SA_ROW_FRONT 16 /* NOP positions in front of every row stream: a group's last lane starts G - 1 positions behind its first */
+SA_HD constexpr uint32_t sa_pk_row_stride(int k) { return (uint32_t)((k + 3) / 4) * 256u; } /* bytes between two rows of a class's profile */
 struct SaArranged { /* one arranged copy of the row store (sa_plan.cpp: sa_arrange_rows); rows = 0: none */
 	const uint8_t *codes;
 	const int32_t *off;    /* num+1 offsets into codes by position */
@@ -118,6 +128,9 @@ struct SaArranged { /* one arranged copy of the row store (sa_plan.cpp: sa_arran
 	const int32_t *tok_off;  /* stream -> start in tok (a multiple of 16) */
 	const uint16_t *mine;    /* terminator mask per block of a stream   */
 	const uint16_t *any;     /* ... OR-ed over the streams of a wave slot */
+	/* row streams of the copy for the row stride of the class that holds this entry (sa_plan.h: sa_build_row_streams), or
+	 * nullptr: the class keeps the token ring (sa_pk_reg_tokens) or tok is nullptr */
+	const uint32_t *rowoff;
 };
 struct SaPkClassArgs { /* one class of a bundle launch, in device memory */
 	const int32_t *jlist;     /* columns (ascending) of the class                                        */

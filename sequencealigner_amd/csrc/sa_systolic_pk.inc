@@ -66,7 +66,9 @@
  * they are 16 different slots, with 8-lane groups because the two interleaved groups of a DPP row (same slots) read
  * their own copy.  The profile (26 KB at K = 13..16) is shared by the SA_PK_WPB waves of a workgroup.  Tokens: u16 profile-row offsets in a per-group ring (duplicated, no wrap); a lane
  * reads ONE token per step with an immediate offset two steps ahead of its use -- no window registers, no
- * per-step address arithmetic, and the row address is a plain v_add_u32.
+ * per-step address arithmetic, and the row address is a plain v_add_u32.  (NW, 8-lane groups, K <= 16, full tiles of an
+ * arranged level: no ring at all -- the row offsets come from the level's row streams in global memory straight into
+ * registers, sixteen per lane and block; SA_PK_REG_TOKENS, see REGT in pk_tile.)
  *
  * Tiles.  A workgroup-tile = (column pair, SA_PK_WPB * 8 row streams of up to A.chunk sequences).  Rows run over the
  * union of the two columns' row ranges; a score is stored only where its pair belongs to the packed range.  Tiles are
@@ -337,6 +339,7 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 	/* token streams of the level the tile streams (sa_plan.h: SaTokenStreams), or none: see the row streams below */
 	const uint16_t *tk_tok = nullptr, *tk_mine = nullptr, *tk_any = nullptr;
 	const int32_t *tk_off = nullptr;
+	const uint32_t *tk_rows = nullptr; /* row streams of that level for this class's row stride (REGT below) */
 	{
 		const int32_t lvrows[SA_PK_SORT_LEVELS] = { uload(&A.lvp[0].rows), uload(&A.lvp[1].rows), uload(&A.lvp[2].rows),
 							    uload(&A.lvp[3].rows) };
@@ -352,6 +355,7 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			tk_off = uniform_ptr(L.tok_off);
 			tk_mine = uniform_ptr(L.mine);
 			tk_any = uniform_ptr(L.any);
+			tk_rows = uniform_ptr(L.rowoff);
 			sort_rows = lvrows[0]; /* (then the level's own, without a dynamic register index) */
 #pragma unroll
 			for (int k = 1; k < SA_PK_SORT_LEVELS; k++)
@@ -492,19 +496,33 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 	 * end-of-stream select), one multiply scales both, and the terminator masks are loaded instead of balloted.  One
 	 * wave-uniform branch per block picks the way; the sixteen steps exist once. */
 	/* (an integer in a scalar register: as a bool it lives in a lane mask and every block pays a v_cndmask + v_cmp to test it) */
-	const int32_t lean = __builtin_amdgcn_readfirstlane(tk_tok != nullptr ? 1 : 0);
+	/* REGT: the lean way of this class takes its row offsets from the level's ROW STREAMS (sa_plan.h: sa_build_row_streams)
+	 * straight into registers -- sixteen u32 byte offsets per lane and block, T(s) = that of stream position 16 blk + s - lig,
+	 * four 16-byte loads at scalar base + constant lane offset, each issued into the registers of the quad the steps have
+	 * just used up -- and the step's row address is lane_prof + T(s + 1).  No ring, no scaling, no per-step LDS read, and the
+	 * terminator mask is ONE dword spanning the previous and the current block, so the event path tests constant bits.  The
+	 * host builds the row streams of exactly these classes (sa_shapes.h: sa_pk_reg_tokens). */
+	constexpr bool REGT = sa_pk_reg_tokens(METHOD, G, K);
+	static_assert(!REGT || TSHIFT == 0, "a row stream holds byte offsets");
+	const int32_t lean = __builtin_amdgcn_readfirstlane(tk_tok != nullptr && (!REGT || tk_rows != nullptr) ? 1 : 0);
 	/* its three: bw_a = byte offset of this lane's tokens of block 0 in the token copy, bw_b = that of its stream's masks,
 	 * bw_c = LDS byte offset at which it writes its tokens of a block 0 mod 4 (first ring copy) */
 	const uint16_t *tk_any_w = nullptr;
 	if (lean) {
 		const int32_t s0 = i_begin / ch_full + gw; /* the wave's first stream (i_begin is a multiple of the chunk) */
 		const uint32_t o_w = (uint32_t)uload(tk_off + s0), o_g = (uint32_t)tk_off[s0 + grp];
-		bw_a = 2u * o_g + (G == 8 ? 4u * (uint32_t)(r16 >> 1) : 2u * (uint32_t)r16);
 		bw_b = o_g >> 3; /* u16 per block: 2 (o_g / 16) bytes */
 		tk_any_w = tk_any + (o_w >> 4) / NG;
-		/* (with the offset of the rings folded in: derived from the ring READ base the write address is two instructions per
-		 * block instead of one) */
-		bw_c = (uint32_t)(WPB * OUT_HALFS * 2 + 2 * (wv * (NG * GSTRIDE) + grp * GSTRIDE + fpos(0)));
+		if (REGT) {
+			/* byte offset of this lane's window of block 0 in the row streams: position -lig of its stream, which starts
+			 * behind the front pads of the streams before it and its own (sa_plan.h: sa_row_stream_at) */
+			bw_a = 4u * (o_g + (uint32_t)SA_ROW_FRONT * (uint32_t)(s0 + grp + 1) - (uint32_t)lig);
+		} else {
+			bw_a = 2u * o_g + (G == 8 ? 4u * (uint32_t)(r16 >> 1) : 2u * (uint32_t)r16);
+			/* (with the offset of the rings folded in: derived from the ring READ base the write address is two instructions
+			 * per block instead of one) */
+			bw_c = (uint32_t)(WPB * OUT_HALFS * 2 + 2 * (wv * (NG * GSTRIDE) + grp * GSTRIDE + fpos(0)));
+		}
 	}
 	/* The loads take the address form (uniform base in scalar registers + 32-bit lane offset): the base moves with the block
 	 * in scalar arithmetic and the lane offset never changes.  The empty statement makes the offset a new value (in place)
@@ -520,10 +538,30 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 		asm volatile("" : "+v"(bw_b));
 		return *reinterpret_cast<const uint16_t *>(b + bw_b);
 	};
+	/* REGT: quad qd = T(4 qd .. 4 qd + 3) of a block, one global_load_dwordx4 (the address is 4-byte aligned); the base moves
+	 * 64 bytes per block in scalar arithmetic */
+	typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+	typedef uint32_t u32_a2 __attribute__((aligned(2)));
+	auto reg_load = [&](int32_t blk, int qd) -> u32x4 {
+		const uint8_t *const b = reinterpret_cast<const uint8_t *>(tk_rows) + (size_t)(uint32_t)(blk << 6);
+		asm volatile("" : "+v"(bw_a));
+		return *reinterpret_cast<const u32x4_a4 *>(b + bw_a + 16 * qd);
+	};
+	/* ... and the stream's terminator masks of blocks blk - 1 (low half) and blk (high half) as one dword, blk >= 1 */
+	auto reg_mine = [&](int32_t blk) -> uint32_t {
+		const uint8_t *const b = reinterpret_cast<const uint8_t *>(tk_mine) + (size_t)(uint32_t)((blk << 1) - 2);
+		asm volatile("" : "+v"(bw_b));
+		return *reinterpret_cast<const u32_a2 *>(b + bw_b);
+	};
 	/* (every lane loads the wave's mask; it becomes scalar -- lean_any_s -- a block later: right behind the load the
 	 * readfirstlane would wait for it) */
 	auto lean_any = [&](int32_t blk) -> uint32_t { return (uint32_t)tk_any_w[blk]; };
 	auto lean_any_s = [&](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+	/* REGT: the wave's mask of block blk >= 1 as the HIGH half of the dword that starts at block blk - 1 (no entry past the
+	 * slot's last is read), made scalar and shifted down in scalar arithmetic: a u16 load that crosses a basic block costs a
+	 * v_and for its upper half */
+	auto reg_any = [&](int32_t blk) -> uint32_t { return *reinterpret_cast<const u32_a2 *>(tk_any_w + (blk - 1)); };
+	auto reg_any_s = [&](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v) >> 16; };
 	/* both tokens of the dword scaled at once: code < 64 and code * TUNIT < 65536, nothing carries into the upper half */
 	auto lean_ring = [&](int32_t blk, uint32_t raw) {
 		const uint32_t w = __umul24(raw, TUNIT);
@@ -591,8 +629,9 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 
 	/* ---- prologue: empty ring, block 0 in the ring, block 1 in flight ---- */
 	__syncthreads(); /* (every wave has read the staged columns out of the ring storage) */
-	for (int k = lane; k < NG * GSTRIDE; k += 64)
-		s_ring[k] = (uint16_t)NOPWORD;
+	if (!(REGT && lean)) /* (the row-stream way has no ring; a tile that follows in this workgroup clears its own) */
+		for (int k = lane; k < NG * GSTRIDE; k += 64)
+			s_ring[k] = (uint16_t)NOPWORD;
 	__syncthreads(); /* profile complete (all waves), ring cleared */
 	/* Gotoh: the first sequence starts like after a terminator at stream position -1 */
 	/* ev_hi: positions of the current block at which some group of the wave has a terminator (16 bits); ev_lo: the same
@@ -600,8 +639,17 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 	uint32_t ev_lo = METHOD == SA_METHOD_GA ? 0x8000u : 0u, ev_hi;
 	/* gm: bit s + 2 = my group's token at position s of the current block is a terminator; bits 1, 0 = positions 15, 14
 	 * of the previous block */
+	/* REGT, lean: gm is the mask dword instead -- bit 16 + s = position s of the current block, bits 0..15 the previous block */
 	uint32_t gm, gmask;
-	if (lean) {
+	u32x4 TQ[4] = {}; /* REGT, lean: T(s) = TQ[s >> 2][s & 3] */
+	if (REGT && lean) {
+#pragma unroll
+		for (int qd = 0; qd < 4; qd++)
+			TQ[qd] = reg_load(0, qd);
+		gmask = lean_mine(0);
+		ev_hi = lean_any_s(lean_any(0));
+		gm = (gmask << 16) | (METHOD == SA_METHOD_GA ? 0x8000u : 0u);
+	} else if (lean) {
 		lean_ring(0, lean_load(0));
 		gmask = lean_mine(0);
 		ev_hi = lean_any_s(lean_any(0));
@@ -624,7 +672,9 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 	int raw_next[TPL];
 	uint32_t mask_pf = 0, any_next = 0;
 	uint32_t &mask_next = TPL == 2 ? reinterpret_cast<uint32_t &>(raw_next[TPL - 1]) : mask_pf;
-	if (lean) {
+	if (REGT && lean) {
+		any_next = reg_any(1); /* (the stream's mask dword of a block is loaded in the block before it: do_block) */
+	} else if (lean) {
 		raw_next[0] = (int)lean_load(1);
 		mask_next = lean_mine(1);
 		any_next = lean_any(1);
@@ -642,12 +692,21 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 		for (int p = 0; p < PARTS; p++)
 			P[p] = *reinterpret_cast<const uint4 *>(row + p * PARTSTRIDE);
 	};
-	const uint16_t *rb0 = ring_base(0);
-	uint32_t tk_cur = rb0[0], tk_nxt = rb0[1];
+	uint32_t tk_cur = 0, tk_nxt = 0;
+	if (REGT && lean) {
+		tk_cur = TQ[0][0];
+	} else {
+		const uint16_t *rb0 = ring_base(0);
+		tk_cur = rb0[0], tk_nxt = rb0[1];
+	}
 	uint4 P[PARTS];
 	prof_row(tk_cur, P);
 
-	auto do_block = [&](const int32_t blk) __attribute__((always_inline)) {
+	/* way: std::true_type = the row-stream way (REGT, lean tiles), std::false_type = the ring (lean or derived).  The steps
+	 * exist once per way. */
+	auto do_block = [&](auto way, const int32_t blk) __attribute__((always_inline)) {
+		constexpr bool RW = decltype(way)::value;
+		constexpr int MB = RW ? 16 : 2; /* bit of gm that stands for position 0 of the current block */
 		if (A.rotate_prio) { /* (see the bundle kernel: fairness among the persistent waves of a SIMD) */
 			switch (((uint32_t)A.rotate_prio + (uint32_t)blk) & 3u) {
 			case 0: __builtin_amdgcn_s_setprio(0); break;
@@ -662,11 +721,22 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			METHOD == SA_METHOD_GA ? (ev_hi | (ev_hi << 1) | (ev_hi << 2) | (ev_lo >> 15) | (ev_lo >> 14)) : ev_hi;
 		const uint32_t ev = ((ev_lo >> (16 - (G - 1))) | (ev_hi << (G - 1)) | ev_in) & 0xffffu;
 		/* next block's tokens go into the ring while this block computes */
-		uint32_t gm_next, evn; /* gm and ev_hi of the next block */
+		uint32_t gm_next = 0, evn; /* gm and ev_hi of the next block */
 		/* (everything in flight was loaded a block ago and is used now: said once, here, the wait costs nothing, and the
-		 * compiler's bookkeeping of the two ways' loads does not end in a wait for the NEW loads further down) */
-		__builtin_amdgcn_s_waitcnt(0x0f70); /* vmcnt(0) */
-		if (lean) {
+		 * compiler's bookkeeping of the two ways' loads does not end in a wait for the NEW loads further down.  Not on the
+		 * row-stream way: the quad loaded behind step 15 of the block before is still in flight and first read at step 11;
+		 * the masks were loaded in front of it, and loads return in order) */
+		if constexpr (!RW)
+			__builtin_amdgcn_s_waitcnt(0x0f70); /* vmcnt(0) */
+		if constexpr (RW) {
+			/* (the next block's mask dword is in flight for this block only and becomes gm at its end: with a block of
+			 * idling as gm_next, as on the ring way, three registers rotate through the two blocks of a trip and the back edge
+			 * pays two copies) */
+			evn = reg_any_s(any_next);
+			asm volatile("" ::: "memory"); /* (what was in flight is consumed before its registers are loaded again) */
+			mask_next = reg_mine(blk + 1);
+			any_next = reg_any(blk + 2);
+		} else if (!REGT && lean) { /* (REGT: the lean tiles of this class never come this way) */
 			lean_ring(blk + 1, (uint32_t)raw_next[0]);
 			gm_next = (mask_next << 2) | (gm >> 16);
 			evn = lean_any_s(any_next);
@@ -688,7 +758,8 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			for (int u = 0; u < TPL; u++)
 				raw_next[u] = load_block(blk + 2, u);
 		}
-		const uint16_t *rbase = ring_base(blk);
+		const uint16_t *rbase = RW ? nullptr : ring_base(blk);
+		auto T = [&](int s) -> uint32_t { return TQ[(s >> 2) & 3][s & 3]; };
 
 		/* One step of the block.  has_events = false is the same step without the event test: a block in which no
 		 * terminator enters or leaves any group of the wave (ev == 0: ~70 % of the blocks of cfg 2) can run sixteen steps as ONE
@@ -704,7 +775,7 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			if (decltype(has_events)::value && __builtin_expect((ev >> s) & 1u, 0)) { /* wave-uniform, rare */
 				/* the empty volatile statement keeps this a scalar branch (see sa_systolic_kernel.inc) */
 				asm volatile("" ::: "memory");
-				if ((gm >> (s + 2)) & 1u) { /* a terminator enters my group: shift the group's frame down by DELTA */
+				if ((gm >> (s + MB)) & 1u) { /* a terminator enters my group: shift the group's frame down by DELTA */
 					/* One saturating subtraction per register (v_pk_sub_u16 clamp).  Whatever it clamps to 0 is stale
 					 * -- at least PK_LIVE shifts old, see the header -- and has lost every max of a live row already.
 					 * Only rows past the end of a stream (bubbles) can then see the Gotoh / SW subtractions wrap; their
@@ -735,16 +806,16 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 					 * corner only if column 0 is a real column; if it is padding the corner reaches the first real
 					 * column through the padding (profile tweak) and column 0 must see the plain border -- a padding
 					 * entry is 0 here, not the s32 kernels' -128, so it would not lose.  Row t + 2: plain again. */
-					if ((gm >> (s + 2)) & 1u) {
+					if ((gm >> (s + MB)) & 1u) {
 						vl[(s + 1) & 1] = vbase;
 						vcur = vbase + q2;
-					} else if ((gm >> (s + 1)) & 1u) {
+					} else if ((gm >> (s + MB - 1)) & 1u) {
 						vl[(s + 1) & 1] = vbase + (q2 & cmask2);
-					} else if ((gm >> s) & 1u) {
+					} else if ((gm >> (s + MB - 2)) & 1u) {
 						vcur = vbase;
 					}
 				}
-				if (lig == G - 1 && tk_cur == SEPWORD) { /* a score pair leaves the pipeline */
+				if (lig == G - 1 && (RW ? T(s) : tk_cur) == SEPWORD) { /* a score pair leaves the pipeline */
 					/* global: the sequence's last column; local: the best of all its cells, back from the row domain of
 					 * its terminator row (that row's stream position times e) */
 					const uint32_t v = METHOD == SA_METHOD_SW ? carry : V[K - 1];
@@ -757,13 +828,16 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			}
 			/* token two steps ahead (positions 16, 17 belong to the next block, already in the ring).  Loaded BEHIND the event
 			 * branch: load and the step's end then sit in one basic block (see SA_PK_OPAQUE_TOKEN below) */
-			const uint32_t tk_far = rbase[s + 2];
+			uint32_t tk_far = 0;
+			if constexpr (!RW)
+				tk_far = rbase[s + 2];
 			const uint32_t vprev = vl[PAIRED ? 0 : (s + 1) & 1];
 			/* Diagonal adds are made just in time (column q + 1's from the still-old V[q]), and a 16-byte part of the
 			 * profile row is re-loaded for the NEXT step as soon as its four columns have been consumed -- no d[] array,
 			 * no second profile buffer.  A packed op that reads the result of the packed op right before it costs a
 			 * wait state, so independent work of the next columns sits between the dependent ops of the chain. */
-			const uint8_t *const row_next = lane_prof + (tk_nxt << TSHIFT);
+			/* (the row-stream way: step 15 reads the next block's T(0), loaded into quad 0 behind step 3) */
+			const uint8_t *const row_next = lane_prof + (RW ? T(s + 1) : tk_nxt << TSHIFT);
 			auto reload = [&](int q_done) { /* columns 0..q_done are consumed */
 				if ((q_done & 3) == 3 || q_done == K - 1) {
 					P[q_done >> 2] = *reinterpret_cast<const uint4 *>(row_next + (q_done >> 2) * PARTSTRIDE);
@@ -926,6 +1000,11 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 				}
 				xout = x;
 			}
+			if constexpr (RW) {
+				/* the quad whose last offset was this step's own is used up: the next block's, into the same registers */
+				if ((s & 3) == 3)
+					TQ[s >> 2] = reg_load(blk + 1, s >> 2);
+			} else {
 			tk_cur = tk_nxt;
 #if SA_PK_OPAQUE_TOKEN
 			/* The token travels through the loop as a 32-bit value the optimiser cannot narrow back to the u16 it was loaded
@@ -941,6 +1020,7 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 #else
 			tk_nxt = tk_far;
 #endif
+			}
 		};
 		/* (where the registers allow it: the quiet block's schedule holds more rows of the profile in flight -- NW, K <= 16:
 		 * 92 -> 128 VGPRs, still four waves per SIMD; NW K = 17..24 would go 119 -> 167, Gotoh / SW K = 9..16 to 163 / 165:
@@ -955,16 +1035,28 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 			for (int s = 0; s < 16; s++)
 				step(std::true_type{}, s);
 		}
-		gm = gm_next;
+		if constexpr (RW)
+			gm = mask_next;
+		else
+			gm = gm_next;
 		ev_lo = ev_hi;
 		ev_hi = evn;
 	};
 	const unsigned long long ph1 = A.stamps ? __builtin_amdgcn_s_memtime() : 0ull; /* diagnostics: end of the prologue */
 	/* two blocks per trip: the compiler leaves a register copy per loop-carried DP value on the back edge */
-	for (int32_t blk2 = 0; blk2 < nblk; blk2 += 2) {
-		do_block(blk2);
-		if (blk2 + 1 < nblk)
-			do_block(blk2 + 1);
+	if (REGT && lean) {
+		if constexpr (REGT)
+			for (int32_t blk2 = 0; blk2 < nblk; blk2 += 2) {
+				do_block(std::true_type{}, blk2);
+				if (blk2 + 1 < nblk)
+					do_block(std::true_type{}, blk2 + 1);
+			}
+	} else {
+		for (int32_t blk2 = 0; blk2 < nblk; blk2 += 2) {
+			do_block(std::false_type{}, blk2);
+			if (blk2 + 1 < nblk)
+				do_block(std::false_type{}, blk2 + 1);
+		}
 	}
 	if (A.stamps && threadIdx.x == 0) { /* diagnostics: shader clock at the end of the prologue and of the main loop, steps */
 		A.stamps[3 * (size_t)A.nlocal + 3 * (size_t)A.stamp_u + 0] = ph1;

@@ -17,6 +17,7 @@ asm = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-s
                       *defs, "-S", str(csrc / tu), "-o", "-"], capture_output=True, text=True).stdout
 name = f"_ZN12_GLOBAL__N_123sa_k_systolic_pk_bundleILi{mi}ELi{g}ELi{klo}ELb{f16}EEEv9SaSysArgs"
 body = asm[asm.index(name + ":"):]
+tail = body[body.index("s_endpgm"):]
 body = body[:body.index("s_endpgm")]
 ops = [l.split()[0] for l in body.split("\n") if l.strip() and not l.strip().startswith((";", ".")) and not l.strip().endswith(":")]
 c = collections.Counter(ops)
@@ -28,6 +29,9 @@ for k in ("flat_load_ubyte", "flat_load_dword", "global_load_ubyte", "global_loa
     print(f"  {k:22s} {c.get(k, 0)}")
 flat = sum(v for k, v in c.items() if k.startswith("flat_"))
 print("FLAT memory instructions:", flat, "(must be 0)" if flat else "")
+for key in ("codeLenInByte", "ScratchSize"):
+    mm = re.search(r"; " + key + r"\s*[=:]\s*(\d+)", tail)
+    print(key, mm.group(1) if mm else "?")
 for key in ("vgpr_count", "sgpr_count", "sgpr_spill_count", "vgpr_spill_count"):
     for mm in re.finditer(r"\.name:\s+" + name + r"\n(?:.*\n)*?\s+\." + key + r":\s+(\d+)", asm):
         print(key, mm.group(1))
@@ -36,8 +40,10 @@ if m == "nw" and f16:
     # keep, per K, the most frequent shape among the pieces with exactly K maxima (15 of the 16 steps of a block)
     cuts = [i for i, o in enumerate(ops) if o == "v_mov_b32_dpp"]
     shapes = collections.defaultdict(collections.Counter)
+    valus = collections.defaultdict(collections.Counter)
     for a, b in zip(cuts, cuts[1:]):
         sc = collections.Counter(ops[a:b])
+        valus[sc["v_pk_maximum3_f16"]][sum(v for o, v in sc.items() if o.startswith("v_"))] += 1
         shapes[sc["v_pk_maximum3_f16"]][(b - a, sum(v for o, v in sc.items() if o.startswith("v_")), sc["s_nop"], sc["v_lshl_add_u64"],
                                          sc["v_mov_b32_e32"], sc["s_waitcnt"])] += 1
     print("step body per K (most frequent of the steps found): instructions, VALU, s_nop, v_lshl_add_u64, v_mov_b32, s_waitcnt")
@@ -45,3 +51,6 @@ if m == "nw" and f16:
         if shapes.get(k):
             (n, valu, nop, add64, mov, wait), cnt = shapes[k].most_common(1)[0]
             print(f"  K = {k:2d}: {n:3d} instructions, {valu:2d} VALU, s_nop {nop:2d}, v_lshl_add_u64 {add64}, v_mov_b32 {mov}, s_waitcnt {wait}   ({cnt} steps of this shape)")
+            # a piece that runs from the last step of a block into the first of the next carries that block's work outside the
+            # steps: its VALU count less the plain step's (the main loop is two blocks per way; cold event paths lie elsewhere)
+            print("          VALU of every piece with K maxima (VALU: pieces):", ", ".join(f"{v}: {n}" for v, n in sorted(valus[k].items())))
