@@ -658,10 +658,32 @@ static int open_output(const char *path, const struct sa_host_store *s, unsigned
 	return 0;
 }
 
+/* a 1-D dataset of the store's sequences as variable-length C strings (src/io/format/hdf5.c:36-68); 0 on success */
+static int write_sequences(hid_t file, const char *name, const struct sa_host_store *s)
+{
+	const size_t dim = (size_t)s->in.num;
+	const char **strs = malloc(sizeof(*strs) * dim);
+	if (!strs)
+		return fail("Out of memory allocating output sequence data");
+	for (size_t k = 0; k < dim; k++)
+		strs[k] = (const char *)(s->in.seqs + s->in.meta[k].off);
+	hsize_t sd[1] = { dim };
+	hid_t sspace = H5Screate_simple(1, sd, NULL);
+	hid_t stype = H5Tcopy(H5T_C_S1);
+	H5Tset_size(stype, H5T_VARIABLE);
+	hid_t sset = H5Dcreate2(file, name, stype, sspace, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+	herr_t st = sset < 0 ? -1 : H5Dwrite(sset, stype, H5S_ALL, H5S_ALL, H5P_DEFAULT, strs);
+	if (sset >= 0)
+		H5Dclose(sset);
+	H5Sclose(sspace);
+	H5Tclose(stype);
+	free(strs);
+	return st < 0 ? fail("Failed to write sequence data to HDF5 dataset") : 0;
+}
+
 /* the file and /sequences (src/io/format/hdf5.c:14-68); 0 on success: *file_out open */
 static int create_with_sequences(const char *path, const struct sa_host_store *s, hid_t *file_out)
 {
-	const size_t dim = (size_t)s->in.num;
 	hid_t fapl = H5Pcreate(H5P_FILE_ACCESS);
 	H5Pset_libver_bounds(fapl, H5F_LIBVER_LATEST, H5F_LIBVER_LATEST);
 	H5Pset_alignment(fapl, 4096, 4096);
@@ -669,29 +691,9 @@ static int create_with_sequences(const char *path, const struct sa_host_store *s
 	H5Pclose(fapl);
 	if (file < 0)
 		return fail("Failed to create HDF5 file: %s", path);
-
-	/* /sequences: 1-D, N variable-length C strings */
-	const char **strs = malloc(sizeof(*strs) * dim);
-	if (!strs) {
+	if (write_sequences(file, "/sequences", s)) {
 		H5Fclose(file);
-		return fail("Out of memory allocating output sequence data");
-	}
-	for (size_t k = 0; k < dim; k++)
-		strs[k] = (const char *)(s->in.seqs + s->in.meta[k].off);
-	hsize_t sd[1] = { dim };
-	hid_t sspace = H5Screate_simple(1, sd, NULL);
-	hid_t stype = H5Tcopy(H5T_C_S1);
-	H5Tset_size(stype, H5T_VARIABLE);
-	hid_t sset = H5Dcreate2(file, "/sequences", stype, sspace, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-	herr_t st = sset < 0 ? -1 : H5Dwrite(sset, stype, H5S_ALL, H5S_ALL, H5P_DEFAULT, strs);
-	if (sset >= 0)
-		H5Dclose(sset);
-	H5Sclose(sspace);
-	H5Tclose(stype);
-	free(strs);
-	if (st < 0) {
-		H5Fclose(file);
-		return fail("Failed to write sequence data to HDF5 dataset");
+		return 1;
 	}
 	*file_out = file;
 	return 0;
@@ -710,6 +712,24 @@ struct side_set {
 };
 #define SIDE_I32 H5T_STD_I32LE, H5T_NATIVE_INT32
 #define SIDE_I64 H5T_STD_I64LE, H5T_NATIVE_INT64
+
+/* the sets into an open file, in table order; the first failure ends it with its message */
+static int add_side_sets(hid_t file, const struct side_set *sets, int count)
+{
+	int rc = 0;
+	for (int d = 0; d < count && !rc; d++) {
+		if (sets[d].optional && !sets[d].data)
+			continue;
+		hid_t space = H5Screate_simple(sets[d].rank, sets[d].dims, NULL);
+		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
+		if (set < 0 || (sets[d].dims[0] && H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
+			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
+		if (set >= 0)
+			H5Dclose(set);
+		H5Sclose(space);
+	}
+	return rc;
+}
 
 /* The tail of every side writer.  create = 0: the sets are added to the finished file at `path`, whose other datasets stay as they
  * are; create = 1: a new file with /sequences of `s` and these sets, no /similarity_matrix.  The sets are created in table order
@@ -731,18 +751,7 @@ static int write_side_sets(const char *path, const struct sa_host_store *s, int 
 		if (file < 0)
 			return fail("Failed to open HDF5 file: %s", path);
 	}
-	int rc = 0;
-	for (int d = 0; d < count && !rc; d++) {
-		if (sets[d].optional && !sets[d].data)
-			continue;
-		hid_t space = H5Screate_simple(sets[d].rank, sets[d].dims, NULL);
-		hid_t set = H5Dcreate2(file, sets[d].name, sets[d].file_type, space, H5P_DEFAULT, H5P_DEFAULT, H5P_DEFAULT);
-		if (set < 0 || (sets[d].dims[0] && H5Dwrite(set, sets[d].mem_type, H5S_ALL, H5S_ALL, H5P_DEFAULT, sets[d].data) < 0))
-			rc = fail("Failed to write %s to HDF5", sets[d].name + 1);
-		if (set >= 0)
-			H5Dclose(set);
-		H5Sclose(space);
-	}
+	const int rc = add_side_sets(file, sets, count);
 	H5Fclose(file);
 	if (rc && create && remove_failed)
 		remove(path);
@@ -794,6 +803,62 @@ int sa_host_write_alignments(const char *path, const struct sa_host_store *s, in
 					  { "/neighbor_cigar_offsets", 1, { np + 1 }, SIDE_I64, offs, false },
 					  { "/neighbor_cigars", 1, { (hsize_t)runs }, H5T_STD_U32LE, H5T_NATIVE_UINT32, cigar, false } };
 	const int rc = write_side_sets(path, s, 0, false, sets, 3);
+	free(fields);
+	free(offs);
+	return rc;
+}
+
+/* --query: a file of its own with /sequences (the database), /query_sequences, /hit_indices and /hit_scores (M x k I32LE: the
+ * arrays of sa_hip_search), with `rect` also /query_scores (M x N I32LE), with `records` also /hit_alignment_records (M x k x 8),
+ * /hit_cigar_offsets (M k + 1 I64LE) and /hit_cigars (U32LE) in the format of the neighbour datasets; no /similarity_matrix.
+ * Checked before anything is opened: k in [1, min(N, SA_HIP_NEIGHBORS_MAX)], every index in [0, N).  A failed file is removed. */
+int sa_host_write_search(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
+			 const int32_t *index, const int32_t *score, const int32_t *rect, const struct sa_aln *records, const uint32_t *cigar,
+			 int64_t runs)
+{
+	if (!path || !db || !queries || !index || !score || (records && (runs < 0 || (runs > 0 && !cigar))))
+		return fail("Search data missing");
+	const size_t n = (size_t)db->in.num, m = (size_t)queries->in.num;
+	if (n < 1 || m < 1)
+		return fail("A search needs a database and queries");
+	if (k < 1 || k > SA_HIP_NEIGHBORS_MAX || (size_t)k > n)
+		return fail("Hit count must be between 1 and %d and at most the number of database sequences", SA_HIP_NEIGHBORS_MAX);
+	const size_t np = m * (size_t)k;
+	for (size_t t = 0; t < np; t++)
+		if (index[t] < 0 || (size_t)index[t] >= n)
+			return fail("Hit index %d of query %zu outside the %zu database sequences", index[t], t / (size_t)k, n);
+	int32_t *fields = NULL;
+	int64_t *offs = NULL;
+	if (records) {
+		fields = malloc(sizeof(int32_t) * 8 * np);
+		offs = malloc(sizeof(int64_t) * (np + 1));
+		if (!fields || !offs) {
+			free(fields);
+			free(offs);
+			return fail("Out of memory allocating alignment records");
+		}
+		for (size_t t = 0; t < np; t++) {
+			const struct sa_aln *r = records + t;
+			const int32_t f[8] = { r->score, r->a_begin, r->a_end, r->b_begin, r->b_end, r->columns, r->identities, r->cigar_len };
+			memcpy(fields + 8 * t, f, sizeof(f));
+			offs[t] = r->cigar_off;
+		}
+		offs[np] = runs;
+	}
+	const struct side_set sets[6] = { { "/hit_indices", 2, { m, (hsize_t)k }, SIDE_I32, index, false },
+					  { "/hit_scores", 2, { m, (hsize_t)k }, SIDE_I32, score, false },
+					  { "/query_scores", 2, { m, n }, SIDE_I32, rect, true },
+					  { "/hit_alignment_records", 3, { m, (hsize_t)k, 8 }, SIDE_I32, fields, true },
+					  { "/hit_cigar_offsets", 1, { np + 1 }, SIDE_I64, offs, true },
+					  { "/hit_cigars", 1, { (hsize_t)(records ? runs : 0) }, H5T_STD_U32LE, H5T_NATIVE_UINT32, cigar, !records } };
+	hid_t file;
+	int rc = create_with_sequences(path, db, &file);
+	if (!rc) {
+		rc = write_sequences(file, "/query_sequences", queries) || add_side_sets(file, sets, 6);
+		H5Fclose(file);
+		if (rc)
+			remove(path);
+	}
 	free(fields);
 	free(offs);
 	return rc;

@@ -83,6 +83,15 @@ int sa_host_write_neighbors(const char *path, const struct sa_host_store *s, int
  * /neighbor_cigars (`runs` uint32), added to the file at `path` (which sa_host_write_neighbors has written to). */
 int sa_host_write_alignments(const char *path, const struct sa_host_store *s, int32_t k, const struct sa_aln *records,
 			     const uint32_t *cigar, int64_t runs);
+/* --query: the one writer of a search.  A NEW file at `path` with /sequences (the database as searched, N), /query_sequences (M),
+ * /hit_indices and /hit_scores (M x k I32LE, the arrays of sa_hip_search: row q lists the k best database sequences of query q,
+ * indices into /sequences); with `rect` (or NULL) also /query_scores (M x N I32LE, rect[q * N + d]); with `records` (or NULL) also
+ * /hit_alignment_records (M x k x 8), /hit_cigar_offsets (M k + 1 I64LE) and /hit_cigars (`runs` U32LE), in the format of the
+ * neighbour datasets (a = the query, b = its hit).  No /similarity_matrix.  k outside [1, min(N, 64)] or an index outside [0, N)
+ * give an error before anything is opened; a file that fails later is removed. */
+int sa_host_write_search(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
+			 const int32_t *index, const int32_t *score, const int32_t *rect, const struct sa_aln *records, const uint32_t *cigar,
+			 int64_t runs);
 /* --min-score: /edge_offsets (N + 1 I64LE), /edge_indices and /edge_scores (E = offsets[N] I32LE each; extent 0 when E = 0),
  * the CSR arrays of sa_hip_edges / sa_zjob_edges.  `create` as in sa_host_write_neighbors: 0 adds the three datasets to the
  * finished file at `path`, 1 writes a new file with /sequences and the three (--edges-only).  offsets[0] != 0, decreasing

@@ -27,8 +27,13 @@
  *             --identity DENOM   (the same selections from PERCENT IDENTITY in parts per million: identities of the canonical
  *             alignment of every pair, carried through one sweep on the device, over columns | shorter | longer | mean;
  *             /similarity_matrix stays raw: /identity_rule, /identity_scale)
+ *             --query FILE  --query-scores   (a search: the sequences of FILE against the input as the database, with -k the K best
+ *             database sequences of every query selected on the device: /query_sequences, /hit_indices and /hit_scores, with
+ *             --alignments /hit_alignment_records, /hit_cigar_offsets and /hit_cigars, with --query-scores /query_scores; only the
+ *             M x N query-database pairs are aligned, no /similarity_matrix)
  * Flow (main, one function per phase): options -> banner -> load + filter -> output plan -> the first pass (tile job | one selection only |
- * host matrix) -> per selection, in the order of the file: its second pass where the first left it unanswered, then its datasets -> -B report.
+ * host matrix | the search) -> per selection, in the order of the file: its second pass where the first left it unanswered, then its
+ * datasets (a search: its alignments, then its one file) -> -B report.
  * Exit code 1 with a usage hint on any failure (src/main.c:11-14).
  */
 #define _GNU_SOURCE
@@ -133,6 +138,9 @@ struct options {
 	bool identity;
 	int32_t pid_denom;
 	const char *pid_name;
+	/* --query FILE: a search of FILE's sequences against the input; -k is then the hits per query.  --query-scores: /query_scores too */
+	const char *query;
+	bool query_scores;
 };
 
 static void usage(const char *argv0)
@@ -221,6 +229,18 @@ static void usage(const char *argv0)
 	       "                           (900000: 90 %% identity).  /similarity_matrix, when written, STAYS RAW.  Not together\n"
 	       "                           with --normalize.  Writes /identity_rule (0 = columns, 1 = shorter, 2 = longer,\n"
 	       "                           3 = mean) and /identity_scale (1000000)\n"
+	       "      --query FILE         A search: the M sequences of FILE (same formats, same residue checks) as queries against the\n"
+	       "                           N of the input as the database.  Needs -k K, 1 <= K <= min(N, 64).  Only the M x N\n"
+	       "                           query-database pairs are aligned: no all-vs-all, no /similarity_matrix.  Writes\n"
+	       "                           /query_sequences (M) beside /sequences, /hit_indices and /hit_scores (M x K: the K best\n"
+	       "                           database sequences of every query, score descending, index ascending; indices into\n"
+	       "                           /sequences as written, so after -f, which filters the database and never the queries).\n"
+	       "                           With --alignments: /hit_alignment_records, /hit_cigar_offsets and /hit_cigars in the\n"
+	       "                           format of the neighbor datasets (a = the query, b = its hit).  The database is the row\n"
+	       "                           and the query the column sequence of the substitution matrix.  Not together with -z,\n"
+	       "                           the --*-only modes or any other selection (--min-score, --min-quantile, --linkage,\n"
+	       "                           --clusters, --clusters-quantile, --linkage-method, --quantiles, --normalize, --identity)\n"
+	       "      --query-scores       With --query: also /query_scores (M x N), every query-database score\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -282,7 +302,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "min-score", 5, true }, { "edges-only", 6, false }, { "linkage", 7, false }, { "clusters", 8, true },
 		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
 		     { "quantiles", 12, true }, { "normalize", 13, true }, { "identity", 14, true },
-		     { "linkage-method", 15, true }, { NULL, 0, false } };
+		     { "linkage-method", 15, true }, { "query", 16, true }, { "query-scores", 17, false }, { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -493,6 +513,8 @@ static int parse_args(int argc, char **argv, struct options *o)
 				}
 				break;
 			}
+			case 16: o->query = val; break;
+			case 17: o->query_scores = true; break;
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -602,6 +624,9 @@ struct run {
 	double t_quantity;
 	double t_write0; /* WRITE_OUT */
 	struct { int32_t *index, *score; bool done, second_pass; double seconds; } nb;
+	/* --query: the queries, the hits (M x K), with --query-scores the rectangle (M x N), with --alignments the M x K records */
+	struct sa_host_store queries;
+	struct { int32_t *index, *score, *rect; sa_alns *alns; double hits_seconds, gather_seconds; int32_t batches; } sr;
 	struct { double seconds; long long runs; } trace;
 	struct { /* the fractions' ranks: one select call answers all of them, where the matrix is */
 		int64_t ranks[SA_HIP_SELECT_MAX], below[SA_HIP_SELECT_MAX];
@@ -716,6 +741,16 @@ static enum q_call answer_quantiles(struct run *r, bool with_tree)
 	return call;
 }
 
+/* the first option given that a search (--query) does not go together with, or NULL: the --*-only modes, every selection from the
+ * all-vs-all matrix, and -z (a search has no chunked dataset) */
+static const char *query_conflict(const struct options *o)
+{
+	return o->neighbors_only ? "--neighbors-only" : o->edges_only ? "--edges-only" : o->linkage_only ? "--linkage-only"
+	     : o->min_q >= 0 ? "--min-quantile" : o->has_min_score ? "--min-score" : o->clusters_q >= 0 ? "--clusters-quantile"
+	     : o->has_clusters ? "--clusters" : o->has_method ? "--linkage-method" : o->linkage ? "--linkage" : o->nquant ? "--quantiles"
+	     : o->normalize ? "--normalize" : o->identity ? "--identity" : o->compression ? "-z, --compression" : NULL;
+}
+
 /* ---- the phases of main, in its order ------------------------------------------------------------------------------------------ */
 /* options, -l, validation in the reference's terms (src/bio/align.c:130-201, ga.c:70-88, output.c:126-148) and the scoring.
  * returns 0 ok, 1 error, 2 handled-and-exit-success */
@@ -748,6 +783,13 @@ static int set_up(int argc, char **argv, struct run *r)
 		ok = (err("Options -o, --output and -W, --no-write conflict"), false);
 	if (ok && !o->output && !o->no_write)
 		ok = (err("Missing required option: -o, --output"), false);
+	if (ok && o->query_scores && !o->query)
+		ok = (err("Option --query-scores requires --query"), false);
+	if (ok && o->query && !o->neighbors)
+		ok = (err("Option --query requires -k, --neighbors: the number of hits per query"), false);
+	if (ok && o->query && query_conflict(o))
+		ok = (err("Options --query and %s conflict: a search writes the hits of the queries and nothing selected from an all-vs-all matrix, "
+			  "which it never computes", query_conflict(o)), false);
 	if (ok && o->neighbors_only && !o->neighbors)
 		ok = (err("Option --neighbors-only requires -k, --neighbors"), false);
 	if (ok && o->alignments && !o->neighbors)
@@ -840,7 +882,9 @@ static void banner(const struct run *r)
 		info("Gap open: %d, extend: %d", r->sc.gap_opn, r->sc.gap_ext);
 	if (o->filter > 0.0f)
 		info("Filter threshold: %.1f%%", (double)o->filter * 100.0);
-	if (o->neighbors)
+	if (o->query)
+		info("Queries: %s, the %d best database sequences of each (no similarity matrix)", o->query, o->neighbors);
+	else if (o->neighbors)
 		info("Neighbors: %d per sequence%s", o->neighbors, o->neighbors_only ? " (no similarity matrix)" : "");
 	if (o->min_q >= 0)
 		info("Score graph: pairs that score at least the %g quantile of the scores%s", o->quantiles[o->min_q],
@@ -863,6 +907,34 @@ static void banner(const struct run *r)
 		info("Normalization: %s, in parts per million (the similarity matrix stays raw)", o->norm_name);
 	if (o->identity)
 		info("Percent identity over %s, in parts per million (the similarity matrix stays raw)", o->pid_name);
+}
+
+/* --query: the queries through the same reader and LUT as the input, never filtered; K against the database as filtered; room for the
+ * hits.  The pairs of the run are the M x N of the rectangle */
+static bool load_queries(struct run *r)
+{
+	const struct options *o = &r->o;
+	const double t0 = now();
+	if (sa_host_load(o->query, r->sc.lut, r->sc.gap_pen, o->dsv_column, o->dsv_has_header, &r->queries))
+		return failed(sa_host_error());
+	r->t_in += now() - t0;
+	stamp("queries loaded");
+	const size_t m = (size_t)r->queries.in.num;
+	info("Loaded %d query sequences", r->queries.in.num);
+	info("Average query length: %.2f", (double)r->queries.blob_bytes / (double)m - 1.0);
+	if ((size_t)o->neighbors > r->n) {
+		err("Hit count %d exceeds the %zu database sequences", o->neighbors, r->n);
+		fprintf(stderr, "Use %s -h, --help for usage information\n", r->argv0);
+		return false;
+	}
+	r->npairs = (long long)m * (long long)r->n;
+	r->sr.index = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+	r->sr.score = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+	if (o->query_scores)
+		r->sr.rect = malloc(sizeof(int32_t) * m * r->n);
+	if (!r->sr.index || !r->sr.score || (o->query_scores && !r->sr.rect))
+		return failed("Out of memory allocating search results");
+	return true;
 }
 
 /* the sequences, filtered, and what the selections need once their number is known: the ranks of the fractions, the quantity, room
@@ -893,6 +965,8 @@ static bool load_and_filter(struct run *r)
 	info("Average sequence length: %.2f", (double)store->blob_bytes / (double)store->in.num - 1.0);
 	r->n = (size_t)store->in.num;
 	r->npairs = (long long)r->n * ((long long)r->n - 1) / 2;
+	if (o->query)
+		return load_queries(r);
 
 	if (o->neighbors && (long long)o->neighbors > (long long)store->in.num - 1) {
 		err("Neighbor count %d exceeds the %d other sequences", o->neighbors, store->in.num - 1);
@@ -935,7 +1009,7 @@ static bool plan_output(struct run *r)
 	 * one writing thread (what flush_hdf5 leaves to H5Dwrite, src/io/format/hdf5.c:148-194) takes 41 CPU-minutes for config 5.
 	 * SA_HOST_CPU_DEFLATE=1 keeps zlib at exactly the level asked for (all cores, sa_host_write_hdf5). */
 	r->zchunk = sa_host_hdf5_chunk_dim(n);
-	r->no_matrix = o->neighbors_only || o->edges_only || o->linkage_only; /* the matrix never leaves the device */
+	r->no_matrix = o->neighbors_only || o->edges_only || o->linkage_only || o->query != NULL; /* the matrix never leaves the device, or never is */
 	r->device_deflate = !o->no_write && !r->no_matrix && n > 256 && !getenv("SA_HOST_MATRIX") &&
 			    (o->compression > 0 ? !getenv("SA_HOST_CPU_DEFLATE") && !getenv("SA_HOST_SERIAL_DEFLATE")
 						/* without -z the same walk returns the tiles as they are: H5Dwrite_chunk instead of H5Dwrite's
@@ -1085,6 +1159,60 @@ static bool run_only(struct run *r)
 	const double t_sel = o->linkage_only ? r->lk.seconds : o->edges_only ? r->eg.seconds : (r->nb.seconds = sa_hip_last_neighbors_seconds());
 	r->t_setup = call > r->t_align + t_sel ? call - r->t_align - t_sel : 0.0;
 	return true;
+}
+
+/* --query: the M x N rectangle and the hits of every query in one call, in batches of queries sized by the library; only the hits
+ * (and with --query-scores the rectangle) come back.  Set-up is the call less its device time. */
+static bool run_search(struct run *r)
+{
+	const struct options *o = &r->o;
+	info("Search: %d queries against %zu database sequences, %d hits per query selected on the device", r->queries.in.num, r->n, o->neighbors);
+	const double t0 = now();
+	if (!sa_hip_search(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.score, r->sr.rect))
+		return failed(sa_last_error());
+	const double call = now() - t0;
+	stamp("sa_hip_search returned");
+	finish_progress(r);
+	sa_hip_last_search_breakdown(&r->t_align, &r->sr.gather_seconds, &r->sr.hits_seconds, &r->sr.batches);
+	const double device = sa_hip_last_search_seconds();
+	r->t_setup = call > device ? call - device : 0.0;
+	return true;
+}
+
+/* --query --alignments: the M x K pairs (query q, hit_indices[q][t]), row-major, traced back on a search context: a = N + q of the
+ * concatenated store, b = the hit, so every record comes back with the query as a (include/seqalign_hip.h: search) */
+static bool trace_hits(struct run *r)
+{
+	const struct options *o = &r->o;
+	if (!o->alignments)
+		return true;
+	const size_t np = (size_t)r->queries.in.num * (size_t)o->neighbors;
+	int32_t *pa = malloc(sizeof(int32_t) * np);
+	if (!pa)
+		return failed("Out of memory allocating alignment pairs");
+	for (size_t t = 0; t < np; t++)
+		pa[t] = (int32_t)(r->n + t / (size_t)o->neighbors);
+	sa_ctx *ctx = sa_ctx_create_search(0, r->store.in, r->queries.in, &r->sc);
+	r->sr.alns = ctx ? sa_ctx_alignments(ctx, pa, r->sr.index, (int64_t)np) : NULL;
+	free(pa);
+	if (ctx)
+		sa_ctx_destroy(ctx);
+	if (!r->sr.alns)
+		return failed(sa_last_error());
+	r->trace.seconds = sa_hip_last_alignments_seconds();
+	stamp("sa_ctx_alignments returned");
+	return true;
+}
+
+/* --query: everything of a search into one file of its own */
+static bool write_search(struct run *r)
+{
+	const struct options *o = &r->o;
+	int64_t runs = 0;
+	const uint32_t *cigar = r->sr.alns ? sa_alns_cigar(r->sr.alns, &runs) : NULL;
+	r->trace.runs = (long long)runs;
+	return WRITE_OUT(r, sa_host_write_search(o->output, &r->store, &r->queries, o->neighbors, r->sr.index, r->sr.score, r->sr.rect,
+						 r->sr.alns ? sa_alns_records(r->sr.alns) : NULL, cigar, runs), "search written");
 }
 
 /* the matrix into host memory, then the file from there */
@@ -1278,6 +1406,7 @@ static void report(const struct run *r)
 	printf("  (device set-up and upload, outside the phases as in the reference: %.3f sec)\n", r->t_setup);
 	printf("  (schedule: %s)\n", r->device_deflate ? (o->compression ? "column blocks into device memory, their tiles deflated on the device and written meanwhile"
 									  : "column blocks into device memory, their tiles delivered as HDF5 chunks meanwhile")
+			       : o->query ? "only the query-database rectangle is aligned, in batches of queries; only the hits come back"
 			       : o->linkage_only && o->method == SA_AGGLO_COMPLETE ? "the packed matrix stays in device memory, only the complete-linkage tree comes back"
 			       : o->linkage_only && o->method == SA_AGGLO_AVERAGE ? "the packed matrix stays in device memory, only the average-linkage tree comes back"
 			       : o->linkage_only ? "the packed matrix stays in device memory, only the single-linkage tree comes back"
@@ -1285,9 +1414,15 @@ static void report(const struct run *r)
 			       : o->neighbors_only ? "the packed matrix stays in device memory, only the neighbors come back"
 			       : r->schedule == 2 ? "tiles dealt over the devices, RCCL all-gather of the dense shares, placement on every device"
 						  : "every device delivers its slice of the packed index straight into the host matrix");
-	if (o->neighbors)
+	if (o->query) {
+		printf("  (hit selection on the device, K = %d: %.6f sec; rows gathered in %.6f sec; %d batches of queries)\n", o->neighbors,
+		       r->sr.hits_seconds, r->sr.gather_seconds, r->sr.batches);
+		if (o->alignments)
+			printf("  (alignments of the %lld hit pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
+			       (long long)r->queries.in.num * o->neighbors, r->trace.seconds, r->trace.runs);
+	} else if (o->neighbors)
 		printf("  (neighbor selection on the device, K = %d: %.6f sec%s)\n", o->neighbors, r->nb.seconds, r->nb.second_pass ? AGAIN : "");
-	if (o->alignments)
+	if (o->alignments && !o->query)
 		printf("  (alignments of the %lld neighbor pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
 		       (long long)r->store.in.num * o->neighbors, r->trace.seconds, r->trace.runs);
 	if (o->nquant)
@@ -1319,6 +1454,12 @@ static void release(struct run *r)
 	free(r->nb.index);
 	free(r->nb.score);
 	free(r->norm_spec.denominators);
+	if (r->sr.alns)
+		sa_alns_destroy(r->sr.alns);
+	free(r->sr.index);
+	free(r->sr.score);
+	free(r->sr.rect);
+	sa_host_store_free(&r->queries);
 	sa_host_store_free(&r->store);
 	stamp("released");
 }
@@ -1345,9 +1486,12 @@ int main(int argc, char **argv)
 		progress_line(0.0, NULL);
 	}
 	verb("Devices: %d (%s)", sa_hip_device_count(), sa_hip_device_name(0) ? sa_hip_device_name(0) : "none");
-	if (!(r->device_deflate ? run_tile_job(r) : r->no_matrix ? run_only(r) : run_host_matrix(r)))
+	if (!(r->o.query ? run_search(r) : r->device_deflate ? run_tile_job(r) : r->no_matrix ? run_only(r) : run_host_matrix(r)))
 		return 1;
-	if (!pass_neighbors(r) || !write_neighbors(r) || !trace_alignments(r) || !pass_quantiles(r) || !pass_edges(r) || !write_edges(r) ||
+	if (r->o.query) { /* a search has one selection, the hits, and one writer */
+		if (!trace_hits(r) || !write_search(r))
+			return 1;
+	} else if (!pass_neighbors(r) || !write_neighbors(r) || !trace_alignments(r) || !pass_quantiles(r) || !pass_edges(r) || !write_edges(r) ||
 	    !pass_linkage(r) || !write_linkage(r) || !write_quantiles_and_quantity(r))
 		return 1;
 	if (r->o.benchmark)

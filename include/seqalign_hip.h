@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls, then the *_search* / *_hits calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -275,6 +275,58 @@ bool sa_hip_neighbors(struct sa_input in, const struct sa_scoring *sc, int32_t k
 int sa_zjob_neighbors(sa_zjob *job, int32_t k, int32_t *index, int32_t *score);
 /* device time (seconds) of the selection kernel in the last successful sa_hip_neighbors / sa_zjob_neighbors call */
 double sa_hip_last_neighbors_seconds(void);
+
+/* ---- search: queries against a database, the k best hits of every query selected on the device -----------------------
+ * No reference counterpart: the reference scores one store against itself.  Let db (N >= 1 sequences) and queries (M >= 1)
+ * be two stores; the CONCATENATED store is db followed by queries.  The score of query q against database sequence d is the
+ * similarity-matrix entry of pair (d, N + q) of the concatenated store: d is the row sequence, the query the column
+ * sequence, and the substitution table is indexed exactly as struct sa_scoring documents -- with an asymmetric table the
+ * search of A against B is not the search of B against A.  Only the M * N query-database pairs are computed; no pair of two
+ * queries and no pair of two database sequences is.
+ *   rect   int32 M x N, row-major: rect[q * N + d]
+ *   hits   the candidates of query q are ALL d in [0, N) (the stores are separate: there is no self to exclude); order: score
+ *          DESCENDING, then d ASCENDING; row q of index / score (M x k) holds the first k.  1 <= k <= min(N,
+ *          SA_HIP_NEIGHBORS_MAX).  The tie rule is part of the contract: the same inputs give the same bytes run after run.
+ *   alignments of hits   sa_ctx_alignments on the search context with a = N + q, b = d.  a > b, so the record comes back
+ *          mirrored as that call documents: the a_* spans are the query's, SA_ALN_I is a residue of the query only, and
+ *          `score` equals rect[q * N + d].
+ *
+ * sa_ctx_create_search concatenates the two stores on the host and is otherwise sa_ctx_create; the context's launch plans are
+ * bounded to the database rows.  NULL + sa_last_error for an empty store, or when N + M or the concatenated blob passes the
+ * int32 of struct sa_meta.  sa_ctx_search_db / _queries: N and M, or 0 for a context of sa_ctx_create.
+ * A search context has no packed triangle: every sa_ctx_* call over a packed range or a packed matrix (sa_ctx_align_range /
+ * _range16 / _host / _share, _share_elems, _place_shares, _expand_full, _identity_range, _neighbors, _edge_*, _linkage,
+ * _agglomerate, _select, _normalize) refuses it with one message that names sa_ctx_search_range.  sa_ctx_alignments,
+ * sa_ctx_timing, sa_ctx_timing_read and sa_ctx_token_tiles work.  The calls that take no context but a packed matrix and its
+ * order (sa_zjob_create and what follows from it) know nothing of contexts: there is no packed matrix of a search to hand them,
+ * and a rectangle passed as one is the caller's error, undefined as any wrong pointer is.
+ *
+ * sa_ctx_search_range   queries [q0, q0 + nq) into dense DEVICE memory d_rect[(q - q0) * N + d].  Asynchronous on `stream`,
+ *          allocates nothing.  d_scratch: sa_search_scratch_bytes(ctx, q0, nq) bytes of device memory -- the bounded packed
+ *          range [tri(N + q0), tri(N + q0 + nq)) lands there, row q at pitch N + q, and a gather kernel moves the rows to
+ *          pitch N (the score kernels place scores by packed index; dense stores straight from them are not built).
+ * sa_ctx_hits   the hits of rows [0, nq) of a device rectangle of pitch N = sa_ctx_search_db(ctx): d_index, d_score nq * k
+ *          int32 each, device memory.  Asynchronous on `stream`, allocates nothing, leaves d_rect unchanged.  d_scratch:
+ *          sa_hits_scratch_bytes(N, nq, k) bytes of device memory, 8-byte aligned (refused otherwise); that is 0, and d_scratch may be NULL, when the rows alone
+ *          fill the device (with few rows every row is cut into segments whose partial lists go through the scratch).
+ * sa_hip_search   one call, host in / host out, one device (the first).  rect may be NULL; index and score may both be NULL
+ *          when rect is not (k is then ignored).  The queries go in batches sized from the free device memory
+ *          (SA_HIP_SEARCH_BATCH_BYTES=n caps the device buffers that grow with a batch), so any M works.  Arguments are checked
+ *          before a device is looked for.
+ * sa_hip_last_search_seconds / _breakdown   device time of the last successful sa_hip_search, summed over its batches:
+ *          alignment, gather, selection; and the number of batches.
+ * Non-zero / false / NULL + sa_last_error on failure. */
+sa_ctx *sa_ctx_create_search(int device, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc);
+int32_t sa_ctx_search_db(const sa_ctx *ctx);
+int32_t sa_ctx_search_queries(const sa_ctx *ctx);
+size_t sa_search_scratch_bytes(const sa_ctx *ctx, int32_t q0, int32_t nq);
+int sa_ctx_search_range(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void *d_scratch, void *stream);
+size_t sa_hits_scratch_bytes(int32_t n_db, int32_t nq, int32_t k);
+int sa_ctx_hits(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, void *stream);
+bool sa_hip_search(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score,
+		   int32_t *rect);
+double sa_hip_last_search_seconds(void);
+void sa_hip_last_search_breakdown(double *align, double *gather, double *hits, int32_t *batches);
 
 /* ---- alignments for chosen pairs: traceback on the device, run-length CIGARs ----------------------------------------
  * No reference counterpart: the reference keeps scores only.  For an explicit list of pairs (a[t], b[t]) of one store,

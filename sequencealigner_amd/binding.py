@@ -70,6 +70,8 @@ ABI_SYMBOLS = (
     "sa_hip_linkage_pid", "sa_hip_select_pid", "sa_hip_edges_at_rank_pid", "sa_hip_linkage_with_ranks_pid", "sa_hip_last_identity_seconds",
     "sa_agglo_scratch_bytes", "sa_ctx_agglomerate", "sa_hip_agglomerate", "sa_hip_agglomerate_with_ranks", "sa_zjob_agglomerate",
     "sa_agglo_labels", "sa_hip_last_agglomerate_seconds", "sa_hip_last_agglomerate_rescans",
+    "sa_ctx_create_search", "sa_ctx_search_db", "sa_ctx_search_queries", "sa_search_scratch_bytes", "sa_ctx_search_range",
+    "sa_hits_scratch_bytes", "sa_ctx_hits", "sa_hip_search", "sa_hip_last_search_seconds", "sa_hip_last_search_breakdown",
 )
 
 
@@ -332,6 +334,25 @@ def load_library() -> C.CDLL:
     lib.sa_agglo_labels.restype = C.c_int32
     lib.sa_hip_last_agglomerate_seconds.restype = C.c_double
     lib.sa_hip_last_agglomerate_rescans.restype = C.c_int64
+    lib.sa_ctx_create_search.argtypes = [C.c_int, _Input, _Input, C.POINTER(_Scoring)]
+    lib.sa_ctx_create_search.restype = C.c_void_p
+    lib.sa_ctx_search_db.argtypes = [C.c_void_p]
+    lib.sa_ctx_search_db.restype = C.c_int32
+    lib.sa_ctx_search_queries.argtypes = [C.c_void_p]
+    lib.sa_ctx_search_queries.restype = C.c_int32
+    lib.sa_search_scratch_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.sa_search_scratch_bytes.restype = C.c_size_t
+    lib.sa_ctx_search_range.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_search_range.restype = C.c_int
+    lib.sa_hits_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.sa_hits_scratch_bytes.restype = C.c_size_t
+    lib.sa_ctx_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_hits.restype = C.c_int
+    lib.sa_hip_search.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_hip_search.restype = C.c_bool
+    lib.sa_hip_last_search_seconds.restype = C.c_double
+    lib.sa_hip_last_search_breakdown.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    lib.sa_hip_last_search_breakdown.restype = None
     _lib = lib
     return lib
 
@@ -1063,13 +1084,18 @@ class Context:
     index computed into device buffers the caller owns (e.g. torch tensors)."""
 
     def __init__(self, store: SequenceStore, scoring: Scoring, device: int = 0):
-        self._lib = load_library()
-        self._store = store  # keep host arrays alive
         sc = scoring._as_c()
-        self._h = self._lib.sa_ctx_create(int(device), store._as_c(), C.byref(sc))
+        self._adopt(lambda lib: lib.sa_ctx_create(int(device), store._as_c(), C.byref(sc)), store, store.num, device)
+
+    def _adopt(self, create, keep, num: int, device: int) -> None:
+        """the state every context has, whichever call creates it: the library, the handle of create(lib), what keeps the
+        host arrays alive, the number of sequences in the context's store, the device"""
+        self._lib = load_library()
+        self._store = keep
+        self._h = create(self._lib)
         if not self._h:
             raise AlignError(_err())
-        self.num = store.num
+        self.num = int(num)
         self.device = int(device)
 
     def close(self) -> None:
@@ -1256,6 +1282,90 @@ class Context:
             raise AlignError(_err())
         return dict(kernel=name.value.decode(), launches=int(launches.value), ms=float(ms.value),
                     pairs=int(pairs.value), cells=int(cells.value), all_kernels_ms=float(all_ms.value))
+
+
+def _int32(name: str, v) -> int:
+    v = int(v)
+    if not -2**31 <= v < 2**31:
+        raise AlignError(f"{name} = {v} is not an int32")
+    return v
+
+
+class SearchContext(Context):
+    """Search context (sa_ctx_create_search): db followed by queries as one store whose launches are bounded to the database
+    rows.  search_range computes the (nq, N) rectangle of a query range into device memory, hits selects the k best database
+    sequences of every row; alignments takes pairs (N + q, d).  The packed-range calls inherited from Context are refused by the
+    library on such a context."""
+
+    def __init__(self, db: SequenceStore, queries: SequenceStore, scoring: Scoring, device: int = 0):
+        sc = scoring._as_c()
+        self._adopt(lambda lib: lib.sa_ctx_create_search(int(device), db._as_c(), queries._as_c(), C.byref(sc)), (db, queries),
+                    db.num + queries.num, device)
+        self.n_db = int(self._lib.sa_ctx_search_db(self._h))
+        self.n_queries = int(self._lib.sa_ctx_search_queries(self._h))
+
+    def cells(self, start: int = 0, count: Optional[int] = None) -> int:
+        raise AlignError("a search context has no packed pair space")
+
+    def partition(self, parts: int) -> list[int]:
+        raise AlignError("a search context has no packed pair space")
+
+    def search_scratch_bytes(self, q0: int, nq: int) -> int:
+        return int(self._lib.sa_search_scratch_bytes(self._h, _int32("q0", q0), _int32("nq", nq)))
+
+    def search_range(self, q0: int, nq: int, d_rect_ptr: int, d_scratch_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_search_range: queries [q0, q0 + nq) into the dense device rectangle d_rect[(q - q0) * N + d]"""
+        if self._lib.sa_ctx_search_range(self._h, _int32("q0", q0), _int32("nq", nq), C.c_void_p(d_rect_ptr), C.c_void_p(d_scratch_ptr),
+                                         C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def hits(self, d_rect_ptr: int, nq: int, k: int, d_index_ptr: int, d_score_ptr: int, d_scratch_ptr: int = 0, stream: int = 0) -> None:
+        """sa_ctx_hits: the k best database sequences of rows [0, nq) of a device rectangle of pitch N"""
+        if self._lib.sa_ctx_hits(self._h, C.c_void_p(d_rect_ptr), _int32("nq", nq), _int32("k", k), C.c_void_p(d_index_ptr),
+                                 C.c_void_p(d_score_ptr), C.c_void_p(d_scratch_ptr), C.c_void_p(stream)):
+            raise AlignError(_err())
+
+
+def hits_scratch_bytes(n_db: int, nq: int, k: int) -> int:
+    """device bytes SearchContext.hits needs as scratch (0: none, the rows alone fill the device)"""
+    return int(load_library().sa_hits_scratch_bytes(_int32("n_db", n_db), _int32("nq", nq), _int32("k", k)))
+
+
+def hip_search(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: Optional[int] = None, rect: bool = False):
+    """sa_hip_search: queries against a database on the first device.  With k: (index, score), two (M, k) int32 arrays, row q
+    lists the database sequences by score descending, then index ascending; 1 <= k <= min(N, NEIGHBORS_MAX).  With rect=True
+    the (M, N) int32 rectangle rect[q, d] follows (alone when k is None)."""
+    n, m = db.num, queries.num
+    if k is None and not rect:
+        raise AlignError("hip_search: nothing asked for (k is None and rect is False)")
+    kk = 0 if k is None else _int32("k", k)
+    index = score = out = None
+    if k is not None:
+        rows = max(m, 1) * max(min(kk, NEIGHBORS_MAX), 1)
+        index, score = np.empty(rows, np.int32), np.empty(rows, np.int32)
+    if rect:
+        out = np.empty((max(m, 0), max(n, 0)), np.int32)
+    sc = scoring._as_c()
+    if not load_library().sa_hip_search(db._as_c(), queries._as_c(), C.byref(sc), kk, index.ctypes.data if index is not None else None,
+                                        score.ctypes.data if score is not None else None, out.ctypes.data if out is not None else None):
+        raise AlignError(_err())
+    res = ()
+    if k is not None:
+        res += (index[:m * kk].reshape(m, kk), score[:m * kk].reshape(m, kk))
+    if rect:
+        res += (out,)
+    return res[0] if len(res) == 1 else res
+
+
+def last_search_seconds() -> float:
+    """device time of the last hip_search call: alignment + gather + selection, summed over its batches"""
+    return float(load_library().sa_hip_last_search_seconds())
+
+
+def last_search_breakdown() -> dict:
+    a, g, h, b = C.c_double(), C.c_double(), C.c_double(), C.c_int32()
+    load_library().sa_hip_last_search_breakdown(C.byref(a), C.byref(g), C.byref(h), C.byref(b))
+    return dict(align=float(a.value), gather=float(g.value), hits=float(h.value), batches=int(b.value))
 
 
 class DeflateJob:

@@ -520,6 +520,8 @@ extern "C" size_t sa_agglo_scratch_bytes(int32_t num, int32_t method) { return a
 extern "C" int sa_ctx_agglomerate(sa_ctx *ctx, const int32_t *d_packed, int32_t method, int32_t *d_pairs, int32_t *d_score, void *d_scratch,
 				  void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_agglomerate"))
+		return 1;
 	return sa_guard("sa_ctx_agglomerate", 1, [&] {
 		if (!ctx || !d_packed || !d_pairs || !d_score || !d_scratch) {
 			sa_set_error("sa_ctx_agglomerate: null argument");

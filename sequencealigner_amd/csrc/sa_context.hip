@@ -145,6 +145,7 @@ SaPlanInputs sa_plan_inputs(const sa_ctx *ctx)
 	in.env_chunk = ctx->env.chunk;
 	in.no_sort = ctx->env.no_sort;
 	in.no_tokens = ctx->env.no_tokens;
+	in.row_end = ctx->search_db;
 	return in;
 }
 
@@ -154,7 +155,8 @@ struct CtxDeleter {
 };
 } // namespace
 
-static sa_ctx *ctx_create_impl(int device, struct sa_input in, const struct sa_scoring *sc)
+/* search_db != 0: `in` is a database of search_db sequences followed by queries (ctx_create_search_impl) */
+static sa_ctx *ctx_create_impl(int device, struct sa_input in, const struct sa_scoring *sc, int32_t search_db = 0)
 {
 	if (!sc) {
 		sa_set_error("sa_ctx_create: null scoring");
@@ -189,6 +191,8 @@ static sa_ctx *ctx_create_impl(int device, struct sa_input in, const struct sa_s
 	for (int32_t k = 0; k < in.num; k++)
 		ctx->min_len = std::min<int32_t>(ctx->min_len, (int32_t)in.meta[k].len);
 	ctx->pairs = (int64_t)in.num * (in.num - 1) / 2;
+	ctx->search_db = search_db;
+	ctx->search_queries = search_db ? in.num - search_db : 0;
 	ctx->sc = *sc;
 	ctx->meta.resize((size_t)in.num);
 	for (int32_t k = 0; k < in.num; k++)
@@ -286,6 +290,75 @@ static sa_ctx *ctx_create_impl(int device, struct sa_input in, const struct sa_s
 extern "C" sa_ctx *sa_ctx_create(int device, struct sa_input in, const struct sa_scoring *sc)
 {
 	return sa_guard("sa_ctx_create", (sa_ctx *)nullptr, [&] { return ctx_create_impl(device, in, sc); });
+}
+
+/* The concatenated store of a search: db followed by queries, copied into one blob with fresh offsets (the inputs may
+ * overlap, share a blob or lie anywhere); everything else is sa_ctx_create with the plans bounded to the rows below N. */
+static sa_ctx *ctx_create_search_impl(int device, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc)
+{
+	if (!sc) {
+		sa_set_error("sa_ctx_create_search: null scoring");
+		return nullptr;
+	}
+	if (db.num < 1 || queries.num < 1) {
+		sa_set_error("sa_ctx_create_search: empty store (%d database sequences, %d queries; min: 1 each)", db.num, queries.num);
+		return nullptr;
+	}
+	if (!db.seqs || !db.meta || !queries.seqs || !queries.meta) {
+		sa_set_error("sa_ctx_create_search: null sequence store");
+		return nullptr;
+	}
+	if ((int64_t)db.num + queries.num > INT32_MAX) {
+		sa_set_error("sa_ctx_create_search: %lld sequences exceed 32-bit sequence indices", (long long)db.num + queries.num);
+		return nullptr;
+	}
+	const struct sa_input parts[2] = { db, queries };
+	int64_t bytes = 0;
+	for (const auto &st : parts)
+		for (int32_t k = 0; k < st.num; k++) {
+			const sa_meta m = st.meta[k];
+			if (m.len < 1 || m.off < 0) {
+				sa_set_error("%s sequence #%d has invalid offset/length (%d/%d)", &st == &parts[0] ? "Database" : "Query", k + 1, m.off, m.len);
+				return nullptr;
+			}
+			bytes += (int64_t)m.len + 1;
+			if (bytes > INT32_MAX) {
+				sa_set_error("sa_ctx_create_search: the concatenated sequence store exceeds 2 GiB");
+				return nullptr;
+			}
+		}
+	std::vector<uint8_t> blob((size_t)bytes);
+	std::vector<sa_meta> meta((size_t)db.num + (size_t)queries.num);
+	int64_t at = 0;
+	size_t n = 0;
+	for (const auto &st : parts)
+		for (int32_t k = 0; k < st.num; k++) {
+			const sa_meta m = st.meta[k];
+			memcpy(blob.data() + at, st.seqs + m.off, (size_t)m.len + 1); /* (the terminator too: validate_and_encode checks it) */
+			meta[n++] = sa_meta{ (int32_t)at, m.len };
+			at += (int64_t)m.len + 1;
+		}
+	struct sa_input cat{};
+	cat.seqs = blob.data();
+	cat.meta = meta.data();
+	cat.num = db.num + queries.num;
+	cat.max = std::max(db.max, queries.max);
+	return ctx_create_impl(device, cat, sc, db.num);
+}
+
+extern "C" sa_ctx *sa_ctx_create_search(int device, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc)
+{
+	return sa_guard("sa_ctx_create_search", (sa_ctx *)nullptr, [&] { return ctx_create_search_impl(device, db, queries, sc); });
+}
+
+extern "C" int32_t sa_ctx_search_db(const sa_ctx *ctx)
+{
+	return sa_guard("sa_ctx_search_db", (int32_t)0, [&] { return ctx ? ctx->search_db : (int32_t)0; });
+}
+
+extern "C" int32_t sa_ctx_search_queries(const sa_ctx *ctx)
+{
+	return sa_guard("sa_ctx_search_queries", (int32_t)0, [&] { return ctx ? ctx->search_queries : (int32_t)0; });
 }
 
 extern "C" void sa_ctx_destroy(sa_ctx *ctx)

@@ -6,6 +6,7 @@
  *   sa_deliver.hip : sa_ctx_align_host (the launch/copy loop towards host memory)
  *   sa_gather.hip  : several devices of one process through dense shares + RCCL all-gather
  *   sa_identity.hip: sa_ctx_identity_range, sa_hip_identity (percent identity of every pair)
+ *   sa_search.hip  : sa_ctx_search_range, sa_ctx_hits, sa_hip_search (queries against a database: search contexts)
  *   sa_abi.hip     : sa_hip_align, sa_hip_memory, sa_hip_filter, progress, side channels
  */
 #ifndef SA_CTX_H
@@ -29,6 +30,9 @@ struct sa_ctx {
 	int device = 0;
 	int32_t num = 0, max_len = 0, min_len = 0;
 	int64_t pairs = 0;
+	/* search context (sa_ctx_create_search): the store is db followed by queries, num = search_db + search_queries, and every
+	 * plan is bounded to the rows below search_db (SaPlanInputs::row_end); both 0 on an ordinary context */
+	int32_t search_db = 0, search_queries = 0;
 	sa_scoring sc{};
 	SaEnv env;                     /* the switches, as they were when the context was created             */
 	std::vector<sa_meta> meta;     /* device-side (tight) layout: off[k] = sum_{i<k}(len_i+1)          */
@@ -143,6 +147,15 @@ struct sa_ctx {
 		int64_t h_counters_n = 0;
 	} dl;
 };
+
+/* A search context (sa_ctx_create_search) has no packed triangle: every call over a packed range or a packed matrix refuses it */
+static inline bool sa_search_refused(const sa_ctx *ctx, const char *who)
+{
+	if (!ctx || !ctx->search_db)
+		return false;
+	sa_set_error("%s: a search context has no packed triangle; its scores come from sa_ctx_search_range", who);
+	return true;
+}
 
 /* ---- shared between the translation units ------------------------------------------------------------------------ */
 static inline double sa_ms_since(std::chrono::steady_clock::time_point t0)

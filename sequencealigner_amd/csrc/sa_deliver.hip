@@ -527,5 +527,7 @@ static int align_host_impl(sa_ctx *ctx, int64_t start, int64_t count, struct sa_
 
 extern "C" int sa_ctx_align_host(sa_ctx *ctx, int64_t start, int64_t count, struct sa_output out, double *phase_seconds)
 {
+	if (sa_search_refused(ctx, "sa_ctx_align_host"))
+		return 1;
 	return sa_guard("sa_ctx_align_host", 1, [&] { return align_host_impl(ctx, start, count, out, phase_seconds); });
 }

@@ -265,6 +265,8 @@ sa_edges *sa_edges_to_host(const char *who, const int32_t *d_packed, int32_t num
 
 extern "C" int sa_ctx_edge_offsets(sa_ctx *ctx, const int32_t *d_packed, int32_t min_score, int64_t *d_offsets, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_edge_offsets"))
+		return 1;
 	return sa_guard("sa_ctx_edge_offsets", 1, [&] {
 		if (!ctx || !d_packed || !d_offsets) {
 			sa_set_error("sa_ctx_edge_offsets: null argument");
@@ -279,6 +281,8 @@ extern "C" int sa_ctx_edge_offsets(sa_ctx *ctx, const int32_t *d_packed, int32_t
 extern "C" int sa_ctx_edge_fill(sa_ctx *ctx, const int32_t *d_packed, int32_t min_score, const int64_t *d_offsets, int32_t *d_index,
 				int32_t *d_score, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_edge_fill"))
+		return 1;
 	return sa_guard("sa_ctx_edge_fill", 1, [&] {
 		if (!ctx || !d_packed || !d_offsets || !d_index || !d_score) {
 			sa_set_error("sa_ctx_edge_fill: null argument");

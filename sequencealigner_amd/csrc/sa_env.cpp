@@ -32,6 +32,7 @@ SaEnv sa_env_read()
 	e.tiles_split = number("SA_HIP_TILES_SPLIT", 0, 0, 64);
 	e.trace_batch_bytes = getenv("SA_HIP_TRACE_BATCH_BYTES") ? std::max(0LL, atoll(getenv("SA_HIP_TRACE_BATCH_BYTES"))) : 0LL;
 	e.identity_batch_bytes = getenv("SA_HIP_IDENTITY_BATCH_BYTES") ? std::max(0LL, atoll(getenv("SA_HIP_IDENTITY_BATCH_BYTES"))) : 0LL;
+	e.search_batch_bytes = getenv("SA_HIP_SEARCH_BATCH_BYTES") ? std::max(0LL, atoll(getenv("SA_HIP_SEARCH_BATCH_BYTES"))) : 0LL;
 	e.verbose = flag("SA_HIP_VERBOSE");
 	e.stamps = flag("SA_HIP_STAMPS");
 	e.stamps_dump = getenv("SA_HIP_STAMPS_DUMP");

@@ -467,6 +467,8 @@ extern "C" int32_t sa_pid_value(int32_t identities, int32_t columns, int32_t len
 
 extern "C" int sa_ctx_identity_range(sa_ctx *ctx, int64_t start, int64_t count, const struct sa_identity_out *d_out, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_identity_range"))
+		return 1;
 	return sa_guard("sa_ctx_identity_range", 1, [&] { return identity_range_impl(ctx, start, count, d_out, stream); });
 }
 

@@ -70,6 +70,7 @@ struct SaSysArgs {
 	int32_t *host_out;        /* dense shares only: page-locked packed host matrix (device-visible address of element
 	                           * `start`) that receives the same scores in packed order, or nullptr          */
 	int32_t nlocal;
+	int32_t row_end;          /* != 0: no tile runs a row >= row_end (search contexts: the database rows, sa_search.hip) */
 	const SaPkClassArgs *pkc; /* packed bundle launch: its classes; nlocal = tiles of the whole launch */
 	const uint32_t *ulist;    /* ... and its tiles in walking order: two words per tile, the code (SA_PK_UTILE_BITS)
 	                           * and the tile's column pair in its class                                      */

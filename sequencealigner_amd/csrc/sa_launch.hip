@@ -493,6 +493,7 @@ static int align_range_launches(sa_ctx *ctx, int64_t start, int64_t count, int32
 	common.num = ctx->num;
 	common.start = start;
 	common.end = start + count;
+	common.row_end = ctx->search_db;
 	common.out = d_scores;
 	common.out16 = out16 ? 1 : 0;
 	common.gap_g = ctx->sc.gap_pen;
@@ -589,6 +590,8 @@ extern "C" int sa_ctx_token_tiles(const sa_ctx *ctx, int64_t *lean, int64_t *leg
 
 extern "C" int sa_ctx_align_range(sa_ctx *ctx, int64_t start, int64_t count, int32_t *d_scores, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_align_range"))
+		return 1;
 	return sa_guard("sa_ctx_align_range", 1, [&] { return sa_align_range_impl(ctx, start, count, d_scores, stream, false); });
 }
 
@@ -613,6 +616,8 @@ extern "C" int sa_ctx_scores_fit16(const sa_ctx *ctx)
 
 extern "C" int sa_ctx_align_range16(sa_ctx *ctx, int64_t start, int64_t count, int16_t *d_scores, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_align_range16"))
+		return 1;
 	if (!sa_ctx_scores_fit16(ctx)) {
 		sa_set_error("sa_ctx_align_range16: scores of this store and scoring are not provably within int16");
 		return 1;
@@ -650,6 +655,8 @@ extern "C" void sa_ctx_leave_room(sa_ctx *ctx, int on)
 
 extern "C" int64_t sa_ctx_share_elems(sa_ctx *ctx, int64_t start, int64_t count, int world, int to_host)
 {
+	if (sa_search_refused(ctx, "sa_ctx_share_elems"))
+		return -1;
 	return sa_guard("sa_ctx_share_elems", (int64_t)-1, [&]() -> int64_t {
 		if (!share_args_ok(ctx, start, count, world, "sa_ctx_share_elems"))
 			return -1;
@@ -663,6 +670,8 @@ extern "C" int64_t sa_ctx_share_elems(sa_ctx *ctx, int64_t start, int64_t count,
 extern "C" int sa_ctx_align_share(sa_ctx *ctx, int64_t start, int64_t count, int world, int rank, void *d_share, int elem16,
 				   int32_t *host_packed, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_align_share"))
+		return 1;
 	return sa_guard("sa_ctx_align_share", 1, [&] {
 		if (!share_args_ok(ctx, start, count, world, "sa_ctx_align_share"))
 			return 1;
@@ -693,6 +702,8 @@ extern "C" int sa_ctx_align_share(sa_ctx *ctx, int64_t start, int64_t count, int
 extern "C" int sa_ctx_place_shares(sa_ctx *ctx, int64_t start, int64_t count, int world, int to_host, const void *d_shares,
 				    int elem16, int32_t *d_packed, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_place_shares"))
+		return 1;
 	return sa_guard("sa_ctx_place_shares", 1, [&] {
 		if (!share_args_ok(ctx, start, count, world, "sa_ctx_place_shares"))
 			return 1;
@@ -710,6 +721,8 @@ extern "C" int sa_ctx_place_shares(sa_ctx *ctx, int64_t start, int64_t count, in
 
 extern "C" int sa_ctx_expand_full(sa_ctx *ctx, const int32_t *d_packed, int32_t *d_full, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_expand_full"))
+		return 1;
 	if (!ctx || !d_packed || !d_full) {
 		sa_set_error("sa_ctx_expand_full: null argument");
 		return 1;

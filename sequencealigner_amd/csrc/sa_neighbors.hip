@@ -184,6 +184,8 @@ bool sa_neighbors_to_host(const int32_t *d_packed, int32_t num, int32_t k, int32
 
 extern "C" int sa_ctx_neighbors(sa_ctx *ctx, const int32_t *d_packed, int32_t k, int32_t *d_index, int32_t *d_score, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_neighbors"))
+		return 1;
 	return sa_guard("sa_ctx_neighbors", 1, [&] {
 		if (!ctx || !d_packed || !d_index || !d_score) {
 			sa_set_error("sa_ctx_neighbors: null argument");

@@ -299,6 +299,8 @@ extern "C" int sa_ctx_denominators(sa_ctx *ctx, int32_t source, int32_t *d_den, 
 
 extern "C" int sa_ctx_normalize(sa_ctx *ctx, const int32_t *d_packed, const int32_t *d_den, int32_t rule, int32_t *d_out, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_normalize"))
+		return 1;
 	return sa_guard("sa_ctx_normalize", 1, [&] {
 		if (!ctx || !d_packed || !d_den || !d_out) {
 			sa_set_error("sa_ctx_normalize: null argument");

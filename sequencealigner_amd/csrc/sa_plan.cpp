@@ -241,6 +241,36 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 		return false;
 	}
 	const int64_t end = start + count;
+	const int32_t row_end = in.row_end;
+	if (row_end < 0 || (row_end && world >= 1)) {
+		sa_set_error("plan: a row bound (%d) goes with no share plan (world %d)", row_end, world);
+		return false;
+	}
+	/* rows of column j inside the range: [ia, ib) with the row bound applied */
+	auto rows_in = [&](int64_t j, int64_t &ia, int64_t &ib) {
+		const int64_t tri = j * (j - 1) / 2;
+		ia = std::max<int64_t>(0, start - tri);
+		ib = std::min<int64_t>(j, end - tri);
+		if (row_end)
+			ib = std::min<int64_t>(ib, row_end);
+	};
+	/* bounded plans: pairs of the columns [j0, j) of the range, for the sizing below (without a bound that is tri(j) - start) */
+	std::vector<int64_t> bounded_below;
+	int64_t work = count; /* pairs the range really runs */
+	if (row_end) {
+		const int64_t jlo = sa_column_of(start), jhi = sa_column_of(end - 1) + 1;
+		bounded_below.assign((size_t)(jhi - jlo) + 1, 0);
+		for (int64_t j = jlo; j < jhi; j++) {
+			int64_t ia, ib;
+			rows_in(j, ia, ib);
+			bounded_below[(size_t)(j - jlo) + 1] = bounded_below[(size_t)(j - jlo)] + std::max<int64_t>(0, ib - ia);
+		}
+		work = bounded_below.back();
+		if (work <= 0) {
+			sa_set_error("plan: no pair of [%lld,+%lld) has a row below the bound %d", (long long)start, (long long)count, row_end);
+			return false;
+		}
+	}
 	std::vector<std::vector<int32_t>> jl((size_t)SA_PLAN_NCLASSES), tp((size_t)SA_PLAN_NCLASSES);
 	std::vector<int64_t> cpairs((size_t)SA_PLAN_NCLASSES, 0), ccells((size_t)SA_PLAN_NCLASSES, 0);
 	std::vector<std::vector<std::pair<int32_t, int32_t>>> rows_of((size_t)SA_PLAN_NCLASSES); /* packed classes: [ia, ib) per column */
@@ -252,7 +282,7 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 	 * so that there are still several tiles per wave slot. */
 	{
 		const int64_t want_tiles = (int64_t)in.persistent_wgs * 6;
-		const int64_t mine = world > 1 ? count / world : count; /* pairs one rank runs */
+		const int64_t mine = world > 1 ? count / world : work; /* pairs one rank runs */
 		int32_t chunk = SA_SYS_CHUNK;
 		while (chunk > 8 && mine / (4 * chunk) < want_tiles)
 			chunk >>= 1;
@@ -289,7 +319,8 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 				int64_t lo = jlo, hi = jhi; /* smallest column with >= a fifth of the range's pairs below it */
 				while (lo < hi) {
 					const int64_t mid = (lo + hi) / 2;
-					if (mid * (mid - 1) / 2 - start >= count / SMALL_PAIRS_FRAC)
+					const int64_t below = row_end ? bounded_below[(size_t)(mid - jlo)] : mid * (mid - 1) / 2 - start;
+					if (below >= work / SMALL_PAIRS_FRAC)
 						hi = mid;
 					else
 						lo = mid + 1;
@@ -301,7 +332,8 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 	const int32_t j0 = sa_column_of(start), j1 = sa_column_of(end - 1);
 	for (int32_t j = j0; j <= j1; j++) {
 		const int64_t tri = (int64_t)j * (j - 1) / 2;
-		const int64_t ia = std::max<int64_t>(0, start - tri), ib = std::min<int64_t>(j, end - tri);
+		int64_t ia, ib;
+		rows_in(j, ia, ib);
 		if (ib <= ia)
 			continue;
 		const int32_t n = in.meta[j].len;
@@ -318,7 +350,8 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 		}
 		const int cls = in.sys_ok ? sa_systolic_class_for(n) : -1;
 		if (cls < 0) {
-			if (!plan.generic.empty() && plan.generic.back().first + plan.generic.back().second == tri + ia)
+			/* (bounded: one run [tri(j) + ia, +rows) per column -- column row_end itself is whole and would join the next) */
+			if (!row_end && !plan.generic.empty() && plan.generic.back().first + plan.generic.back().second == tri + ia)
 				plan.generic.back().second += ib - ia;
 			else
 				plan.generic.emplace_back(tri + ia, ib - ia);

@@ -57,6 +57,9 @@ struct SaPlanInputs {
 	int32_t pk_q = 0, pk_floor = 0;
 	int64_t pk_gain = 0, pk_slack = 0;
 	int persistent_wgs = 256 * 32; /* 32 x CUs */
+	/* row bound (search contexts, sa_search.hip): != 0 cuts every column's rows to [ia, min(ib, row_end)) -- the pairs of a
+	 * column with the rows below row_end only; 0: none, the plan of the whole packed range.  Not for share plans. */
+	int32_t row_end = 0;
 	/* development switches (sa_env.h) */
 	int env_chunk = 0;
 	bool no_sort = false;

@@ -279,6 +279,8 @@ extern "C" int64_t sa_score_rank(int64_t pairs, double q) { return sa_sel_rank(p
 extern "C" int sa_ctx_select(sa_ctx *ctx, const int32_t *d_packed, const int64_t *ranks, int32_t m, int32_t *d_value, int64_t *d_below,
 			     void *d_scratch, void *stream)
 {
+	if (sa_search_refused(ctx, "sa_ctx_select"))
+		return 1;
 	return sa_guard("sa_ctx_select", 1, [&] {
 		if (!ctx || !d_packed || !ranks || !d_value || !d_below || !d_scratch) {
 			sa_set_error("sa_ctx_select: null argument");

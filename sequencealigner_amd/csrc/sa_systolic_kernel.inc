@@ -207,7 +207,8 @@ __device__ __forceinline__ void systolic_tile(const SaSysArgs &A, const int32_t 
 	const int32_t chunk = t - A.tprefix[lo];
 	const int64_t tri = (int64_t)j * (j - 1) / 2;
 	const int64_t ia64 = A.start > tri ? A.start - tri : 0;
-	const int64_t ib64 = A.end - tri < j ? A.end - tri : j;
+	const int64_t jb = A.row_end && A.row_end < j ? A.row_end : j; /* (a search context's row bound) */
+	const int64_t ib64 = A.end - tri < jb ? A.end - tri : jb;
 	const int32_t ch_full = A.chunk; /* sequences per group stream (<= CH): shorter tiles when the range is small */
 	constexpr int NGW = NG * WPB; /* row streams of the workgroup-tile */
 	const int32_t i_begin = (int32_t)ia64 + chunk * (NGW * ch_full);

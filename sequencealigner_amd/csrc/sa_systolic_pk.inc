@@ -309,7 +309,8 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 		const int32_t j = jh[h];
 		tri[h] = (int64_t)j * (j - 1) / 2;
 		const int64_t a = A.start > tri[h] ? A.start - tri[h] : 0;
-		const int64_t b = A.end - tri[h] < j ? A.end - tri[h] : j;
+		const int64_t jb = A.row_end && A.row_end < j ? A.row_end : j; /* (a search context's row bound) */
+		const int64_t b = A.end - tri[h] < jb ? A.end - tri[h] : jb;
 		ia[h] = (int32_t)a;
 		ib[h] = (int32_t)(b > a ? b : a);
 		offj[h] = uload(A.off + j);
