@@ -864,6 +864,68 @@ int sa_host_write_search(const char *path, const struct sa_host_store *db, const
 	return rc;
 }
 
+/* --query --hits-by (include/seqalign_hip.h: sa_hip_search_norm / _pid): /hit_values, /hit_quantity, /hit_scale, for a normalised
+ * kind /database_denominators and /query_denominators, with `vrect` /query_values, added to the finished file of sa_host_write_search.
+ * Everything that can be refused is refused while the file is open read-only. */
+int sa_host_write_search_values(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
+				const int32_t *value, int32_t kind, int32_t source, int32_t rule_or_denom, const int32_t *denominators,
+				const int32_t *vrect)
+{
+	if (!path || !db || !queries || !value)
+		return fail("Hit value data missing");
+	const size_t n = (size_t)db->in.num, m = (size_t)queries->in.num;
+	if (db->in.num < 1 || queries->in.num < 1)
+		return fail("A search needs a database and queries");
+	if (k < 1 || k > SA_HIP_NEIGHBORS_MAX || (size_t)k > n)
+		return fail("Hit count must be between 1 and %d and at most the number of database sequences", SA_HIP_NEIGHBORS_MAX);
+	if (kind != 1 && kind != 2)
+		return fail("Hit quantity kind %d is neither normalised score (1) nor percent identity (2)", kind);
+	if (kind == 1 && source != SA_NORM_SELF && source != SA_NORM_LENGTH)
+		return fail("Normalization source %d is neither self-score (%d) nor length (%d)", source, (int)SA_NORM_SELF, (int)SA_NORM_LENGTH);
+	if (kind == 1 && rule_or_denom != SA_NORM_MIN && rule_or_denom != SA_NORM_MAX && rule_or_denom != SA_NORM_MEAN)
+		return fail("Normalization rule %d is none of min (%d), max (%d), mean (%d)", rule_or_denom, (int)SA_NORM_MIN, (int)SA_NORM_MAX,
+			    (int)SA_NORM_MEAN);
+	if (kind == 2 && rule_or_denom != SA_PID_COLUMNS && rule_or_denom != SA_PID_SHORTER && rule_or_denom != SA_PID_LONGER && rule_or_denom != SA_PID_MEAN)
+		return fail("Identity denominator %d is none of columns (%d), shorter (%d), longer (%d), mean (%d)", rule_or_denom, (int)SA_PID_COLUMNS,
+			    (int)SA_PID_SHORTER, (int)SA_PID_LONGER, (int)SA_PID_MEAN);
+	if (kind == 1 && !denominators)
+		return fail("Hit value data missing");
+	for (size_t q = 0; q < m; q++)
+		for (size_t t = 1; t < (size_t)k; t++)
+			if (value[q * (size_t)k + t] > value[q * (size_t)k + t - 1])
+				return fail("Hit values of query %zu are not in descending order", q);
+	const int32_t what[3] = { kind, kind == 1 ? source : 0, rule_or_denom }, scale = SA_NORM_SCALE;
+	const struct side_set sets[6] = { { "/hit_values", 2, { m, (hsize_t)k }, SIDE_I32, value, false },
+					  { "/hit_quantity", 1, { 3 }, SIDE_I32, what, false },
+					  { "/hit_scale", 1, { 1 }, SIDE_I32, &scale, false },
+					  { "/database_denominators", 1, { n }, SIDE_I32, kind == 1 ? denominators : NULL, true },
+					  { "/query_denominators", 1, { m }, SIDE_I32, kind == 1 ? denominators + n : NULL, true },
+					  { "/query_values", 2, { m, n }, SIDE_I32, vrect, true } };
+	/* read-only first: the file is a search's, of this shape, and has none of the datasets yet */
+	hid_t file;
+	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDONLY, H5P_DEFAULT); } H5E_END_TRY
+	if (file < 0)
+		return fail("Failed to open HDF5 file: %s", path);
+	int rc = 0;
+	hsize_t dims[2] = { 0, 0 };
+	hid_t set = -1, space = -1;
+	H5E_BEGIN_TRY {
+		set = H5Lexists(file, "/hit_indices", H5P_DEFAULT) > 0 ? H5Dopen2(file, "/hit_indices", H5P_DEFAULT) : -1;
+		space = set >= 0 ? H5Dget_space(set) : -1;
+	} H5E_END_TRY
+	if (space < 0 || H5Sget_simple_extent_ndims(space) != 2 || H5Sget_simple_extent_dims(space, dims, NULL) != 2 || dims[0] != m || dims[1] != (hsize_t)k)
+		rc = fail("%s holds no /hit_indices of %zu x %d hits: the values belong to the file of a search", path, m, k);
+	if (space >= 0)
+		H5Sclose(space);
+	if (set >= 0)
+		H5Dclose(set);
+	for (int d = 0; d < 6 && !rc; d++)
+		if (H5Lexists(file, sets[d].name, H5P_DEFAULT) > 0)
+			rc = fail("%s already holds %s", path, sets[d].name);
+	H5Fclose(file);
+	return rc ? rc : write_side_sets(path, NULL, 0, false, sets, 6);
+}
+
 /* The score graph as CSR (include/seqalign_hip.h: sa_hip_edges): /edge_offsets N + 1 I64LE, /edge_indices and /edge_scores
  * E = offsets[N] I32LE each (extent 0 when there is no edge).  create: as write_side_sets has it.  The arrays are checked before
  * anything is opened: offsets[0] == 0, offsets non-decreasing, every index in [0, N). */

@@ -92,6 +92,16 @@ int sa_host_write_alignments(const char *path, const struct sa_host_store *s, in
 int sa_host_write_search(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
 			 const int32_t *index, const int32_t *score, const int32_t *rect, const struct sa_aln *records, const uint32_t *cigar,
 			 int64_t runs);
+/* --query --hits-by: the values the hits were ranked by, ADDED to the finished file of sa_host_write_search at `path`, whose other
+ * datasets stay as they are: /hit_values (M x k I32LE, parts per million; row q descending, ties by index ascending), /hit_quantity
+ * (3 I32LE: kind 1 = normalised score, 2 = percent identity; source, SA_NORM_SELF / SA_NORM_LENGTH, or 0; rule, SA_NORM_MIN / _MAX /
+ * _MEAN, or the denominator SA_PID_*), /hit_scale (1 I32LE: SA_NORM_SCALE); kind 1 with `denominators` (N + M, database first) also
+ * /database_denominators (N) and /query_denominators (M); with `vrect` (or NULL) also /query_values (M x N I32LE).  The arguments are
+ * checked, and the file is looked at read-only -- it holds /hit_indices of extent M x k and none of the datasets to add -- before it
+ * is opened for writing: a file this call cannot finish is left as it was. */
+int sa_host_write_search_values(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
+				const int32_t *value, int32_t kind, int32_t source, int32_t rule_or_denom, const int32_t *denominators,
+				const int32_t *vrect);
 /* --min-score: /edge_offsets (N + 1 I64LE), /edge_indices and /edge_scores (E = offsets[N] I32LE each; extent 0 when E = 0),
  * the CSR arrays of sa_hip_edges / sa_zjob_edges.  `create` as in sa_host_write_neighbors: 0 adds the three datasets to the
  * finished file at `path`, 1 writes a new file with /sequences and the three (--edges-only).  offsets[0] != 0, decreasing

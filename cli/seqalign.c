@@ -31,6 +31,9 @@
  *             database sequences of every query selected on the device: /query_sequences, /hit_indices and /hit_scores, with
  *             --alignments /hit_alignment_records, /hit_cigar_offsets and /hit_cigars, with --query-scores /query_scores; only the
  *             M x N query-database pairs are aligned, no /similarity_matrix)
+ *             --hits-by QUANTITY  (with --query: the hits ranked by a normalised score or by percent identity instead of the raw score:
+ *             /hit_values beside /hit_indices, /hit_scores the raw score of each hit, /hit_quantity, /hit_scale, the denominators,
+ *             with --query-scores /query_values)
  * Flow (main, one function per phase): options -> banner -> load + filter -> output plan -> the first pass (tile job | one selection only |
  * host matrix | the search) -> per selection, in the order of the file: its second pass where the first left it unanswered, then its
  * datasets (a search: its alignments, then its one file) -> -B report.
@@ -141,6 +144,11 @@ struct options {
 	/* --query FILE: a search of FILE's sequences against the input; -k is then the hits per query.  --query-scores: /query_scores too */
 	const char *query;
 	bool query_scores;
+	/* --hits-by QUANTITY: what the hits of a search are ranked by -- kind 0 the score (as without the option), 1 a normalised score
+	 * (hits_source, hits_rule), 2 percent identity (hits_denom) */
+	bool hits_by;
+	int32_t hits_kind, hits_source, hits_rule, hits_denom;
+	const char *hits_name;
 };
 
 static void usage(const char *argv0)
@@ -241,6 +249,17 @@ static void usage(const char *argv0)
 	       "                           the --*-only modes or any other selection (--min-score, --min-quantile, --linkage,\n"
 	       "                           --clusters, --clusters-quantile, --linkage-method, --quantiles, --normalize, --identity)\n"
 	       "      --query-scores       With --query: also /query_scores (M x N), every query-database score\n"
+	       "      --hits-by QUANTITY   With --query: rank the hits by QUANTITY = score (as without the option) | self-min |\n"
+	       "                           self-max | self-mean | len-min | len-max | len-mean (the normalised scores of --normalize,\n"
+	       "                           the denominators those of the database sequence and the query) | identity-columns |\n"
+	       "                           identity-shorter | identity-longer | identity-mean (the percent identity of --identity).\n"
+	       "                           Values are in parts per million.  Writes /hit_values (M x K, descending, ties by index\n"
+	       "                           ascending) beside /hit_indices; /hit_scores is then the raw score of each hit and NO LONGER\n"
+	       "                           SORTED.  Also /hit_quantity (kind 1 = normalised, 2 = identity; source or 0; rule or\n"
+	       "                           denominator, numbered as /normalization_rule and /identity_rule), /hit_scale (1000000), for\n"
+	       "                           the normalised kinds /database_denominators (N) and /query_denominators (M), and with\n"
+	       "                           --query-scores /query_values (M x N) beside /query_scores, which stays raw.  --alignments\n"
+	       "                           is unchanged (a = the query, b = its hit)\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -302,7 +321,8 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "min-score", 5, true }, { "edges-only", 6, false }, { "linkage", 7, false }, { "clusters", 8, true },
 		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
 		     { "quantiles", 12, true }, { "normalize", 13, true }, { "identity", 14, true },
-		     { "linkage-method", 15, true }, { "query", 16, true }, { "query-scores", 17, false }, { NULL, 0, false } };
+		     { "linkage-method", 15, true }, { "query", 16, true }, { "query-scores", 17, false }, { "hits-by", 18, true },
+	     { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
 		const char *arg = argv[k];
@@ -515,6 +535,33 @@ static int parse_args(int argc, char **argv, struct options *o)
 			}
 			case 16: o->query = val; break;
 			case 17: o->query_scores = true; break;
+			case 18: {
+				static const struct {
+					const char *name;
+					int32_t kind, source, rule, denom;
+				} BY[] = { { "score", 0, 0, 0, 0 },
+					   { "self-min", 1, SA_NORM_SELF, SA_NORM_MIN, 0 }, { "self-max", 1, SA_NORM_SELF, SA_NORM_MAX, 0 },
+					   { "self-mean", 1, SA_NORM_SELF, SA_NORM_MEAN, 0 }, { "len-min", 1, SA_NORM_LENGTH, SA_NORM_MIN, 0 },
+					   { "len-max", 1, SA_NORM_LENGTH, SA_NORM_MAX, 0 }, { "len-mean", 1, SA_NORM_LENGTH, SA_NORM_MEAN, 0 },
+					   { "identity-columns", 2, 0, 0, SA_PID_COLUMNS }, { "identity-shorter", 2, 0, 0, SA_PID_SHORTER },
+					   { "identity-longer", 2, 0, 0, SA_PID_LONGER }, { "identity-mean", 2, 0, 0, SA_PID_MEAN } };
+				o->hits_by = false;
+				for (size_t t = 0; t < sizeof(BY) / sizeof(BY[0]); t++)
+					if (!strcmp(val, BY[t].name)) {
+						o->hits_by = true;
+						o->hits_kind = BY[t].kind;
+						o->hits_source = BY[t].source;
+						o->hits_rule = BY[t].rule;
+						o->hits_denom = BY[t].denom;
+						o->hits_name = BY[t].name;
+					}
+				if (!o->hits_by) {
+					err("Hit quantity must be one of score, self-min, self-max, self-mean, len-min, len-max, len-mean, identity-columns, "
+					    "identity-shorter, identity-longer, identity-mean: %s", val);
+					return 1;
+				}
+				break;
+			}
 			}
 			if (is_long || OPTS[idx].takes)
 				break;
@@ -626,7 +673,7 @@ struct run {
 	struct { int32_t *index, *score; bool done, second_pass; double seconds; } nb;
 	/* --query: the queries, the hits (M x K), with --query-scores the rectangle (M x N), with --alignments the M x K records */
 	struct sa_host_store queries;
-	struct { int32_t *index, *score, *rect; sa_alns *alns; double hits_seconds, gather_seconds; int32_t batches; } sr;
+	struct { int32_t *index, *score, *rect, *value, *vrect; sa_alns *alns; double hits_seconds, gather_seconds; int32_t batches; } sr;
 	struct { double seconds; long long runs; } trace;
 	struct { /* the fractions' ranks: one select call answers all of them, where the matrix is */
 		int64_t ranks[SA_HIP_SELECT_MAX], below[SA_HIP_SELECT_MAX];
@@ -785,6 +832,8 @@ static int set_up(int argc, char **argv, struct run *r)
 		ok = (err("Missing required option: -o, --output"), false);
 	if (ok && o->query_scores && !o->query)
 		ok = (err("Option --query-scores requires --query"), false);
+	if (ok && o->hits_by && !o->query)
+		ok = (err("Option --hits-by requires --query: it ranks the hits of a search"), false);
 	if (ok && o->query && !o->neighbors)
 		ok = (err("Option --query requires -k, --neighbors: the number of hits per query"), false);
 	if (ok && o->query && query_conflict(o))
@@ -882,9 +931,11 @@ static void banner(const struct run *r)
 		info("Gap open: %d, extend: %d", r->sc.gap_opn, r->sc.gap_ext);
 	if (o->filter > 0.0f)
 		info("Filter threshold: %.1f%%", (double)o->filter * 100.0);
-	if (o->query)
+	if (o->query) {
 		info("Queries: %s, the %d best database sequences of each (no similarity matrix)", o->query, o->neighbors);
-	else if (o->neighbors)
+		if (o->hits_by && o->hits_kind)
+			info("Hits ranked by %s, in parts per million (the hit scores stay raw)", o->hits_name);
+	} else if (o->neighbors)
 		info("Neighbors: %d per sequence%s", o->neighbors, o->neighbors_only ? " (no similarity matrix)" : "");
 	if (o->min_q >= 0)
 		info("Score graph: pairs that score at least the %g quantile of the scores%s", o->quantiles[o->min_q],
@@ -934,6 +985,20 @@ static bool load_queries(struct run *r)
 		r->sr.rect = malloc(sizeof(int32_t) * m * r->n);
 	if (!r->sr.index || !r->sr.score || (o->query_scores && !r->sr.rect))
 		return failed("Out of memory allocating search results");
+	/* --hits-by: the quantity of the search, carried as the quantity of every selection is (kind 0: the scores, q stays empty) */
+	if (o->hits_by && o->hits_kind) {
+		r->norm_spec = (struct sa_norm){ o->hits_source, o->hits_rule, NULL };
+		r->sr.value = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+		if (o->query_scores)
+			r->sr.vrect = malloc(sizeof(int32_t) * m * r->n);
+		if (o->hits_kind == 1) {
+			r->norm_spec.denominators = malloc(sizeof(int32_t) * (r->n + m));
+			r->q.norm = &r->norm_spec;
+		} else
+			r->q.pid = &o->hits_denom;
+		if (!r->sr.value || (o->query_scores && !r->sr.vrect) || (r->q.norm && !r->norm_spec.denominators))
+			return failed("Out of memory allocating search results");
+	}
 	return true;
 }
 
@@ -1168,13 +1233,18 @@ static bool run_search(struct run *r)
 	const struct options *o = &r->o;
 	info("Search: %d queries against %zu database sequences, %d hits per query selected on the device", r->queries.in.num, r->n, o->neighbors);
 	const double t0 = now();
-	if (!sa_hip_search(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.score, r->sr.rect))
+	/* (the *_norm call with norm == NULL is sa_hip_search itself) */
+	if (!(r->q.pid ? sa_hip_search_pid(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->sr.rect,
+					   r->sr.vrect, *r->q.pid)
+		       : sa_hip_search_norm(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->sr.rect,
+					    r->sr.vrect, r->q.norm)))
 		return failed(sa_last_error());
 	const double call = now() - t0;
 	stamp("sa_hip_search returned");
+	r->t_quantity = sa_hip_last_search_quantity_seconds();
 	finish_progress(r);
 	sa_hip_last_search_breakdown(&r->t_align, &r->sr.gather_seconds, &r->sr.hits_seconds, &r->sr.batches);
-	const double device = sa_hip_last_search_seconds();
+	const double device = sa_hip_last_search_seconds() + (r->q.norm ? r->t_quantity : 0.0);
 	r->t_setup = call > device ? call - device : 0.0;
 	return true;
 }
@@ -1211,8 +1281,14 @@ static bool write_search(struct run *r)
 	int64_t runs = 0;
 	const uint32_t *cigar = r->sr.alns ? sa_alns_cigar(r->sr.alns, &runs) : NULL;
 	r->trace.runs = (long long)runs;
-	return WRITE_OUT(r, sa_host_write_search(o->output, &r->store, &r->queries, o->neighbors, r->sr.index, r->sr.score, r->sr.rect,
-						 r->sr.alns ? sa_alns_records(r->sr.alns) : NULL, cigar, runs), "search written");
+	if (!WRITE_OUT(r, sa_host_write_search(o->output, &r->store, &r->queries, o->neighbors, r->sr.index, r->sr.score, r->sr.rect,
+					       r->sr.alns ? sa_alns_records(r->sr.alns) : NULL, cigar, runs), "search written"))
+		return false;
+	if (!r->q.norm && !r->q.pid)
+		return true;
+	return WRITE_OUT(r, sa_host_write_search_values(o->output, &r->store, &r->queries, o->neighbors, r->sr.value, r->q.norm ? 1 : 2,
+							r->q.norm ? r->q.norm->source : 0, r->q.norm ? r->q.norm->rule : *r->q.pid,
+							r->q.norm ? r->q.norm->denominators : NULL, r->sr.vrect), "hit values written");
 }
 
 /* the matrix into host memory, then the file from there */
@@ -1417,6 +1493,11 @@ static void report(const struct run *r)
 	if (o->query) {
 		printf("  (hit selection on the device, K = %d: %.6f sec; rows gathered in %.6f sec; %d batches of queries)\n", o->neighbors,
 		       r->sr.hits_seconds, r->sr.gather_seconds, r->sr.batches);
+		if (r->q.norm)
+			printf("  (hits by %s on the device: denominators + sweep over %lld pairs, %.6f sec)\n", o->hits_name, r->npairs, r->t_quantity);
+		if (r->q.pid)
+			printf("  (hits by %s on the device: one identity sweep over %lld pairs, scores and values together, %.6f sec)\n", o->hits_name,
+			       r->npairs, r->t_quantity);
 		if (o->alignments)
 			printf("  (alignments of the %lld hit pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
 			       (long long)r->queries.in.num * o->neighbors, r->trace.seconds, r->trace.runs);
@@ -1439,9 +1520,9 @@ static void report(const struct run *r)
 		       r->lk.second_pass ? AGAIN : "");
 	if (o->has_clusters)
 		printf("  (clusters at score >= %d: %d)\n", o->clusters_at, r->lk.clusters);
-	if (r->q.norm)
+	if (r->q.norm && !o->query)
 		printf("  (Normalisation on the device, %s: denominators + sweep over %lld pairs, %.6f sec)\n", o->norm_name, r->npairs, r->t_quantity);
-	if (r->q.pid)
+	if (r->q.pid && !o->query)
 		printf("  (Percent identity on the device, over %s: one sweep over %lld pairs, %.6f sec)\n", o->pid_name, r->npairs, r->t_quantity);
 	printf("Alignments per second: %.2f\n", r->t_align > 0 ? (double)r->npairs / r->t_align : 0.0);
 }
@@ -1459,6 +1540,8 @@ static void release(struct run *r)
 	free(r->sr.index);
 	free(r->sr.score);
 	free(r->sr.rect);
+	free(r->sr.value);
+	free(r->sr.vrect);
 	sa_host_store_free(&r->queries);
 	sa_host_store_free(&r->store);
 	stamp("released");

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls, then the *_search* / *_hits calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls, then the *_search* / *_hits calls, then the *_rect / _hits_take / sa_hip_search_norm / _pid calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -328,6 +328,59 @@ bool sa_hip_search(struct sa_input db, struct sa_input queries, const struct sa_
 double sa_hip_last_search_seconds(void);
 void sa_hip_last_search_breakdown(double *align, double *gather, double *hits, int32_t *batches);
 
+/* ---- search: hits ranked by a value -- normalised score or percent identity -- instead of the raw score ---------------------
+ * No reference counterpart.  A raw score grows with length: against a database of mixed lengths the k "best" hits of a query are
+ * led by the long entries, and "which database sequences are at least 90 % identical to my query" cannot be asked.  The
+ * quantities are the ones the all-vs-all selections read ("normalised scores" and "percent identity" below), at rectangle pitch.
+ * Pair and orientation: for query q and database sequence d the pair is (d, N + q) of the concatenated store, already canonical:
+ * i = d is the row sequence, j = N + q the column sequence.  Values are in parts per million (SA_NORM_SCALE):
+ *   normalised   sa_norm_value(rect[q * N + d], den[d], den[N + q], rule); den holds the N + M denominators of the concatenated
+ *                store.  sa_ctx_denominators on a search context gives exactly these N + M (d_den: N + M int32); a caller may
+ *                pass denominators of their own.
+ *   identity     sa_pid_value(identities, columns, len_d, len_query, denom) of the canonical alignment of (d, N + q): exactly the
+ *                numbers sa_ctx_identity_range gives that pair on a context of the concatenated store.
+ * Hits by value: all d in [0, N) ordered value DESCENDING, then d ASCENDING, the first k taken -- the key of sa_ctx_hits,
+ * unchanged: sa_ctx_hits over a value rectangle selects them.  Every hit also carries its raw score (sa_ctx_hits_take).
+ *
+ * sa_ctx_normalize_rect   device-resident, asynchronous on `stream`, no scratch, no host synchronisation: rows [0, nq) of a
+ *          rectangle of pitch N whose row r is query q0 + r: d_out[r * N + d] = value of d_rect[r * N + d].  d_den: N + M int32 of
+ *          device memory.  d_out == d_rect (in place) or disjoint; partial overlap is the caller's error.  4-byte alignment is
+ *          enough (an offset view will do).  Refused before any launch: a context of sa_ctx_create, a null pointer, a rule outside
+ *          its enum, q0 < 0, nq < 1 or q0 + nq > M, a misaligned pointer.
+ * sa_ctx_identity_rect   the dense form of sa_ctx_identity_range for a search context: queries [q0, q0 + nq), element
+ *          (q - q0) * N + d of every non-NULL output of *d_out.  Same struct, same subset rule, same refusals (and a context of
+ *          sa_ctx_create, queries outside [0, M)); like that call it uses the context's strip-boundary scratch and payload buffer
+ *          and does not run beside sa_ctx_search_range, sa_ctx_denominators or another identity call of the SAME context on
+ *          another stream; in order on one stream is fine.
+ * sa_ctx_hits_take   d_out[r * k + t] = d_rect[r * N + d_index[r * k + t]] for rows [0, nq): the raw scores of hits that were
+ *          selected on a value rectangle.  An index outside [0, N) reads nothing and gives INT32_MIN.  nq and k as sa_ctx_hits.
+ * sa_hip_search_norm / _pid   one call, host in / host out, first device.  index, value, score are M x k; rect holds the raw
+ *          scores and vrect the values, both M x N.  Any of value, score, rect, vrect may be NULL; index may be NULL only when
+ *          nothing M x k is wanted.  Row q of index / value is ordered by value descending, then index ascending; score is the raw
+ *          score of each hit and is not sorted.  norm == NULL is exactly sa_hip_search, with value a copy of score and vrect a
+ *          copy of rect.  norm->denominators, when not NULL, receives N + M values.  _pid runs no packed alignment: the identity
+ *          sweep delivers score and pid together.  Stream order, norm: range, rows to pitch N, denominators (once per call),
+ *          sweep into the value rectangle, sa_ctx_hits on it, take; pid: identity sweep, hits, take.  The queries go in batches
+ *          sized as sa_hip_search sizes them with the extra rectangle counted -- per query 4 (N + M) bytes (norm only) + 8 N +
+ *          20 k (with hits) -- and SA_HIP_SEARCH_BATCH_BYTES caps a batch.  Every argument is checked before a device is looked
+ *          for.
+ * sa_hip_last_search_quantity_seconds   the device time of denominators + sweep, or of the identity sweep, summed over the
+ *          batches of the last successful sa_hip_search_norm / _pid call (0 after norm == NULL).  sa_hip_last_search_seconds /
+ *          _breakdown answer for these calls as well: alignment (under percent identity the sweep itself, which delivers the
+ *          scores), gather, selection + take, batches; the quantity's time is not in them except in that case.
+ * Non-zero / false + sa_last_error on failure. */
+struct sa_norm;
+struct sa_identity_out;
+int sa_ctx_normalize_rect(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, int32_t q0, const int32_t *d_den, int32_t rule, int32_t *d_out,
+			  void *stream);
+int sa_ctx_identity_rect(sa_ctx *ctx, int32_t q0, int32_t nq, const struct sa_identity_out *d_out, void *stream);
+int sa_ctx_hits_take(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, int32_t k, const int32_t *d_index, int32_t *d_out, void *stream);
+bool sa_hip_search_norm(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *value,
+			int32_t *score, int32_t *rect, int32_t *vrect, const struct sa_norm *norm);
+bool sa_hip_search_pid(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *value,
+		       int32_t *score, int32_t *rect, int32_t *vrect, int32_t denom);
+double sa_hip_last_search_quantity_seconds(void);
+
 /* ---- alignments for chosen pairs: traceback on the device, run-length CIGARs ----------------------------------------
  * No reference counterpart: the reference keeps scores only.  For an explicit list of pairs (a[t], b[t]) of one store,
  * a != b, any order, duplicates allowed (the natural list: the N x k neighbours), the device repeats the exact s32 sweep of
@@ -536,7 +589,8 @@ struct sa_norm {
 };
 /* host only: the value rule above for one entry.  INT32_MIN + sa_last_error for a rule outside the enum. */
 int32_t sa_norm_value(int32_t s, int32_t di, int32_t dj, int32_t rule);
-/* device-resident, asynchronous on `stream`: d_den = N int32 of device memory.  SA_NORM_SELF runs one wavefront per sequence
+/* device-resident, asynchronous on `stream`: d_den = N int32 of device memory (on a search context: the N + M of the
+ * concatenated store, database first).  SA_NORM_SELF runs one wavefront per sequence
  * over the context's strip-boundary scratch, so -- like sa_ctx_alignments -- it does not run beside sa_ctx_align_range (or
  * another sa_ctx_denominators) of the SAME context on another stream; in order on one stream is fine.  SA_NORM_LENGTH copies
  * the lengths.  Non-zero + sa_last_error for a null pointer or a source outside the enum, nothing launched. */

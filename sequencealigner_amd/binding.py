@@ -72,6 +72,8 @@ ABI_SYMBOLS = (
     "sa_agglo_labels", "sa_hip_last_agglomerate_seconds", "sa_hip_last_agglomerate_rescans",
     "sa_ctx_create_search", "sa_ctx_search_db", "sa_ctx_search_queries", "sa_search_scratch_bytes", "sa_ctx_search_range",
     "sa_hits_scratch_bytes", "sa_ctx_hits", "sa_hip_search", "sa_hip_last_search_seconds", "sa_hip_last_search_breakdown",
+    "sa_ctx_normalize_rect", "sa_ctx_identity_rect", "sa_ctx_hits_take", "sa_hip_search_norm", "sa_hip_search_pid",
+    "sa_hip_last_search_quantity_seconds",
 )
 
 
@@ -353,6 +355,17 @@ def load_library() -> C.CDLL:
     lib.sa_hip_last_search_seconds.restype = C.c_double
     lib.sa_hip_last_search_breakdown.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     lib.sa_hip_last_search_breakdown.restype = None
+    lib.sa_ctx_normalize_rect.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_normalize_rect.restype = C.c_int
+    lib.sa_ctx_identity_rect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_IdentityOut), C.c_void_p]
+    lib.sa_ctx_identity_rect.restype = C.c_int
+    lib.sa_ctx_hits_take.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_hits_take.restype = C.c_int
+    lib.sa_hip_search_norm.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(_Norm)]
+    lib.sa_hip_search_norm.restype = C.c_bool
+    lib.sa_hip_search_pid.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_int32] + [C.c_void_p] * 5 + [C.c_int32]
+    lib.sa_hip_search_pid.restype = C.c_bool
+    lib.sa_hip_last_search_quantity_seconds.restype = C.c_double
     _lib = lib
     return lib
 
@@ -1325,16 +1338,86 @@ class SearchContext(Context):
                                  C.c_void_p(d_score_ptr), C.c_void_p(d_scratch_ptr), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def normalize_rect(self, d_rect_ptr: int, nq: int, q0: int, d_den_ptr: int, rule: int, d_out_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_normalize_rect: rows [0, nq) of a device rectangle of pitch N whose row r is query q0 + r, divided by the
+        denominators d_den (N + M int32 of device memory: denominators() of this context, or the caller's own) under `rule`, into
+        d_out -- d_rect itself (in place) or a disjoint buffer -- asynchronously on `stream`"""
+        if self._lib.sa_ctx_normalize_rect(self._h, C.c_void_p(d_rect_ptr or None), _int32("nq", nq), _int32("q0", q0),
+                                           C.c_void_p(d_den_ptr or None), _int32("rule", rule), C.c_void_p(d_out_ptr or None), C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def identity_rect(self, q0: int, nq: int, score: int = 0, identities: int = 0, columns: int = 0, pid: int = 0, denom: int = 0,
+                      stream: int = 0) -> None:
+        """sa_ctx_identity_rect: score / identities / columns / pid of queries [q0, q0 + nq) against every database sequence into
+        the device arrays given (nq * N int32 each, element (q - q0) * N + d; 0: not asked for; `denom` is read iff pid),
+        asynchronously on `stream`; not beside another sweep of this context on another stream"""
+        out = _IdentityOut(score or None, identities or None, columns or None, pid or None, _denom(denom))
+        if self._lib.sa_ctx_identity_rect(self._h, _int32("q0", q0), _int32("nq", nq), C.byref(out), C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def hits_take(self, d_rect_ptr: int, nq: int, k: int, d_index_ptr: int, d_out_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_hits_take: d_out[r, t] = d_rect[r, d_index[r, t]] for rows [0, nq) -- the raw scores of hits selected on a value
+        rectangle"""
+        if self._lib.sa_ctx_hits_take(self._h, C.c_void_p(d_rect_ptr or None), _int32("nq", nq), _int32("k", k), C.c_void_p(d_index_ptr or None),
+                                      C.c_void_p(d_out_ptr or None), C.c_void_p(stream)):
+            raise AlignError(_err())
+
 
 def hits_scratch_bytes(n_db: int, nq: int, k: int) -> int:
     """device bytes SearchContext.hits needs as scratch (0: none, the rows alone fill the device)"""
     return int(load_library().sa_hits_scratch_bytes(_int32("n_db", n_db), _int32("nq", nq), _int32("k", k)))
 
 
-def hip_search(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: Optional[int] = None, rect: bool = False):
+def _search_quantity(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: Optional[int], rect: bool, norm: Optional["Norm"],
+                     pid: Optional[int]):
+    """sa_hip_search_norm / sa_hip_search_pid: (index, value, score[, rect, vrect][, denominators])"""
+    n, m = db.num, queries.num
+    if k is None and not rect:
+        raise AlignError("hip_search: nothing asked for (k is None and rect is False)")
+    kk = 0 if k is None else _int32("k", k)
+    index = value = score = out = vout = None
+    if k is not None:
+        rows = max(m, 1) * max(min(kk, NEIGHBORS_MAX), 1)
+        index, value, score = (np.empty(rows, np.int32) for _ in range(3))
+    if rect:
+        out, vout = np.empty((max(m, 0), max(n, 0)), np.int32), np.empty((max(m, 0), max(n, 0)), np.int32)
+    ptr = [None if a is None else a.ctypes.data for a in (index, value, score, out, vout)]
+    sc = scoring._as_c()
+    lib = load_library()
+    tail = ()
+    if norm is not None:
+        cn, den = norm._as_c(n + m)
+        ok = lib.sa_hip_search_norm(db._as_c(), queries._as_c(), C.byref(sc), kk, *ptr, C.byref(cn))
+        tail = (den[:n + m],)
+    elif pid is not None:
+        ok = lib.sa_hip_search_pid(db._as_c(), queries._as_c(), C.byref(sc), kk, *ptr, _denom(pid))
+    else:  # (values=True without a quantity: norm == NULL, value a copy of score)
+        ok = lib.sa_hip_search_norm(db._as_c(), queries._as_c(), C.byref(sc), kk, *ptr, None)
+    if not ok:
+        raise AlignError(_err())
+    res = ()
+    if k is not None:
+        res += tuple(a[:m * kk].reshape(m, kk) for a in (index, value, score))
+    if rect:
+        res += (out, vout)
+    return res + tail
+
+
+def hip_search(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: Optional[int] = None, rect: bool = False,
+               norm: Optional["Norm"] = None, pid: Optional[int] = None, values: bool = False):
     """sa_hip_search: queries against a database on the first device.  With k: (index, score), two (M, k) int32 arrays, row q
     lists the database sequences by score descending, then index ascending; 1 <= k <= min(N, NEIGHBORS_MAX).  With rect=True
-    the (M, N) int32 rectangle rect[q, d] follows (alone when k is None)."""
+    the (M, N) int32 rectangle rect[q, d] follows (alone when k is None).
+
+    With a quantity -- norm=Norm(source, rule): normalised scores, or pid=PID_*: percent identity, both in parts per million
+    (sa_hip_search_norm / sa_hip_search_pid) -- or with values=True the hits are ranked by the value and the result is
+    (index, value, score[, rect, vrect]): value descending, then index ascending; score is the raw score of each hit, not sorted;
+    vrect the (M, N) values.  A norm appends the N + M denominators (database first).  values=True without a quantity gives value
+    = score and vrect = rect.  Asking for both quantities is a ValueError."""
+    if norm is not None and pid is not None:
+        raise ValueError("hip_search: norm and pid exclude each other")
+    if norm is not None or pid is not None or values:
+        return _search_quantity(db, queries, scoring, k, rect, norm, pid)
     n, m = db.num, queries.num
     if k is None and not rect:
         raise AlignError("hip_search: nothing asked for (k is None and rect is False)")
@@ -1360,6 +1443,12 @@ def hip_search(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: O
 def last_search_seconds() -> float:
     """device time of the last hip_search call: alignment + gather + selection, summed over its batches"""
     return float(load_library().sa_hip_last_search_seconds())
+
+
+def last_search_quantity_seconds() -> float:
+    """device time of denominators + sweep (norm=) or of the identity sweep (pid=) of the last hip_search call with a quantity,
+    summed over its batches"""
+    return float(load_library().sa_hip_last_search_quantity_seconds())
 
 
 def last_search_breakdown() -> dict:

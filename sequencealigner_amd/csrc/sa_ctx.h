@@ -214,4 +214,24 @@ bool sa_normalize_in_place(const char *who, sa_ctx *ctx, int32_t *d_packed, cons
 bool sa_identity_denom_check(const char *who, int32_t denom);
 bool sa_identity_in_place(const char *who, sa_ctx *ctx, int32_t *d_packed, int32_t denom, hipStream_t s);
 
+/* ---- what sa_search_quantity.hip (values of the hits: normalised scores, percent identity) takes from its neighbours ---------- */
+/* sa_normalize.hip: the rule inside its enum, or sa_set_error; the denominators of ctx's whole store (N + M on a search context)
+ * into d_den on `s`, the current device being the context's */
+bool sa_norm_rule_check(const char *who, int32_t rule);
+hipError_t sa_denominators_launch(sa_ctx *ctx, int32_t source, int32_t *d_den, hipStream_t s);
+/* sa_identity.hip: the rectangle form of the identity sweep on a search context whose queries [q0, q0 + nq) have been checked:
+ * element (q - q0) * N + d of every non-null output; the outputs are checked as sa_ctx_identity_range checks them */
+bool sa_identity_rect(const char *who, sa_ctx *ctx, int32_t q0, int32_t nq, const struct sa_identity_out *d_out, hipStream_t s);
+/* the boundary payloads of ctx's identity sweeps, allocated now (they are allocated at the first sweep otherwise) */
+bool sa_identity_payload_scratch(sa_ctx *ctx);
+/* sa_search.hip: the checks and launches of sa_ctx_search_range / sa_ctx_hits under another caller's name */
+bool sa_search_ctx_check(const char *who, const sa_ctx *ctx);
+bool sa_search_queries_check(const char *who, const sa_ctx *ctx, int32_t q0, int32_t nq);
+bool sa_hits_check(const char *who, int64_t n_db, int64_t nq, int32_t k);
+/* (`mid`, when not null, is recorded between the alignment of the range and the move of its rows) */
+int sa_search_range_launch(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void *d_scratch, hipStream_t s, hipEvent_t mid);
+/* what sa_hip_last_search_seconds / _breakdown report from now on */
+void sa_search_last_set(double align, double gather, double hits, int32_t batches);
+int sa_hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, hipStream_t s);
+
 #endif /* SA_CTX_H */

@@ -13,6 +13,9 @@
  *                          cell and reduces it with the end key (best descending, r ascending, c ascending).  Lane 0 stores
  *                          whichever of score / identities / columns / pid are asked for at [p - start]; pid is computed from
  *                          the two lengths in the kernel, so a triangle of scores can be overwritten in place.
+ *                          RECT = true is the rectangle form of a search context (sa_ctx_identity_rect): wave item q is element q
+ *                          of the dense outputs and the pair (d, N + q0 + r), q = r N + d -- that mapping is the only difference,
+ *                          the body is the one body.
  * No state is shared between wavefronts: the same input gives the same bytes.
  */
 #include <algorithm>
@@ -20,6 +23,7 @@
 
 #include "sa_ctx.h"
 #include "sa_identity_core.h"
+#include "sa_search_quantity_core.h"
 
 static_assert(SA_ID_DENOM_COLUMNS == SA_PID_COLUMNS && SA_ID_DENOM_SHORTER == SA_PID_SHORTER && SA_ID_DENOM_LONGER == SA_PID_LONGER &&
 		      SA_ID_DENOM_MEAN == SA_PID_MEAN,
@@ -38,6 +42,7 @@ struct IdArgs {
 	int64_t start, count;                          /* packed pair range */
 	int32_t *score, *identities, *columns, *pid;   /* [count] each, any of them null */
 	int32_t denom;                                 /* SA_PID_*, read iff pid */
+	int32_t rect_n;                                /* RECT: the database size N; start is then the first query q0 (in the padding before bnd) */
 	int32_t *bnd;                                  /* per-wave strip boundary columns (M and X): the context's */
 	int64_t bnd_stride;                            /* ints per wave = 2 * (max_len + 2) */
 	sa_id_pay *pbnd;                               /* their payloads (PM and PX): bnd_stride payloads per wave */
@@ -64,7 +69,7 @@ __device__ __forceinline__ sa_id_pay from_left(sa_id_pay p) { return sa_id_make(
 
 __device__ __forceinline__ sa_id_pay shfl_xor(sa_id_pay p, int d) { return sa_id_make(__shfl_xor(p.identities, d, 64), __shfl_xor(p.columns, d, 64)); }
 
-template <int METHOD>
+template <int METHOD, bool RECT>
 __global__ __launch_bounds__(256) void sa_k_identity(IdArgs A)
 {
 	__shared__ int32_t s_sub[SA_SUB_DIM * SA_SUB_DIM];
@@ -94,7 +99,10 @@ __global__ __launch_bounds__(256) void sa_k_identity(IdArgs A)
 
 	for (int64_t q = wave; q < A.count; q += nwaves) {
 		int32_t i, j;
-		unpack_pair(A.start + q, i, j);
+		if (RECT)
+			sa_sq_identity_item(A.rect_n, (int32_t)A.start, q, &i, &j);
+		else
+			unpack_pair(A.start + q, i, j);
 		const int32_t m = A.st.meta[i].len, offi = A.st.meta[i].off; /* rows: seq i    */
 		const int32_t n = A.st.meta[j].len, offj = A.st.meta[j].off; /* columns: seq j */
 		const uint8_t *ci = A.st.codes + offi;
@@ -259,8 +267,9 @@ bool payload_scratch(sa_ctx *ctx)
 	return true;
 }
 
-/* the current device is the context's; the range and the outputs have been checked */
-bool launch_identity(sa_ctx *ctx, int64_t start, int64_t count, const struct sa_identity_out &out, hipStream_t s)
+/* the current device is the context's; the range and the outputs have been checked.  rect_n = 0: the packed range [start,
+ * start + count); rect_n = N > 0: the rectangle form, start the first query and count = nq * N */
+bool launch_identity(sa_ctx *ctx, int64_t start, int64_t count, const struct sa_identity_out &out, hipStream_t s, int32_t rect_n = 0)
 {
 	if (count == 0)
 		return true;
@@ -281,6 +290,7 @@ bool launch_identity(sa_ctx *ctx, int64_t start, int64_t count, const struct sa_
 	a.columns = out.columns;
 	a.pid = out.pid;
 	a.denom = out.pid ? out.denom : 0;
+	a.rect_n = rect_n;
 	a.bnd = ctx->d_scratch;
 	a.bnd_stride = ctx->scratch_stride;
 	a.pbnd = static_cast<sa_id_pay *>(ctx->d_id_scratch);
@@ -288,13 +298,22 @@ bool launch_identity(sa_ctx *ctx, int64_t start, int64_t count, const struct sa_
 	const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->generic_blocks, (count + 3) / 4));
 	switch (ctx->sc.method) {
 	case SA_METHOD_NW:
-		hipLaunchKernelGGL(sa_k_identity<SA_METHOD_NW>, dim3(blocks), dim3(256), 0, s, a);
+		if (rect_n)
+			hipLaunchKernelGGL((sa_k_identity<SA_METHOD_NW, true>), dim3(blocks), dim3(256), 0, s, a);
+		else
+			hipLaunchKernelGGL((sa_k_identity<SA_METHOD_NW, false>), dim3(blocks), dim3(256), 0, s, a);
 		break;
 	case SA_METHOD_GA:
-		hipLaunchKernelGGL(sa_k_identity<SA_METHOD_GA>, dim3(blocks), dim3(256), 0, s, a);
+		if (rect_n)
+			hipLaunchKernelGGL((sa_k_identity<SA_METHOD_GA, true>), dim3(blocks), dim3(256), 0, s, a);
+		else
+			hipLaunchKernelGGL((sa_k_identity<SA_METHOD_GA, false>), dim3(blocks), dim3(256), 0, s, a);
 		break;
 	case SA_METHOD_SW:
-		hipLaunchKernelGGL(sa_k_identity<SA_METHOD_SW>, dim3(blocks), dim3(256), 0, s, a);
+		if (rect_n)
+			hipLaunchKernelGGL((sa_k_identity<SA_METHOD_SW, true>), dim3(blocks), dim3(256), 0, s, a);
+		else
+			hipLaunchKernelGGL((sa_k_identity<SA_METHOD_SW, false>), dim3(blocks), dim3(256), 0, s, a);
 		break;
 	default:
 		sa_set_error("sa_ctx_identity_range: method %d", ctx->sc.method);
@@ -426,6 +445,28 @@ bool hip_identity_impl(struct sa_input in, const struct sa_scoring *sc, int32_t 
 } // namespace
 
 bool sa_identity_denom_check(const char *who, int32_t denom) { return denom_ok(who, denom); }
+
+/* the context's boundary payloads, allocated now instead of at its first sweep: for a caller that sizes buffers from the free memory */
+bool sa_identity_payload_scratch(sa_ctx *ctx) { return payload_scratch(ctx); }
+
+/* the rectangle form on a search context: queries [q0, q0 + nq), element (q - q0) * N + d of every non-null output.  The
+ * context, the queries and the stream's device are the caller's to have checked; the outputs are checked here as
+ * sa_ctx_identity_range checks them. */
+bool sa_identity_rect(const char *who, sa_ctx *ctx, int32_t q0, int32_t nq, const struct sa_identity_out *d_out, hipStream_t s)
+{
+	if (!d_out) {
+		sa_set_error("%s: null argument", who);
+		return false;
+	}
+	if (!outputs_ok(who, d_out->score, d_out->identities, d_out->columns, d_out->pid, d_out->denom))
+		return false;
+	if ((uintptr_t)d_out->score % 4 || (uintptr_t)d_out->identities % 4 || (uintptr_t)d_out->columns % 4 || (uintptr_t)d_out->pid % 4) {
+		sa_set_error("%s: the outputs want 4-byte alignment", who);
+		return false;
+	}
+	SA_HIP_CHECK(hipSetDevice(ctx->device), return false);
+	return launch_identity(ctx, q0, (int64_t)nq * ctx->search_db, *d_out, s, ctx->search_db);
+}
 
 /* pid of every pair over a device matrix of ctx's store, in place of whatever it held, in order on `s`, which is synchronised: what
  * sa_zjob_identity and the *_pid one-call selections share.  The current device is the matrix's. */

@@ -218,6 +218,10 @@ bool rule_ok(const char *who, int32_t rule)
 
 } // namespace
 
+/* for sa_search_quantity.hip (sa_ctx.h) */
+bool sa_norm_rule_check(const char *who, int32_t rule) { return rule_ok(who, rule); }
+hipError_t sa_denominators_launch(sa_ctx *ctx, int32_t source, int32_t *d_den, hipStream_t s) { return launch_denominators(ctx, source, d_den, s); }
+
 /* what every entry point refuses before anything is launched */
 bool sa_norm_check(const char *who, const struct sa_norm *norm)
 {

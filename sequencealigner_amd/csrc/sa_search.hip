@@ -360,6 +360,27 @@ bool search_impl(struct sa_input db, struct sa_input queries, const struct sa_sc
 
 } // namespace
 
+/* for sa_search_quantity.hip (sa_ctx.h) */
+bool sa_search_ctx_check(const char *who, const sa_ctx *ctx) { return search_ctx_check(who, ctx); }
+bool sa_search_queries_check(const char *who, const sa_ctx *ctx, int32_t q0, int32_t nq) { return queries_check(who, ctx, q0, nq); }
+bool sa_hits_check(const char *who, int64_t n_db, int64_t nq, int32_t k) { return hits_check(who, n_db, nq, k); }
+int sa_search_range_launch(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void *d_scratch, hipStream_t s, hipEvent_t mid)
+{
+	return search_range_impl(ctx, q0, nq, d_rect, d_scratch, s, mid);
+}
+void sa_search_last_set(double align, double gather, double hits, int32_t batches)
+{
+	std::lock_guard<std::mutex> g(g_last_mutex);
+	g_last.align = align;
+	g_last.gather = gather;
+	g_last.hits = hits;
+	g_last.batches = batches;
+}
+int sa_hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, hipStream_t s)
+{
+	return hits_launch(d_rect, n_db, nq, k, d_index, d_score, d_scratch, s);
+}
+
 extern "C" size_t sa_search_scratch_bytes(const sa_ctx *ctx, int32_t q0, int32_t nq)
 {
 	return sa_guard("sa_search_scratch_bytes", (size_t)0, [&]() -> size_t {
