@@ -145,6 +145,7 @@ SaPlanInputs sa_plan_inputs(const sa_ctx *ctx)
 	in.env_chunk = ctx->env.chunk;
 	in.no_sort = ctx->env.no_sort;
 	in.no_tokens = ctx->env.no_tokens;
+	in.remainder = !ctx->env.no_remainder;
 	in.row_end = ctx->search_db;
 	return in;
 }

@@ -21,6 +21,7 @@ SaEnv sa_env_read()
 	e.no_pk16 = flag("SA_HIP_NO_PK16");
 	e.no_sort = flag("SA_HIP_NO_SORT");
 	e.no_tokens = flag("SA_HIP_NO_TOKENS");
+	e.no_remainder = flag("SA_HIP_NO_REMAINDER");
 	e.chunk = number("SA_HIP_CHUNK", 0, 1, 32);
 	e.stagger = number("SA_HIP_STAGGER", 0, 0, 64);
 	e.no_pin = flag("SA_HIP_NO_PIN");

@@ -13,6 +13,7 @@ struct SaEnv {
 	bool no_pk16 = false;       /* SA_HIP_NO_PK16       : no 16-lane packed kernels                                 */
 	bool no_sort = false;       /* SA_HIP_NO_SORT       : row streams in store order (no arranged copies)           */
 	bool no_tokens = false;     /* SA_HIP_NO_TOKENS     : no pre-built token streams: every packed tile derives its tokens   */
+	bool no_remainder = false;  /* SA_HIP_NO_REMAINDER  : no half / quarter tiles: a pair's last rows are one store-order partial tile */
 	/* launch structure */
 	int chunk = 0;               /* SA_HIP_CHUNK=n        : fixed row-stream length (1..32)                         */
 	int stagger = 0;             /* SA_HIP_STAGGER=n      : start delay per wave slot (sleep periods)               */

@@ -81,6 +81,7 @@ struct SaSysArgs {
 	int32_t rotate_prio;        /* packed bundle: rotate the waves' issue priority tile by tile (sa_systolic_pk.inc)     */
 	int32_t stagger;            /* packed bundle: sleep periods (8128 clocks) per wave slot before the first tile      */
 	int32_t stamp_u;            /* diagnostics: launch-tile index of the tile being run (packed bundle)                */
+	int32_t piece;              /* (kernel-internal: SaPkClassArgs::piece of the tile being run; 0: no row window)      */
 	unsigned long long *stamps; /* diagnostics only (SA_HIP_STAMPS=1): per wave-tile {cycles, 100MHz ticks,
 	                             * steps} of the main loop; nullptr in production                        */
 };

@@ -130,6 +130,7 @@ static bool plan_upload(sa_ctx *ctx, sa_ctx::Plan &pl)
 			a.delta = ha.delta;
 			a.pk_base = ha.pk_base;
 			a.chunk = ha.chunk;
+			a.piece = ha.piece;
 		}
 		if (!upload(pl.db[bi].d_args, args) || !upload(pl.db[bi].d_ulist, b.ulist))
 			return false;

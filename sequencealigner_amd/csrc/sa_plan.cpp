@@ -49,8 +49,10 @@ int sa_systolic_class_for(int32_t n)
 SaPkCls sa_pk_decode(int cls)
 {
 	SaPkCls r;
-	r.small = cls >= SA_PK_CLASSES_END;
-	const int c = r.small ? cls - SA_PK_SMALL : cls;
+	const int copy = (cls - SA_PK_CLASS0) / SA_PK_SMALL; /* small + 2 * variant */
+	r.small = copy & 1;
+	r.variant = copy >> 1;
+	const int c = cls - copy * SA_PK_SMALL;
 	r.g = c >= SA_PK16_CLASS0 ? 16 : 8;
 	r.k = c - (r.g == 16 ? SA_PK16_CLASS0 : SA_PK_CLASS0);
 	return r;
@@ -71,7 +73,8 @@ bool sa_arranged_exists(int32_t num, const SaArrKey &key)
 	return key.block > 0 && wave_rows > 0 && key.block % (wave_rows * SA_PK_WPB) == 0 && key.block <= num;
 }
 
-int sa_pk_arranged_keys(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chunk_pk, bool host_out, SaArrKey (&lv)[SA_PK_SORT_LEVELS])
+int sa_pk_arranged_keys(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chunk_pk, bool host_out, SaArrKey (&lv)[SA_PK_SORT_LEVELS],
+			int variant)
 {
 	for (auto &x : lv)
 		x = SaArrKey{};
@@ -80,7 +83,7 @@ int sa_pk_arranged_keys(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chun
 	const int ng = 64 / pk_g;
 	const int32_t rows = sa_pk_wpb(in.method, pk_g, pk_k) * ng * chunk_pk;
 	int nl = 0;
-	for (int l = 0; l < SA_PK_SORT_LEVELS; l++) {
+	for (int l = 0; l < SA_PK_SORT_LEVELS && variant == SA_PK_MAIN; l++) {
 		const int32_t block = SA_PK_SORT_ROWS >> l;
 		/* (a tile of SA_PK_ROWS_OWN_BLOCK rows has enough equal lengths of its own, and storing in row order keeps
 		 * the HBM write traffic at the algorithmic 4 bytes per pair) */
@@ -96,6 +99,20 @@ int sa_pk_arranged_keys(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chun
 			lv[nl++] = key;
 	}
 	return nl;
+}
+
+int sa_pk_piece_avail(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chunk)
+{
+	if (!in.remainder || in.no_sort)
+		return 0;
+	const int ng = 64 / pk_g, wpb = sa_pk_wpb(in.method, pk_g, pk_k);
+	int avail = 0;
+	for (int v = SA_PK_HALF; v <= SA_PK_QUARTER; v++) {
+		const int32_t ch = chunk >> v;
+		if (chunk % (1 << v) == 0 && ch >= 4 && sa_arranged_exists(in.num, SaArrKey{ ng, ch, wpb * ng * ch }))
+			avail |= 1 << (v - 1);
+	}
+	return avail;
 }
 
 /* A workgroup-tile streams SA_PK_WPB waves x ng streams x ch sequences.  What a terminator costs a wave is the event
@@ -372,6 +389,56 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 		cpairs[(size_t)cls] += ib - ia;
 		ccells[(size_t)cls] += (int64_t)n * (lenpre[(size_t)ib] - lenpre[(size_t)ia]);
 	}
+	/* remainder tiles: the variants of a packed class list its columns with every pair's rows clamped to the variant's window
+	 * (sa_shapes.h: sa_pk_piece_window); a variant no pair gives a row does not exist */
+	std::vector<int32_t> piece_of((size_t)SA_PLAN_NCLASSES, 0);
+	for (int cls = SA_PK_CLASS0; cls < SA_PK_CLASS0 + 2 * SA_PK_SMALL; cls++) {
+		if (rows_of[(size_t)cls].empty())
+			continue;
+		const SaPkCls pc = sa_pk_decode(cls);
+		const int32_t chunk = pc.small ? plan.chunk_pk_small : plan.chunk_pk;
+		const int avail = sa_pk_piece_avail(in, pc.g, pc.k, chunk);
+		if (!avail)
+			continue;
+		const int32_t main_rows = sa_pk_wpb(in.method, pc.g, pc.k) * (64 / pc.g) * chunk;
+		const auto rw = rows_of[(size_t)cls]; /* (a copy: the main class's own rows are clamped last) */
+		for (int v = SA_PK_QUARTER; v >= SA_PK_MAIN; v--) {
+			if (v != SA_PK_MAIN && !(avail & (1 << (v - 1))))
+				continue;
+			const size_t vc = (size_t)cls + (size_t)(2 * v) * SA_PK_SMALL;
+			const int piece = v | avail << 2;
+			std::vector<std::pair<int32_t, int32_t>> out(rw.size());
+			int64_t vpairs = 0, vcells = 0;
+			for (size_t c = 0; c < rw.size(); c += 2) {
+				const size_t c1 = c + 1 < rw.size() ? c + 1 : c;
+				int32_t lo, hi;
+				sa_pk_piece_window(std::min(rw[c].first, rw[c1].first), std::max(rw[c].second, rw[c1].second), main_rows, piece, lo, hi);
+				for (size_t h = c; h <= c1; h++) {
+					out[h] = { sa_pk_clamp(rw[h].first, lo, hi), sa_pk_clamp(rw[h].second, lo, hi) };
+					vpairs += out[h].second - out[h].first;
+					vcells += (int64_t)in.meta[jl[(size_t)cls][h]].len * (lenpre[(size_t)out[h].second] - lenpre[(size_t)out[h].first]);
+				}
+			}
+			if (vpairs == 0) {
+				if (v == SA_PK_MAIN) { /* (no pair has a full tile: the class is its variants) */
+					jl[vc].clear();
+					rows_of[vc].clear();
+					cpairs[vc] = ccells[vc] = 0;
+				}
+				continue;
+			}
+			if (v != SA_PK_MAIN)
+				jl[vc] = jl[(size_t)cls];
+			rows_of[vc] = std::move(out);
+			cpairs[vc] = vpairs;
+			ccells[vc] = vcells;
+			piece_of[vc] = piece;
+		}
+	}
+	auto chunk_of = [&](int cls) {
+		const SaPkCls pc = sa_pk_decode(cls);
+		return (pc.small ? plan.chunk_pk_small : plan.chunk_pk) >> pc.variant;
+	};
 	/* packed classes: consecutive columns of a class share a tile (sa_systolic_pk.inc): rows = the union of their row
 	 * ranges, SA_PK_WPB * 64/G streams of `chunk` sequences per workgroup-tile.  The prefix counts the full tiles; the
 	 * partial last tiles follow them in the tile numbering, largest first (their pairs are appended to the prefix). */
@@ -382,7 +449,7 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 		if (rw.empty())
 			continue;
 		const SaPkCls pc = sa_pk_decode(cls);
-		const int64_t rows = (int64_t)sa_pk_wpb(in.method, pc.g, pc.k) * (64 / pc.g) * (pc.small ? plan.chunk_pk_small : plan.chunk_pk);
+		const int64_t rows = (int64_t)sa_pk_wpb(in.method, pc.g, pc.k) * (64 / pc.g) * chunk_of(cls);
 		tp[(size_t)cls].push_back(0);
 		std::vector<std::pair<int32_t, int32_t>> parts; /* (rows, pair) */
 		for (size_t c = 0; c < rw.size(); c += 2) {
@@ -415,7 +482,8 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 		cl.pairs = cpairs[(size_t)cls];
 		cl.cells = ccells[(size_t)cls];
 		cl.part_rows = std::move(part_rows[(size_t)cls]);
-		cl.chunk = cls >= SA_PK_CLASS0 ? (sa_pk_decode(cls).small ? plan.chunk_pk_small : plan.chunk_pk) : 0;
+		cl.chunk = cls >= SA_PK_CLASS0 ? chunk_of(cls) : 0;
+		cl.piece = piece_of[(size_t)cls];
 		if (cls >= SA_PK_CLASS0 && cl.ntiles > (1 << SA_PK_UTILE_BITS)) {
 			sa_set_error("%s", TOO_LARGE);
 			return false;
@@ -459,7 +527,7 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 			std::vector<Geo> tiles((size_t)cl.ntiles);
 			if (is_pk) {
 				SaArrKey lv[SA_PK_SORT_LEVELS];
-				sa_pk_arranged_keys(in, pk_g, K, cl.chunk, share_host, lv);
+				sa_pk_arranged_keys(in, pk_g, K, cl.chunk, share_host, lv, sa_pk_decode(cls).variant);
 				const int32_t lvrows[SA_PK_SORT_LEVELS] = { lv[0].block, lv[1].block, lv[2].block, lv[3].block };
 				const int32_t rows = sa_pk_wpb(in.method, pk_g, K) * (64 / pk_g) * cl.chunk;
 				const auto &rw = rows_of[(size_t)cls];
@@ -594,6 +662,8 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 	/* (the small-tile copies of the classes sort behind all the others: their full tiles end the full tiles) */
 	std::sort(order.begin(), order.end(), [&](int x, int y) { return plan.classes[(size_t)x].cls > plan.classes[(size_t)y].cls; });
 	std::stable_partition(order.begin(), order.end(), [&](int x) { return !sa_pk_decode(plan.classes[(size_t)x].cls).small; });
+	/* (... and the remainder variants behind those: they have no large full tile at all) */
+	std::stable_partition(order.begin(), order.end(), [&](int x) { return sa_pk_decode(plan.classes[(size_t)x].cls).variant == SA_PK_MAIN; });
 	for (int ci : order) {
 		const auto &cl = plan.classes[(size_t)ci];
 		const int g = sa_pk_decode(cl.cls).g;
@@ -618,7 +688,8 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 			const auto &cl = plan.classes[(size_t)b.cls[x]];
 			const int k = sa_pk_decode(cl.cls).k;
 			SaHostPkArgs &a = b.args[x];
-			sa_pk_arranged_keys(in, b.g, k, cl.chunk, share_host, a.lv);
+			sa_pk_arranged_keys(in, b.g, k, cl.chunk, share_host, a.lv, sa_pk_decode(cl.cls).variant);
+			a.piece = cl.piece;
 			a.cls_index = b.cls[x];
 			a.chunk = cl.chunk;
 			a.ncols = cl.ncols;
@@ -648,7 +719,7 @@ bool sa_plan_host(const SaPlanInputs &in, int64_t start, int64_t count, int worl
 				const int32_t nfull = cl.ntiles - cl.npart;
 				const auto &T = cl.tprefix;
 				const int32_t npairs = (cl.ncols + 1) / 2;
-				const bool small = sa_pk_decode(cl.cls).small;
+				const bool small = sa_pk_decode(cl.cls).small || sa_pk_decode(cl.cls).variant != SA_PK_MAIN; /* (half and quarter tiles too) */
 				const int64_t full_rows = (int64_t)sa_pk_wpb(in.method, b.g, sa_pk_decode(cl.cls).k) * (64 / b.g) * cl.chunk;
 				const auto &rw = rows_of[(size_t)cl.cls];
 				const int32_t lvrows[SA_PK_SORT_LEVELS] = { b.args[x].lv[0].block, b.args[x].lv[1].block, b.args[x].lv[2].block,

@@ -64,6 +64,9 @@ struct SaPlanInputs {
 	int env_chunk = 0;
 	bool no_sort = false;
 	bool no_tokens = false;
+	/* remainder tiles (sa_shapes.h: sa_pk_piece_window): cut a column pair's last rows into a half and a quarter tile of
+	 * their own arranged blocks.  false: one store-order partial tile per pair (a context sets it unless SA_HIP_NO_REMAINDER) */
+	bool remainder = false;
 };
 
 /* Which kernel families reproduce the reference exactly for a scoring and a store's length range, and their constants
@@ -86,6 +89,7 @@ int32_t sa_pk_base(const SaPlanInputs &in, int g, int k);
 struct SaPkCls {
 	bool small;
 	int g, k;
+	int variant; /* SA_PK_MAIN, SA_PK_HALF, SA_PK_QUARTER (sa_shapes.h: remainder tiles) */
 };
 SaPkCls sa_pk_decode(int cls);
 /* smallest s32 kernel class whose column budget W = G*K holds a column of length n (SA_SYS_CLASS_LONG beyond) */
@@ -95,7 +99,12 @@ int sa_systolic_class_for(int32_t n);
 bool sa_arranged_exists(int32_t num, const SaArrKey &key);
 /* The arranged copies offered to the tiles of one packed class (largest block first); returns how many, lv[l].block = 0
  * beyond.  host_out: scores (also) leave straight to host memory -- a block is then one tile (row-order epilogue). */
-int sa_pk_arranged_keys(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chunk_pk, bool host_out, SaArrKey (&lv)[SA_PK_SORT_LEVELS]);
+/* variant != SA_PK_MAIN (chunk_pk: the variant's own): a half or quarter tile is always its own block, one key. */
+int sa_pk_arranged_keys(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chunk_pk, bool host_out, SaArrKey (&lv)[SA_PK_SORT_LEVELS],
+			int variant = SA_PK_MAIN);
+/* Which remainder shapes a plan offers the pairs of a main class of `chunk` sequences per stream (bit 0: half tiles, bit 1:
+ * quarter tiles): a shape needs >= 4 sequences per stream, a chunk that divides, and an arranged copy (sa_arranged_exists) */
+int sa_pk_piece_avail(const SaPlanInputs &in, int pk_g, int pk_k, int32_t chunk);
 /* The permutation of one arranged copy: rowmap[position] = row (DESIGN 4.2 "arranged row streams") */
 void sa_arrange_rows(const sa_meta *meta, int32_t num, const SaArrKey &key, std::vector<int32_t> &rowmap);
 
@@ -138,6 +147,7 @@ struct SaHostClass {
 	int32_t ncols = 0, ntiles = 0;
 	int32_t npart = 0; /* packed classes: partial tiles among ntiles (listed behind the tile prefix) */
 	int32_t chunk = 0; /* packed classes: sequences per row stream of a full tile */
+	int32_t piece = 0; /* packed classes: variant | avail << 2 -- the row window of every pair (sa_pk_piece_window); 0: none */
 	int64_t pairs = 0, cells = 0;
 	std::vector<int32_t> jlist, tprefix;
 	std::vector<int32_t> part_rows;  /* packed classes: rows of the partial tiles, in tile order (decreasing)  */
@@ -159,7 +169,7 @@ struct SaHostSeg { /* SaPlaceSeg with the map named instead of pointed to */
 
 struct SaHostPkArgs { /* SaPkClassArgs without the device pointers */
 	int cls_index = 0; /* index into SaHostPlan::classes */
-	int32_t ncols = 0, npart = 0, k = 0, delta = 0, pk_base = 0, chunk = 0;
+	int32_t ncols = 0, npart = 0, k = 0, delta = 0, pk_base = 0, chunk = 0, piece = 0;
 	SaArrKey lv[SA_PK_SORT_LEVELS];
 };
 

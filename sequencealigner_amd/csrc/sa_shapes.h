@@ -98,7 +98,43 @@ enum : int { SA_PK_CLASS0 = SA_SYS_NCLASSES + 1, SA_PK16_CLASS0 = SA_PK_CLASS0 +
 	     /* ... and every packed class once more, + SA_PK_SMALL: the columns of the class that a plan runs in its SMALL tiles (the
 	      * lowest columns of the range, put at the end of the launch so that it tapers off: sa_plan.cpp: sa_plan_host) */
 	     SA_PK_SMALL = SA_PK_CLASSES_END - SA_PK_CLASS0,
-	     SA_PLAN_NCLASSES = SA_PK_CLASSES_END + SA_PK_SMALL };
+	     /* ... and both once per VARIANT (below): class = SA_PK_CLASS0 + c + SA_PK_SMALL * (small + 2 * variant) */
+	     SA_PK_MAIN = 0, SA_PK_HALF = 1, SA_PK_QUARTER = 2, SA_PK_VARIANTS = 3,
+	     SA_PLAN_NCLASSES = SA_PK_CLASS0 + 2 * SA_PK_VARIANTS * SA_PK_SMALL };
+
+/* Remainder tiles.  The rows of a column pair behind its last full tile, r = span mod tile_rows, are cut once more: a HALF tile
+ * (chunk / 2 sequences per stream) where r >= tile_rows / 2, then a QUARTER tile (chunk / 4) where the rest is >= tile_rows / 4;
+ * what is left stays the store-order partial tile.  A half or quarter tile is a full tile of its own shape and its own arranged
+ * block, so it streams arranged rows on the lean way like any full tile.  The pieces are the tiles of VARIANT classes: a
+ * variant lists the columns of its main class -- the same pairs -- with chunk >> variant, and every pair gives each variant a
+ * row window [lo, hi) to which the rows of its two columns are clamped; inside its window a variant is "full tiles of my chunk
+ * plus one partial" like any class.  piece = variant | avail << 2, avail bit 0: the plan offers half tiles, bit 1: quarter
+ * tiles (sa_plan.cpp: sa_pk_piece_avail); piece = 0: one class, no windows.  The last offered variant takes the residual.
+ * ra, rb: row range of the pair before the cut; main_rows: rows of a full tile of the MAIN class.  Planner, share placement
+ * and kernel all ask this function. */
+SA_HD inline void sa_pk_piece_window(int32_t ra, int32_t rb, int32_t main_rows, int piece, int32_t &lo, int32_t &hi)
+{
+	const int variant = piece & 3, avail = piece >> 2;
+	lo = ra, hi = rb;
+	if (!avail)
+		return;
+	if (ra % main_rows != 0) { /* (no arranged copy serves this pair: sa_pk_pick_level) */
+		if (variant != SA_PK_MAIN)
+			hi = lo;
+		return;
+	}
+	const int32_t full_end = ra + (rb - ra) / main_rows * main_rows;
+	const int32_t half_end = full_end + ((avail & 1) && rb - full_end >= main_rows / 2 ? main_rows / 2 : 0);
+	if (variant == SA_PK_MAIN)
+		hi = full_end;
+	else if (variant == SA_PK_HALF) {
+		lo = full_end;
+		if (avail & 2)
+			hi = half_end;
+	} else
+		lo = half_end;
+}
+SA_HD inline int32_t sa_pk_clamp(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 /* The packed kernels are launched as BUNDLES: one persistent kernel (sa_k_systolic_pk_bundle<METHOD, G, KLO, F16>) walks
  * the tiles of up to SA_PK_BUNDLE consecutive K classes -- one launch on the caller's stream, one tail
@@ -139,12 +175,15 @@ struct SaPkClassArgs { /* one class of a bundle launch, in device memory */
 	int32_t ncols, npart, k;
 	int32_t delta, pk_base;
 	int32_t chunk;            /* sequences per row stream of a full tile of this class (SaSysArgs::chunk)  */
+	int32_t piece;            /* remainder tiles: variant | avail << 2 (sa_pk_piece_window); 0: none       */
 	SaArranged lv[SA_PK_SORT_LEVELS]; /* arranged copies of the row store for this tile shape              */
 };
 /* a bundle launch walks ulist[0 .. nlocal): (class of the launch << SA_PK_UTILE_BITS) | tile of the class -- the full
  * tiles class after class (largest K first), then the partial tiles of ALL classes by decreasing size, so that the
- * launch tapers off on its cheapest tiles; share plans: the tiles of one rank in that order */
-#define SA_PK_UTILE_BITS 28
+ * launch tapers off on its cheapest tiles; share plans: the tiles of one rank in that order.  A bundle holds up to
+ * SA_PK_BUNDLE K x {large, small} x SA_PK_VARIANTS = 48 classes: six class bits, 2^26 tiles per class */
+#define SA_PK_UTILE_BITS 26
+static_assert(2 * SA_PK_VARIANTS * SA_PK_BUNDLE <= 1 << (32 - SA_PK_UTILE_BITS), "the classes of a bundle fit the class bits of a tile code");
 /* LDS of a packed workgroup: scores leaving the pipeline, token rings, then the profile of the column pair (the only
  * part that depends on K): a launch asks for the bytes of its largest K as dynamic LDS */
 SA_HD constexpr int sa_pk_lds_fixed(int g, int wpb) { return 416 * wpb * (64 / g); } /* per wave: 64/g groups x (32 scores x 2 halves x 2 B + a 144-entry u16 ring) */

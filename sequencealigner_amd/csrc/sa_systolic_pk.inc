@@ -317,7 +317,15 @@ __device__ __forceinline__ void pk_tile(const SaSysArgs &A, const int32_t t_raw,
 		nh[h] = uload(A.off + j + 1) - offj[h] - 1;
 		pad[h] = W - nh[h]; /* the sequence is right-aligned over the W column slots */
 	}
-	const int32_t ra = ia[0] < ia[1] ? ia[0] : ia[1], rb = ib[0] > ib[1] ? ib[0] : ib[1];
+	int32_t ra = ia[0] < ia[1] ? ia[0] : ia[1], rb = ib[0] > ib[1] ? ib[0] : ib[1];
+	if (A.piece) { /* remainder tiles: this class runs the rows of its window of the pair (sa_shapes.h: sa_pk_piece_window) */
+		sa_pk_piece_window(ra, rb, (NGW * A.chunk) << (A.piece & 3), A.piece, ra, rb);
+#pragma unroll
+		for (int h = 0; h < 2; h++) {
+			ia[h] = sa_pk_clamp(ia[h], ra, rb);
+			ib[h] = sa_pk_clamp(ib[h], ra, rb);
+		}
+	}
 	const int32_t chunk = t < nfull ? t - uload(A.tprefix + lo) : uload(A.tprefix + lo + 1) - uload(A.tprefix + lo);
 	const int32_t ch_full = A.chunk;
 	const int32_t i_begin = ra + chunk * (NGW * ch_full);
@@ -1260,6 +1268,7 @@ __global__ __launch_bounds__(64 * sa_pk_wpb(METHOD, G, KLO)) void sa_k_systolic_
 		A.pk_base = __builtin_amdgcn_readfirstlane(P.pk_base);
 		A.rotate_prio = A0.rotate_prio ? (int32_t)(4u + (wave_slot & 3u)) : 0;
 		A.chunk = __builtin_amdgcn_readfirstlane(P.chunk);
+		A.piece = __builtin_amdgcn_readfirstlane(P.piece);
 		A.lvp = P.lv; /* (the tile reads the one arranged copy it streams from there: 20 fewer live SGPRs) */
 		const int32_t ntiles = __builtin_amdgcn_readfirstlane(A.tprefix[(A.ncols + 1) >> 1]) + A.npart;
 		const unsigned long long st0 = A0.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -1322,7 +1331,7 @@ template <int METHOD> hipError_t launch_pk(int g, int klo, int f16, const SaSysA
 {
 	/* (one translation unit = one code object per method and group width: a store of short sequences never loads the
 	 * 16-lane kernels, two thirds of the packed code) */
-	if (g != SA_PK_G || !a.pkc || a.npkc < 1 || a.npkc > 2 * SA_PK_BUNDLE) /* (every class once per tile size) */
+	if (g != SA_PK_G || !a.pkc || a.npkc < 1 || a.npkc > 2 * SA_PK_VARIANTS * SA_PK_BUNDLE) /* (every class once per tile size and variant) */
 		return hipErrorInvalidValue;
 #if SA_PK_G == 8
 	if (!f16)
