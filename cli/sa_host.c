@@ -926,6 +926,97 @@ int sa_host_write_search_values(const char *path, const struct sa_host_store *db
 	return rc ? rc : write_side_sets(path, NULL, 0, false, sets, 6);
 }
 
+/* --query --hits-min (include/seqalign_hip.h: sa_hip_search_above): a file of its own with /sequences (the database),
+ * /query_sequences, the hits of every query as CSR -- /hitlist_offsets (M + 1 I64LE), /hitlist_indices and /hitlist_scores
+ * (E = offsets[M] I32LE each, extent 0 when there is no hit) -- and /hitlist_min (the threshold).  Under a quantity (kind 1 or 2,
+ * numbered as sa_host_write_search_values numbers them; 0: raw scores) also /hitlist_values (E), /hit_quantity, /hit_scale and for a
+ * normalised kind /database_denominators and /query_denominators; with `alignments` /hitlist_alignment_records (E x 8),
+ * /hitlist_cigar_offsets (E + 1 I64LE) and /hitlist_cigars (U32LE) in the format of the neighbour datasets; with `rect` /query_scores
+ * and with `vrect` /query_values (M x N); no /similarity_matrix.  Checked before anything is opened: offsets[0] == 0, offsets
+ * non-decreasing, every index in [0, N), every row in ascending index.  A failed file is removed. */
+int sa_host_write_search_list(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, const int64_t *offsets,
+			      const int32_t *index, const int32_t *score, int32_t min_value, const int32_t *value, int32_t kind, int32_t source,
+			      int32_t rule_or_denom, const int32_t *denominators, const int32_t *rect, const int32_t *vrect, int alignments,
+			      const struct sa_aln *records, const uint32_t *cigar, int64_t runs)
+{
+	if (!path || !db || !queries || !offsets)
+		return fail("Hit list data missing");
+	const size_t n = (size_t)db->in.num, m = (size_t)queries->in.num;
+	if (db->in.num < 1 || queries->in.num < 1)
+		return fail("A search needs a database and queries");
+	if (kind < 0 || kind > 2)
+		return fail("Hit quantity kind %d is none of raw score (0), normalised score (1), percent identity (2)", kind);
+	if (kind == 1 && source != SA_NORM_SELF && source != SA_NORM_LENGTH)
+		return fail("Normalization source %d is neither self-score (%d) nor length (%d)", source, (int)SA_NORM_SELF, (int)SA_NORM_LENGTH);
+	if (kind == 1 && rule_or_denom != SA_NORM_MIN && rule_or_denom != SA_NORM_MAX && rule_or_denom != SA_NORM_MEAN)
+		return fail("Normalization rule %d is none of min (%d), max (%d), mean (%d)", rule_or_denom, (int)SA_NORM_MIN, (int)SA_NORM_MAX,
+			    (int)SA_NORM_MEAN);
+	if (kind == 2 && rule_or_denom != SA_PID_COLUMNS && rule_or_denom != SA_PID_SHORTER && rule_or_denom != SA_PID_LONGER && rule_or_denom != SA_PID_MEAN)
+		return fail("Identity denominator %d is none of columns (%d), shorter (%d), longer (%d), mean (%d)", rule_or_denom, (int)SA_PID_COLUMNS,
+			    (int)SA_PID_SHORTER, (int)SA_PID_LONGER, (int)SA_PID_MEAN);
+	if (offsets[0] != 0)
+		return fail("Hit list offsets must start at 0");
+	for (size_t q = 0; q < m; q++)
+		if (offsets[q + 1] < offsets[q])
+			return fail("Hit list offsets decrease at query %zu", q);
+	const int64_t count = offsets[m];
+	if ((count > 0 && (!index || !score || (kind && !value) || (alignments && !records))) || (kind == 1 && !denominators) ||
+	    (alignments && (runs < 0 || (runs > 0 && !cigar))))
+		return fail("Hit list data missing");
+	for (size_t q = 0; q < m; q++)
+		for (int64_t t = offsets[q]; t < offsets[q + 1]; t++) {
+			if (index[t] < 0 || (size_t)index[t] >= n)
+				return fail("Hit index %d of query %zu outside the %zu database sequences", index[t], q, n);
+			if (t > offsets[q] && index[t] <= index[t - 1])
+				return fail("Hit indices of query %zu are not in ascending order", q);
+		}
+	const size_t e = (size_t)count;
+	int32_t *fields = NULL;
+	int64_t *offs = NULL;
+	if (alignments) {
+		fields = malloc(sizeof(int32_t) * 8 * (e ? e : 1));
+		offs = malloc(sizeof(int64_t) * (e + 1));
+		if (!fields || !offs) {
+			free(fields);
+			free(offs);
+			return fail("Out of memory allocating alignment records");
+		}
+		for (size_t t = 0; t < e; t++) {
+			const struct sa_aln *r = records + t;
+			const int32_t f[8] = { r->score, r->a_begin, r->a_end, r->b_begin, r->b_end, r->columns, r->identities, r->cigar_len };
+			memcpy(fields + 8 * t, f, sizeof(f));
+			offs[t] = r->cigar_off;
+		}
+		offs[e] = runs;
+	}
+	const int32_t what[3] = { kind, kind == 1 ? source : 0, rule_or_denom }, scale = SA_NORM_SCALE;
+	const struct side_set sets[14] = { { "/hitlist_offsets", 1, { (hsize_t)m + 1 }, SIDE_I64, offsets, false },
+					   { "/hitlist_indices", 1, { (hsize_t)e }, SIDE_I32, index, false },
+					   { "/hitlist_scores", 1, { (hsize_t)e }, SIDE_I32, score, false },
+					   { "/hitlist_min", 1, { 1 }, SIDE_I32, &min_value, false },
+					   { "/hitlist_values", 1, { (hsize_t)e }, SIDE_I32, kind ? value : NULL, !kind },
+					   { "/hit_quantity", 1, { 3 }, SIDE_I32, kind ? what : NULL, true },
+					   { "/hit_scale", 1, { 1 }, SIDE_I32, kind ? &scale : NULL, true },
+					   { "/database_denominators", 1, { n }, SIDE_I32, kind == 1 ? denominators : NULL, true },
+					   { "/query_denominators", 1, { m }, SIDE_I32, kind == 1 ? denominators + n : NULL, true },
+					   { "/hitlist_alignment_records", 2, { (hsize_t)e, 8 }, SIDE_I32, fields, true },
+					   { "/hitlist_cigar_offsets", 1, { (hsize_t)e + 1 }, SIDE_I64, offs, true },
+					   { "/hitlist_cigars", 1, { (hsize_t)(alignments ? runs : 0) }, H5T_STD_U32LE, H5T_NATIVE_UINT32, cigar, !alignments },
+					   { "/query_scores", 2, { m, n }, SIDE_I32, rect, true },
+					   { "/query_values", 2, { m, n }, SIDE_I32, kind ? vrect : NULL, true } };
+	hid_t file;
+	int rc = create_with_sequences(path, db, &file);
+	if (!rc) {
+		rc = write_sequences(file, "/query_sequences", queries) || add_side_sets(file, sets, 14);
+		H5Fclose(file);
+		if (rc)
+			remove(path);
+	}
+	free(fields);
+	free(offs);
+	return rc;
+}
+
 /* The score graph as CSR (include/seqalign_hip.h: sa_hip_edges): /edge_offsets N + 1 I64LE, /edge_indices and /edge_scores
  * E = offsets[N] I32LE each (extent 0 when there is no edge).  create: as write_side_sets has it.  The arrays are checked before
  * anything is opened: offsets[0] == 0, offsets non-decreasing, every index in [0, N). */

@@ -102,6 +102,20 @@ int sa_host_write_search(const char *path, const struct sa_host_store *db, const
 int sa_host_write_search_values(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
 				const int32_t *value, int32_t kind, int32_t source, int32_t rule_or_denom, const int32_t *denominators,
 				const int32_t *vrect);
+/* --query --hits-min: the one writer of a threshold search.  A NEW file at `path` with /sequences (N), /query_sequences (M), the hits
+ * of every query as the CSR of sa_hip_search_above -- /hitlist_offsets (M + 1 I64LE), /hitlist_indices and /hitlist_scores (E =
+ * offsets[M] I32LE each; extent 0 when E = 0; row q's indices ascending, the scores raw) -- and /hitlist_min (1 I32LE: the
+ * threshold).  kind 0: raw scores, `value`, `source`, `rule_or_denom`, `denominators` and `vrect` are not looked at; kind 1 / 2, numbered
+ * and checked as sa_host_write_search_values has them: also /hitlist_values (E I32LE, parts per million), /hit_quantity, /hit_scale and,
+ * kind 1, /database_denominators (N) and /query_denominators (M) from `denominators` (N + M), with `vrect` (or NULL) /query_values
+ * (M x N).  With `rect` (or NULL) /query_scores (M x N).  With `alignments` != 0 also /hitlist_alignment_records (E x 8),
+ * /hitlist_cigar_offsets (E + 1 I64LE) and /hitlist_cigars (`runs` U32LE) in the format of the neighbour datasets (a = the query, b =
+ * its hit); `records` may be NULL when E = 0.  No /similarity_matrix.  offsets[0] != 0, decreasing offsets, an index outside [0, N)
+ * or a row not in ascending index give an error before anything is opened; a file that fails later is removed. */
+int sa_host_write_search_list(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, const int64_t *offsets,
+			      const int32_t *index, const int32_t *score, int32_t min_value, const int32_t *value, int32_t kind, int32_t source,
+			      int32_t rule_or_denom, const int32_t *denominators, const int32_t *rect, const int32_t *vrect, int alignments,
+			      const struct sa_aln *records, const uint32_t *cigar, int64_t runs);
 /* --min-score: /edge_offsets (N + 1 I64LE), /edge_indices and /edge_scores (E = offsets[N] I32LE each; extent 0 when E = 0),
  * the CSR arrays of sa_hip_edges / sa_zjob_edges.  `create` as in sa_host_write_neighbors: 0 adds the three datasets to the
  * finished file at `path`, 1 writes a new file with /sequences and the three (--edges-only).  offsets[0] != 0, decreasing

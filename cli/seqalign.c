@@ -34,6 +34,9 @@
  *             --hits-by QUANTITY  (with --query: the hits ranked by a normalised score or by percent identity instead of the raw score:
  *             /hit_values beside /hit_indices, /hit_scores the raw score of each hit, /hit_quantity, /hit_scale, the denominators,
  *             with --query-scores /query_values)
+ *             --hits-min T  (with --query, in place of -k: every hit whose value is at least T, as CSR: /hitlist_offsets,
+ *             /hitlist_indices, /hitlist_scores, /hitlist_min, under --hits-by /hitlist_values, with --alignments
+ *             /hitlist_alignment_records, /hitlist_cigar_offsets and /hitlist_cigars)
  * Flow (main, one function per phase): options -> banner -> load + filter -> output plan -> the first pass (tile job | one selection only |
  * host matrix | the search) -> per selection, in the order of the file: its second pass where the first left it unanswered, then its
  * datasets (a search: its alignments, then its one file) -> -B report.
@@ -149,6 +152,9 @@ struct options {
 	bool hits_by;
 	int32_t hits_kind, hits_source, hits_rule, hits_denom;
 	const char *hits_name;
+	/* --hits-min T: with --query, in place of -k: every hit whose value (the quantity of --hits-by, or the raw score) is at least T */
+	bool has_hits_min;
+	int32_t hits_min;
 };
 
 static void usage(const char *argv0)
@@ -238,7 +244,8 @@ static void usage(const char *argv0)
 	       "                           with --normalize.  Writes /identity_rule (0 = columns, 1 = shorter, 2 = longer,\n"
 	       "                           3 = mean) and /identity_scale (1000000)\n"
 	       "      --query FILE         A search: the M sequences of FILE (same formats, same residue checks) as queries against the\n"
-	       "                           N of the input as the database.  Needs -k K, 1 <= K <= min(N, 64).  Only the M x N\n"
+	       "                           N of the input as the database.  Needs -k K, 1 <= K <= min(N, 64) (or --hits-min T\n"
+	       "                           instead: every hit at or above a threshold, see there).  Only the M x N\n"
 	       "                           query-database pairs are aligned: no all-vs-all, no /similarity_matrix.  Writes\n"
 	       "                           /query_sequences (M) beside /sequences, /hit_indices and /hit_scores (M x K: the K best\n"
 	       "                           database sequences of every query, score descending, index ascending; indices into\n"
@@ -260,6 +267,17 @@ static void usage(const char *argv0)
 	       "                           the normalised kinds /database_denominators (N) and /query_denominators (M), and with\n"
 	       "                           --query-scores /query_values (M x N) beside /query_scores, which stays raw.  --alignments\n"
 	       "                           is unchanged (a = the query, b = its hit)\n"
+	       "      --hits-min T         With --query, in place of -k (exactly one of the two is given): every database sequence\n"
+	       "                           whose value against a query is at least T (any 32-bit integer), however many there are.\n"
+	       "                           T is in the unit of --hits-by: the raw score without it, parts per million with it\n"
+	       "                           (--hits-by identity-shorter --hits-min 900000: at least 90 %% identity).  Writes the\n"
+	       "                           hits as CSR: /hitlist_offsets (M + 1, 64-bit), /hitlist_indices and /hitlist_scores (E,\n"
+	       "                           the hits of query q at offsets[q] .. offsets[q + 1], index ASCENDING, not ranked: ranking\n"
+	       "                           is what -k is for; the scores raw), /hitlist_min (T), under a quantity /hitlist_values\n"
+	       "                           (E) with /hit_quantity, /hit_scale and the denominators as --hits-by writes them; with\n"
+	       "                           --alignments /hitlist_alignment_records (E x 8), /hitlist_cigar_offsets (E + 1) and\n"
+	       "                           /hitlist_cigars; with --query-scores /query_scores and, under a quantity, /query_values,\n"
+	       "                           which cost a second alignment of the rectangle (the hit list does not keep it)\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -322,6 +340,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
 		     { "quantiles", 12, true }, { "normalize", 13, true }, { "identity", 14, true },
 		     { "linkage-method", 15, true }, { "query", 16, true }, { "query-scores", 17, false }, { "hits-by", 18, true },
+		     { "hits-min", 19, true },
 	     { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
@@ -533,6 +552,14 @@ static int parse_args(int argc, char **argv, struct options *o)
 				}
 				break;
 			}
+			case 19:
+				if (!parse_long(val, INT32_MIN, INT32_MAX, &v)) {
+					err("Hit threshold must be an integer between %d and %d", INT32_MIN, INT32_MAX);
+					return 1;
+				}
+				o->has_hits_min = true;
+				o->hits_min = (int32_t)v;
+				break;
 			case 16: o->query = val; break;
 			case 17: o->query_scores = true; break;
 			case 18: {
@@ -674,6 +701,8 @@ struct run {
 	/* --query: the queries, the hits (M x K), with --query-scores the rectangle (M x N), with --alignments the M x K records */
 	struct sa_host_store queries;
 	struct { int32_t *index, *score, *rect, *value, *vrect; sa_alns *alns; double hits_seconds, gather_seconds; int32_t batches; } sr;
+	/* --query --hits-min: the hits of every query as CSR (E of them), in arrays the library owns */
+	struct { sa_hitlist *list; long long count; double rect_seconds; } ab;
 	struct { double seconds; long long runs; } trace;
 	struct { /* the fractions' ranks: one select call answers all of them, where the matrix is */
 		int64_t ranks[SA_HIP_SELECT_MAX], below[SA_HIP_SELECT_MAX];
@@ -834,14 +863,19 @@ static int set_up(int argc, char **argv, struct run *r)
 		ok = (err("Option --query-scores requires --query"), false);
 	if (ok && o->hits_by && !o->query)
 		ok = (err("Option --hits-by requires --query: it ranks the hits of a search"), false);
-	if (ok && o->query && !o->neighbors)
-		ok = (err("Option --query requires -k, --neighbors: the number of hits per query"), false);
+	if (ok && o->has_hits_min && !o->query)
+		ok = (err("Option --hits-min requires --query: it is the threshold of the hits of a search"), false);
+	if (ok && o->has_hits_min && o->neighbors)
+		ok = (err("Options --hits-min and -k, --neighbors conflict: a search writes the K best hits of every query or every hit at or "
+			  "above T, not both"), false);
+	if (ok && o->query && !o->neighbors && !o->has_hits_min)
+		ok = (err("Option --query requires -k, --neighbors (the number of hits per query) or --hits-min (the threshold of the hits)"), false);
 	if (ok && o->query && query_conflict(o))
 		ok = (err("Options --query and %s conflict: a search writes the hits of the queries and nothing selected from an all-vs-all matrix, "
 			  "which it never computes", query_conflict(o)), false);
 	if (ok && o->neighbors_only && !o->neighbors)
 		ok = (err("Option --neighbors-only requires -k, --neighbors"), false);
-	if (ok && o->alignments && !o->neighbors)
+	if (ok && o->alignments && !o->neighbors && !(o->query && o->has_hits_min))
 		ok = (err("Option --alignments requires -k, --neighbors"), false);
 	if (ok && o->has_min_score && o->min_q >= 0)
 		ok = (err("Options --min-score and --min-quantile conflict: one threshold for the score graph"), false);
@@ -931,7 +965,13 @@ static void banner(const struct run *r)
 		info("Gap open: %d, extend: %d", r->sc.gap_opn, r->sc.gap_ext);
 	if (o->filter > 0.0f)
 		info("Filter threshold: %.1f%%", (double)o->filter * 100.0);
-	if (o->query) {
+	if (o->query && o->has_hits_min) {
+		if (o->hits_by && o->hits_kind)
+			info("Queries: %s, every database sequence whose %s is at least %d parts per million (no similarity matrix)", o->query,
+			     o->hits_name, o->hits_min);
+		else
+			info("Queries: %s, every database sequence that scores at least %d (no similarity matrix)", o->query, o->hits_min);
+	} else if (o->query) {
 		info("Queries: %s, the %d best database sequences of each (no similarity matrix)", o->query, o->neighbors);
 		if (o->hits_by && o->hits_kind)
 			info("Hits ranked by %s, in parts per million (the hit scores stay raw)", o->hits_name);
@@ -979,16 +1019,20 @@ static bool load_queries(struct run *r)
 		return false;
 	}
 	r->npairs = (long long)m * (long long)r->n;
-	r->sr.index = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
-	r->sr.score = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+	/* (--hits-min: the hits come back in arrays the library owns) */
+	if (!o->has_hits_min) {
+		r->sr.index = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+		r->sr.score = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+	}
 	if (o->query_scores)
 		r->sr.rect = malloc(sizeof(int32_t) * m * r->n);
-	if (!r->sr.index || !r->sr.score || (o->query_scores && !r->sr.rect))
+	if ((!o->has_hits_min && (!r->sr.index || !r->sr.score)) || (o->query_scores && !r->sr.rect))
 		return failed("Out of memory allocating search results");
 	/* --hits-by: the quantity of the search, carried as the quantity of every selection is (kind 0: the scores, q stays empty) */
 	if (o->hits_by && o->hits_kind) {
 		r->norm_spec = (struct sa_norm){ o->hits_source, o->hits_rule, NULL };
-		r->sr.value = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+		if (!o->has_hits_min)
+			r->sr.value = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
 		if (o->query_scores)
 			r->sr.vrect = malloc(sizeof(int32_t) * m * r->n);
 		if (o->hits_kind == 1) {
@@ -996,7 +1040,7 @@ static bool load_queries(struct run *r)
 			r->q.norm = &r->norm_spec;
 		} else
 			r->q.pid = &o->hits_denom;
-		if (!r->sr.value || (o->query_scores && !r->sr.vrect) || (r->q.norm && !r->norm_spec.denominators))
+		if ((!o->has_hits_min && !r->sr.value) || (o->query_scores && !r->sr.vrect) || (r->q.norm && !r->norm_spec.denominators))
 			return failed("Out of memory allocating search results");
 	}
 	return true;
@@ -1231,10 +1275,21 @@ static bool run_only(struct run *r)
 static bool run_search(struct run *r)
 {
 	const struct options *o = &r->o;
-	info("Search: %d queries against %zu database sequences, %d hits per query selected on the device", r->queries.in.num, r->n, o->neighbors);
+	if (o->has_hits_min)
+		info("Search: %d queries against %zu database sequences, the hits at or above %d selected on the device", r->queries.in.num, r->n,
+		     o->hits_min);
+	else
+		info("Search: %d queries against %zu database sequences, %d hits per query selected on the device", r->queries.in.num, r->n, o->neighbors);
 	const double t0 = now();
-	/* (the *_norm call with norm == NULL is sa_hip_search itself) */
-	if (!(r->q.pid ? sa_hip_search_pid(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->sr.rect,
+	/* the one call that fits (the *_norm call with norm == NULL is sa_hip_search itself) */
+	if (o->has_hits_min) {
+		r->ab.list = sa_hip_search_above(r->store.in, r->queries.in, &r->sc, o->hits_min, r->q.norm, r->q.pid);
+		if (!r->ab.list)
+			return failed(sa_last_error());
+		int64_t count = 0;
+		(void)sa_hitlist_index(r->ab.list, &count);
+		r->ab.count = (long long)count;
+	} else if (!(r->q.pid ? sa_hip_search_pid(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->sr.rect,
 					   r->sr.vrect, *r->q.pid)
 		       : sa_hip_search_norm(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->sr.rect,
 					    r->sr.vrect, r->q.norm)))
@@ -1246,6 +1301,15 @@ static bool run_search(struct run *r)
 	sa_hip_last_search_breakdown(&r->t_align, &r->sr.gather_seconds, &r->sr.hits_seconds, &r->sr.batches);
 	const double device = sa_hip_last_search_seconds() + (r->q.norm ? r->t_quantity : 0.0);
 	r->t_setup = call > device ? call - device : 0.0;
+	if (o->has_hits_min && o->query_scores) {
+		/* the rectangles do not come back with the hit list: a second alignment, index NULL, delivers them */
+		const double t1 = now();
+		if (!(r->q.pid ? sa_hip_search_pid(r->store.in, r->queries.in, &r->sc, 0, NULL, NULL, NULL, r->sr.rect, r->sr.vrect, *r->q.pid)
+			       : sa_hip_search_norm(r->store.in, r->queries.in, &r->sc, 0, NULL, NULL, NULL, r->sr.rect, r->sr.vrect, r->q.norm)))
+			return failed(sa_last_error());
+		r->ab.rect_seconds = now() - t1;
+		stamp("sa_hip_search (rectangles) returned");
+	}
 	return true;
 }
 
@@ -1256,14 +1320,23 @@ static bool trace_hits(struct run *r)
 	const struct options *o = &r->o;
 	if (!o->alignments)
 		return true;
-	const size_t np = (size_t)r->queries.in.num * (size_t)o->neighbors;
+	const int64_t *offsets = o->has_hits_min ? sa_hitlist_offsets(r->ab.list, NULL) : NULL;
+	const int32_t *index = o->has_hits_min ? sa_hitlist_index(r->ab.list, NULL) : r->sr.index;
+	const size_t np = o->has_hits_min ? (size_t)r->ab.count : (size_t)r->queries.in.num * (size_t)o->neighbors;
+	if (np == 0) /* (--hits-min above every value: no pair to trace, the datasets are written with extent 0) */
+		return true;
 	int32_t *pa = malloc(sizeof(int32_t) * np);
 	if (!pa)
 		return failed("Out of memory allocating alignment pairs");
-	for (size_t t = 0; t < np; t++)
-		pa[t] = (int32_t)(r->n + t / (size_t)o->neighbors);
+	if (o->has_hits_min) { /* the E pairs (query q, its hits) in the order of the hit list */
+		for (int32_t q = 0; q < r->queries.in.num; q++)
+			for (int64_t t = offsets[q]; t < offsets[q + 1]; t++)
+				pa[t] = (int32_t)r->n + q;
+	} else
+		for (size_t t = 0; t < np; t++)
+			pa[t] = (int32_t)(r->n + t / (size_t)o->neighbors);
 	sa_ctx *ctx = sa_ctx_create_search(0, r->store.in, r->queries.in, &r->sc);
-	r->sr.alns = ctx ? sa_ctx_alignments(ctx, pa, r->sr.index, (int64_t)np) : NULL;
+	r->sr.alns = ctx ? sa_ctx_alignments(ctx, pa, index, (int64_t)np) : NULL;
 	free(pa);
 	if (ctx)
 		sa_ctx_destroy(ctx);
@@ -1281,6 +1354,13 @@ static bool write_search(struct run *r)
 	int64_t runs = 0;
 	const uint32_t *cigar = r->sr.alns ? sa_alns_cigar(r->sr.alns, &runs) : NULL;
 	r->trace.runs = (long long)runs;
+	if (o->has_hits_min)
+		return WRITE_OUT(r, sa_host_write_search_list(o->output, &r->store, &r->queries, sa_hitlist_offsets(r->ab.list, NULL),
+							      sa_hitlist_index(r->ab.list, NULL), sa_hitlist_score(r->ab.list), o->hits_min,
+							      sa_hitlist_value(r->ab.list), r->q.norm ? 1 : r->q.pid ? 2 : 0, r->q.norm ? r->q.norm->source : 0,
+							      r->q.norm ? r->q.norm->rule : r->q.pid ? *r->q.pid : 0, r->q.norm ? r->q.norm->denominators : NULL,
+							      r->sr.rect, r->sr.vrect, o->alignments, r->sr.alns ? sa_alns_records(r->sr.alns) : NULL, cigar,
+							      runs), "hit list written");
 	if (!WRITE_OUT(r, sa_host_write_search(o->output, &r->store, &r->queries, o->neighbors, r->sr.index, r->sr.score, r->sr.rect,
 					       r->sr.alns ? sa_alns_records(r->sr.alns) : NULL, cigar, runs), "search written"))
 		return false;
@@ -1491,8 +1571,14 @@ static void report(const struct run *r)
 			       : r->schedule == 2 ? "tiles dealt over the devices, RCCL all-gather of the dense shares, placement on every device"
 						  : "every device delivers its slice of the packed index straight into the host matrix");
 	if (o->query) {
-		printf("  (hit selection on the device, K = %d: %.6f sec; rows gathered in %.6f sec; %d batches of queries)\n", o->neighbors,
-		       r->sr.hits_seconds, r->sr.gather_seconds, r->sr.batches);
+		if (o->has_hits_min) {
+			printf("  (hits at or above %d on the device: %lld hits, count + scan + fill %.6f sec; rows gathered in %.6f sec; %d batches of queries)\n",
+			       o->hits_min, r->ab.count, r->sr.hits_seconds, r->sr.gather_seconds, r->sr.batches);
+			if (o->query_scores)
+				printf("  (--query-scores: a second alignment of the rectangle delivered it, %.3f sec, outside the phases)\n", r->ab.rect_seconds);
+		} else
+			printf("  (hit selection on the device, K = %d: %.6f sec; rows gathered in %.6f sec; %d batches of queries)\n", o->neighbors,
+			       r->sr.hits_seconds, r->sr.gather_seconds, r->sr.batches);
 		if (r->q.norm)
 			printf("  (hits by %s on the device: denominators + sweep over %lld pairs, %.6f sec)\n", o->hits_name, r->npairs, r->t_quantity);
 		if (r->q.pid)
@@ -1500,7 +1586,7 @@ static void report(const struct run *r)
 			       r->npairs, r->t_quantity);
 		if (o->alignments)
 			printf("  (alignments of the %lld hit pairs on the device, fill + walk: %.6f sec, %lld CIGAR runs)\n",
-			       (long long)r->queries.in.num * o->neighbors, r->trace.seconds, r->trace.runs);
+			       o->has_hits_min ? r->ab.count : (long long)r->queries.in.num * o->neighbors, r->trace.seconds, r->trace.runs);
 	} else if (o->neighbors)
 		printf("  (neighbor selection on the device, K = %d: %.6f sec%s)\n", o->neighbors, r->nb.seconds, r->nb.second_pass ? AGAIN : "");
 	if (o->alignments && !o->query)
@@ -1537,6 +1623,7 @@ static void release(struct run *r)
 	free(r->norm_spec.denominators);
 	if (r->sr.alns)
 		sa_alns_destroy(r->sr.alns);
+	sa_hitlist_destroy(r->ab.list);
 	free(r->sr.index);
 	free(r->sr.score);
 	free(r->sr.rect);

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls, then the *_search* / *_hits calls, then the *_rect / _hits_take / sa_hip_search_norm / _pid calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls, then the *_search* / *_hits calls, then the *_rect / _hits_take / sa_hip_search_norm / _pid calls, then the *_hits_above_* / sa_hip_search_above / sa_hitlist_* calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -380,6 +380,57 @@ bool sa_hip_search_norm(struct sa_input db, struct sa_input queries, const struc
 bool sa_hip_search_pid(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *value,
 		       int32_t *score, int32_t *rect, int32_t *vrect, int32_t denom);
 double sa_hip_last_search_quantity_seconds(void);
+
+/* ---- search: every hit at or above a threshold, as a CSR over the rows of the rectangle -----------------------------------------
+ * No reference counterpart.  The k best hits answer "who is closest"; "which database sequences are at least 90 % identical to
+ * my query" has no fixed length per query and no bound of 64.  Let vrect be a device rectangle of pitch N whose values are raw
+ * scores, normalised scores or percent identity in parts per million, and min_value any int32.  Database sequence d is a hit of
+ * row r iff vrect[r * N + d] >= min_value.  The result is a CSR over the rows:
+ *   offsets  int64[nq + 1], offsets[0] = 0, offsets[r + 1] - offsets[r] = hits of row r, offsets[nq] = E
+ *   index    int32[E], row r's hits in ASCENDING d (ranking best-first is what the k best hits are for)
+ *   value    int32[E], vrect at each hit
+ *   score    int32[E], the raw-score rectangle rect at each hit
+ * INT32_MIN gives E = nq * N; a threshold above the maximum gives a valid empty result (all offsets 0).  No position depends on
+ * which wave arrives first: the same inputs give the same bytes.  Offsets, and everything computed from them, are 64-bit.
+ *
+ * Both device-resident calls are asynchronous on `stream`, allocate nothing and do not synchronise with the host; both leave
+ * their input rectangles unchanged.  Refused before any launch: a context of sa_ctx_create, a null required pointer, nq outside
+ * [1, M], a scratch that is not 8-byte aligned.
+ * sa_hits_above_scratch_bytes   host only: bytes of d_scratch for rows [0, nq) of a rectangle of pitch n_db -- 8 * (nq * S + 1),
+ *          S the segments a row is cut into, a function of (n_db, nq) alone.  0 for n_db < 1 or nq < 1.
+ * sa_ctx_hits_above_offsets   count + scan: d_offsets (nq + 1 int64 of device memory) for rows [0, nq) of d_vrect.  d_scratch
+ *          receives the place of every segment's first hit and belongs to the fill that follows.
+ * sa_ctx_hits_above_fill   d_index (required), d_value, d_score (each may be NULL): E int32 each, E = d_offsets[nq], which the
+ *          caller has read to size them.  d_offsets and d_scratch as _offsets left them for the SAME d_vrect, nq and min_value.
+ *          d_rect is read iff d_score is not NULL, at the hits only, and may equal d_vrect.  A row never writes at or beyond
+ *          d_offsets[r + 1], whatever the caller handed in.
+ * sa_hip_search_above   one call, host in / host out, first device.  norm and pid_denom both NULL: raw scores, value == score;
+ *          norm: normalised scores (norm->denominators, when not NULL, receives N + M values); pid_denom: percent identity under
+ *          *pid_denom; both given: refused.  Every argument is checked before a device is looked for.  The queries go in batches
+ *          sized as sa_hip_search_norm / _pid size them, with the scratch of this call in place of the hit lists -- per query
+ *          4 (N + M) bytes (not under percent identity) + 4 N (raw scores) or 8 N + 8 -- and SA_HIP_SEARCH_BATCH_BYTES caps a
+ *          batch.  Stream order per batch: range, rows to pitch N, the quantity's sweep (or the identity sweep alone), count +
+ *          scan, the host reads E of the batch, an exact device buffer for its hits (the largest so far is kept), fill, copy into
+ *          host arrays that grow.  A batch whose hits do not fit the device or the host gives NULL + sa_last_error naming the
+ *          queries, E and the bytes; the process goes on working.  The result owns its arrays until sa_hitlist_destroy.
+ * sa_hip_last_search_above_seconds   device time of count + scan + fill, summed over the batches of the last successful
+ *          sa_hip_search_above.  sa_hip_last_search_seconds / _breakdown / _quantity_seconds answer as after sa_hip_search_norm /
+ *          _pid; the `hits` part of the breakdown is this call's count + scan + fill.
+ * Non-zero / NULL + sa_last_error on failure. */
+size_t sa_hits_above_scratch_bytes(int32_t n_db, int32_t nq);
+int sa_ctx_hits_above_offsets(sa_ctx *ctx, const int32_t *d_vrect, int32_t nq, int32_t min_value, int64_t *d_offsets, void *d_scratch,
+			      void *stream);
+int sa_ctx_hits_above_fill(sa_ctx *ctx, const int32_t *d_vrect, const int32_t *d_rect, int32_t nq, int32_t min_value, const int64_t *d_offsets,
+			   const void *d_scratch, int32_t *d_index, int32_t *d_value, int32_t *d_score, void *stream);
+typedef struct sa_hitlist sa_hitlist; /* owns offsets / index / value / score in host memory, like sa_edges */
+sa_hitlist *sa_hip_search_above(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t min_value,
+				const struct sa_norm *norm, const int32_t *pid_denom);
+const int64_t *sa_hitlist_offsets(const sa_hitlist *h, int32_t *queries); /* M + 1 entries; *queries (may be NULL) = M */
+const int32_t *sa_hitlist_index(const sa_hitlist *h, int64_t *count);     /* *count (may be NULL) = E; never NULL for a valid result */
+const int32_t *sa_hitlist_value(const sa_hitlist *h);
+const int32_t *sa_hitlist_score(const sa_hitlist *h);
+void sa_hitlist_destroy(sa_hitlist *h);
+double sa_hip_last_search_above_seconds(void);
 
 /* ---- alignments for chosen pairs: traceback on the device, run-length CIGARs ----------------------------------------
  * No reference counterpart: the reference keeps scores only.  For an explicit list of pairs (a[t], b[t]) of one store,

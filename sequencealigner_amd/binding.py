@@ -74,6 +74,8 @@ ABI_SYMBOLS = (
     "sa_hits_scratch_bytes", "sa_ctx_hits", "sa_hip_search", "sa_hip_last_search_seconds", "sa_hip_last_search_breakdown",
     "sa_ctx_normalize_rect", "sa_ctx_identity_rect", "sa_ctx_hits_take", "sa_hip_search_norm", "sa_hip_search_pid",
     "sa_hip_last_search_quantity_seconds",
+    "sa_hits_above_scratch_bytes", "sa_ctx_hits_above_offsets", "sa_ctx_hits_above_fill", "sa_hip_search_above", "sa_hitlist_offsets",
+    "sa_hitlist_index", "sa_hitlist_value", "sa_hitlist_score", "sa_hitlist_destroy", "sa_hip_last_search_above_seconds",
 )
 
 
@@ -366,6 +368,25 @@ def load_library() -> C.CDLL:
     lib.sa_hip_search_pid.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_int32] + [C.c_void_p] * 5 + [C.c_int32]
     lib.sa_hip_search_pid.restype = C.c_bool
     lib.sa_hip_last_search_quantity_seconds.restype = C.c_double
+    lib.sa_hits_above_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.sa_hits_above_scratch_bytes.restype = C.c_size_t
+    lib.sa_ctx_hits_above_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_hits_above_offsets.restype = C.c_int
+    lib.sa_ctx_hits_above_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    lib.sa_ctx_hits_above_fill.restype = C.c_int
+    lib.sa_hip_search_above.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_int32, C.POINTER(_Norm), C.POINTER(C.c_int32)]
+    lib.sa_hip_search_above.restype = C.c_void_p
+    lib.sa_hitlist_offsets.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.sa_hitlist_offsets.restype = C.c_void_p
+    lib.sa_hitlist_index.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.sa_hitlist_index.restype = C.c_void_p
+    lib.sa_hitlist_value.argtypes = [C.c_void_p]
+    lib.sa_hitlist_value.restype = C.c_void_p
+    lib.sa_hitlist_score.argtypes = [C.c_void_p]
+    lib.sa_hitlist_score.restype = C.c_void_p
+    lib.sa_hitlist_destroy.argtypes = [C.c_void_p]
+    lib.sa_hitlist_destroy.restype = None
+    lib.sa_hip_last_search_above_seconds.restype = C.c_double
     _lib = lib
     return lib
 
@@ -1362,6 +1383,29 @@ class SearchContext(Context):
                                       C.c_void_p(d_out_ptr or None), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def hits_above_offsets(self, d_vrect_ptr: int, nq: int, min_value: int, d_offsets_ptr: int, d_scratch_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_hits_above_offsets: count + scan -- the nq + 1 int64 CSR offsets of the hits (value >= min_value) of rows [0, nq)
+        of a device rectangle of pitch N; d_scratch: hits_above_scratch_bytes(N, nq) bytes, 8-byte aligned, kept for the fill"""
+        if self._lib.sa_ctx_hits_above_offsets(self._h, C.c_void_p(d_vrect_ptr or None), _int32("nq", nq), _int32("min_value", min_value),
+                                               C.c_void_p(d_offsets_ptr or None), C.c_void_p(d_scratch_ptr or None), C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def hits_above_fill(self, d_vrect_ptr: int, d_rect_ptr: int, nq: int, min_value: int, d_offsets_ptr: int, d_scratch_ptr: int,
+                        d_index_ptr: int, d_value_ptr: int = 0, d_score_ptr: int = 0, stream: int = 0) -> None:
+        """sa_ctx_hits_above_fill: index (ascending d per row), value and raw score of every hit, E = offsets[nq] int32 each, from
+        the offsets and scratch hits_above_offsets left for the same rectangle, nq and min_value; d_value / d_score 0: not asked
+        for; d_rect is read iff d_score"""
+        if self._lib.sa_ctx_hits_above_fill(self._h, C.c_void_p(d_vrect_ptr or None), C.c_void_p(d_rect_ptr or None), _int32("nq", nq),
+                                            _int32("min_value", min_value), C.c_void_p(d_offsets_ptr or None), C.c_void_p(d_scratch_ptr or None),
+                                            C.c_void_p(d_index_ptr or None), C.c_void_p(d_value_ptr or None), C.c_void_p(d_score_ptr or None),
+                                            C.c_void_p(stream)):
+            raise AlignError(_err())
+
+
+def hits_above_scratch_bytes(n_db: int, nq: int) -> int:
+    """device bytes SearchContext.hits_above_offsets / _fill need as scratch: 8 * (nq * S + 1), S the segments of a row"""
+    return int(load_library().sa_hits_above_scratch_bytes(_int32("n_db", n_db), _int32("nq", nq)))
+
 
 def hits_scratch_bytes(n_db: int, nq: int, k: int) -> int:
     """device bytes SearchContext.hits needs as scratch (0: none, the rows alone fill the device)"""
@@ -1438,6 +1482,53 @@ def hip_search(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: O
     if rect:
         res += (out,)
     return res[0] if len(res) == 1 else res
+
+
+class HitList:
+    """what hip_search_above returns: the hits of every query as a CSR -- offsets (M + 1, int64), and per hit index (ascending
+    within a query), value (the thresholded quantity) and score (the raw score), int32[E]; denominators (N + M) under a norm"""
+
+    def __init__(self, offsets: np.ndarray, index: np.ndarray, value: np.ndarray, score: np.ndarray, denominators: Optional[np.ndarray] = None):
+        self.offsets, self.index, self.value, self.score, self.denominators = offsets, index, value, score, denominators
+
+    def __len__(self) -> int:
+        return int(self.index.shape[0])
+
+    def row(self, q: int) -> slice:
+        return slice(int(self.offsets[q]), int(self.offsets[q + 1]))
+
+
+def hip_search_above(db: SequenceStore, queries: SequenceStore, scoring: Scoring, min_value: int, norm: Optional["Norm"] = None,
+                     pid: Optional[int] = None) -> HitList:
+    """sa_hip_search_above: every database sequence whose value against a query is at least min_value, on the first device.  The
+    value is the raw score, or with norm=Norm(source, rule) the normalised score, or with pid=PID_* percent identity, both in
+    parts per million.  Any int32 threshold is valid.  Asking for both quantities is the library's to refuse."""
+    lib = load_library()
+    sc = scoring._as_c()
+    t = _int32("min_value", min_value)
+    cn = den = None
+    if norm is not None:
+        cn, den = norm._as_c(db.num + queries.num)
+    cd = None if pid is None else C.c_int32(_denom(pid))
+    handle = lib.sa_hip_search_above(db._as_c(), queries._as_c(), C.byref(sc), t, None if cn is None else C.byref(cn),
+                                     None if cd is None else C.byref(cd))
+    if not handle:
+        raise AlignError(_err())
+    try:
+        m, count = C.c_int32(0), C.c_int64(0)
+        off = lib.sa_hitlist_offsets(handle, C.byref(m))
+        ptrs = (lib.sa_hitlist_index(handle, C.byref(count)), lib.sa_hitlist_value(handle), lib.sa_hitlist_score(handle))
+        e = count.value
+        offsets = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_int64)), (m.value + 1,)).copy()
+        index, value, score = (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (e,)).copy() if e else np.zeros(0, np.int32) for p in ptrs)
+    finally:
+        lib.sa_hitlist_destroy(handle)
+    return HitList(offsets, index, value, score, None if den is None else den[:db.num + queries.num])
+
+
+def last_search_above_seconds() -> float:
+    """device time of count + scan + fill in the last hip_search_above call, summed over its batches"""
+    return float(load_library().sa_hip_last_search_above_seconds())
 
 
 def last_search_seconds() -> float:

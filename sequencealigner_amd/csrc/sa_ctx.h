@@ -7,6 +7,7 @@
  *   sa_gather.hip  : several devices of one process through dense shares + RCCL all-gather
  *   sa_identity.hip: sa_ctx_identity_range, sa_hip_identity (percent identity of every pair)
  *   sa_search.hip  : sa_ctx_search_range, sa_ctx_hits, sa_hip_search (queries against a database: search contexts)
+ *   sa_search_quantity.hip, sa_search_above.hip : the hits of a search by a value; every hit at or above a threshold
  *   sa_abi.hip     : sa_hip_align, sa_hip_memory, sa_hip_filter, progress, side channels
  */
 #ifndef SA_CTX_H
@@ -233,5 +234,12 @@ int sa_search_range_launch(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect,
 /* what sa_hip_last_search_seconds / _breakdown report from now on */
 void sa_search_last_set(double align, double gather, double hits, int32_t batches);
 int sa_hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, hipStream_t s);
+
+/* ---- what sa_search_above.hip (every hit at or above a threshold) takes from sa_search_quantity.hip ------------------------------ */
+/* the sweep of sa_ctx_normalize_rect, its arguments checked by the caller */
+int sa_normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, int32_t nq, const int32_t *d_den, int32_t rule, int32_t *d_out,
+			     hipStream_t s);
+/* what sa_hip_last_search_quantity_seconds reports from now on */
+void sa_search_quantity_last_set(double seconds);
 
 #endif /* SA_CTX_H */

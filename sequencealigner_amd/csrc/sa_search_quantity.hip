@@ -308,6 +308,14 @@ bool search_plain(const char *who, struct sa_input db, struct sa_input queries, 
 
 } // namespace
 
+/* for sa_search_above.hip (sa_ctx.h) */
+int sa_normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, int32_t nq, const int32_t *d_den, int32_t rule, int32_t *d_out,
+			     hipStream_t s)
+{
+	return normalize_rect_launch(d_rect, n_db, q0, nq, d_den, rule, d_out, s);
+}
+void sa_search_quantity_last_set(double seconds) { g_last_quantity_seconds.store(seconds); }
+
 extern "C" int sa_ctx_normalize_rect(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, int32_t q0, const int32_t *d_den, int32_t rule,
 				     int32_t *d_out, void *stream)
 {
