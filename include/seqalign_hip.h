@@ -138,7 +138,24 @@ int64_t sa_ctx_pairs(const sa_ctx *ctx);
 /* Scores of packed pair indices [start, start+count) into DEVICE memory
  * d_scores[0..count) (= the reference's `kernel(scores, start, batch)`,
  * src/bio/align.h:48, src/bio/kernels.cu:32-40,73).  Asynchronous on `stream`
- * (a hipStream_t, NULL = default stream). 0 on success. */
+ * (a hipStream_t, NULL = default stream). 0 on success.
+ * Calls of ONE context (this call, sa_ctx_align_range16, sa_ctx_align_share; all from one host thread at a time -- a context is
+ * not thread-safe):
+ *   in order on one stream   always fine, any number queued: every call takes its own tile counters from a ring, and a call that
+ *                            reuses a slot waits, on its stream, for the slot's previous user.
+ *   on several streams       fine when every range in flight runs on the packed and s32 TILE kernels alone -- no column sequence
+ *                            longer than 1024 residues in it, and a scoring inside the systolic kernels' limits (sa_ctx_timing
+ *                            names the kernels a range ran on: sa_k_systolic_pk_bundle<..> and sa_k_systolic<..,G..,K..> without
+ *                            "strips").  Those launches touch nothing of the context but the call's own counters and read-only
+ *                            tables.
+ *                            NOT for a range with a strip-mined column (> 1024 residues) or a pair-per-wave run (a scoring beyond
+ *                            those limits): these launches work in the context's one strip-boundary scratch, as
+ *                            sa_ctx_identity_range, sa_ctx_denominators and sa_ctx_alignments do.  Such a call is ordered by
+ *                            the caller -- one stream, or the caller's own events -- against every other call of the context
+ *                            that uses the scratch.
+ * The first call of a range builds and uploads its launch plan (blocking copies on the host; later calls of the range only
+ * enqueue); a context keeps the plans of its 160 most recently used ranges, and building the 161st frees the oldest with
+ * hipFree, which waits for the device. */
 int sa_ctx_align_range(sa_ctx *ctx, int64_t start, int64_t count, int32_t *d_scores, void *stream);
 
 /* Diagnostics: how the packed tiles of the context's LAST launch (range, share or host delivery batch) got their row tokens --

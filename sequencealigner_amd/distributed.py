@@ -230,6 +230,14 @@ class TiledGatherStep:
     The step returns with the main stream waiting for everything: an event on the main stream marks "packed s32
     vector complete on every GPU AND this rank's scores in the host matrix".
 
+    Contract between consecutive steps.  Every step overwrites the same buffers (`packed`, `shares`, the host matrix).  With
+    several super-chunks every step first waits for the caller's stream, so whatever the caller enqueued there after step N is
+    ordered before step N + 1.  With ONE super-chunk (the benchmark's configuration) only the FIRST step waits for the caller's
+    stream; later steps follow the previous step on the step's own stream and nothing else.  A reader that the caller puts on
+    its stream after step N -- a kernel or an asynchronous copy out of `packed`, the shares or the host matrix -- must therefore
+    have finished, or be fenced by an event of the caller's own that the caller waits for, before step N + 1 is issued: the step
+    does not wait for it, and would overwrite what it is reading.
+
     `dist=None` with world > 1 emulates the other ranks on this device (their shares are computed here too, in place of
     the all-gather): tests.  `solo=True`: only this rank's share is computed and nothing is gathered (the other shares
     hold stale data): timing rehearsals of one rank's step on one GPU."""
