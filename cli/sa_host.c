@@ -1017,6 +1017,71 @@ int sa_host_write_search_list(const char *path, const struct sa_host_store *db, 
 	return rc;
 }
 
+/* --query --strands both (include/seqalign_hip.h: sa_hip_search_strands / sa_hip_search_above_strands): the strands, added to the
+ * finished file of sa_host_write_search (k >= 1: /hit_strands M x k U8 from hit_strands) or of sa_host_write_search_list (count >= 0:
+ * /hitlist_strands, `count` U8 from list_strands, extent 0 when there is no hit); with `rect_strands` /query_strands (M x N U8), with
+ * `reverse_denominators` /query_reverse_denominators (M I32LE: the denominators of the reverse complements, beside
+ * /query_denominators).  0 is the forward strand, 1 the reverse one; any other byte is refused.  Everything that can be refused is
+ * refused while the file is open read-only: the file holds /hit_indices of M x k (or /hitlist_indices of `count`) and none of the
+ * datasets yet. */
+int sa_host_write_search_strands(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
+				 const uint8_t *hit_strands, int64_t count, const uint8_t *list_strands, const uint8_t *rect_strands,
+				 const int32_t *reverse_denominators)
+{
+	if (!path || !db || !queries)
+		return fail("Strand data missing");
+	if (db->in.num < 1 || queries->in.num < 1)
+		return fail("A search needs a database and queries");
+	const size_t n = (size_t)db->in.num, m = (size_t)queries->in.num;
+	const bool list = count >= 0;
+	if (list ? k != 0 : (k < 1 || k > SA_HIP_NEIGHBORS_MAX || (size_t)k > n))
+		return fail(list ? "The strands of a hit list go without a hit count"
+				 : "Hit count must be between 1 and %d and at most the number of database sequences", SA_HIP_NEIGHBORS_MAX);
+	if (list ? (count > 0 && !list_strands) : !hit_strands)
+		return fail("Strand data missing");
+	const size_t hits = list ? (size_t)count : m * (size_t)k;
+	const uint8_t *of_hits = list ? list_strands : hit_strands;
+	for (size_t t = 0; t < hits; t++)
+		if (of_hits[t] > 1)
+			return fail("Strand %d of hit %zu is neither forward (0) nor reverse (1)", of_hits[t], t);
+	if (rect_strands)
+		for (size_t t = 0; t < m * n; t++)
+			if (rect_strands[t] > 1)
+				return fail("Strand %d of query %zu against database sequence %zu is neither forward (0) nor reverse (1)", rect_strands[t], t / n, t % n);
+#define SIDE_U8 H5T_STD_U8LE, H5T_NATIVE_UINT8
+	const struct side_set sets[4] = { { "/hit_strands", 2, { m, (hsize_t)k }, SIDE_U8, list ? NULL : hit_strands, true },
+					  { "/hitlist_strands", 1, { (hsize_t)hits }, SIDE_U8, list_strands, !list },
+					  { "/query_strands", 2, { m, n }, SIDE_U8, rect_strands, true },
+					  { "/query_reverse_denominators", 1, { m }, SIDE_I32, reverse_denominators, true } };
+#undef SIDE_U8
+	hid_t file;
+	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDONLY, H5P_DEFAULT); } H5E_END_TRY
+	if (file < 0)
+		return fail("Failed to open HDF5 file: %s", path);
+	int rc = 0;
+	const char *of = list ? "/hitlist_indices" : "/hit_indices";
+	hsize_t dims[2] = { 0, 0 };
+	hid_t set = -1, space = -1;
+	H5E_BEGIN_TRY {
+		set = H5Lexists(file, of, H5P_DEFAULT) > 0 ? H5Dopen2(file, of, H5P_DEFAULT) : -1;
+		space = set >= 0 ? H5Dget_space(set) : -1;
+	} H5E_END_TRY
+	const int rank = list ? 1 : 2;
+	if (space < 0 || H5Sget_simple_extent_ndims(space) != rank || H5Sget_simple_extent_dims(space, dims, NULL) != rank ||
+	    (list ? dims[0] != (hsize_t)hits : (dims[0] != m || dims[1] != (hsize_t)k)))
+		rc = list ? fail("%s holds no /hitlist_indices of %zu hits: the strands belong to the file of a search", path, hits)
+			  : fail("%s holds no /hit_indices of %zu x %d hits: the strands belong to the file of a search", path, m, k);
+	if (space >= 0)
+		H5Sclose(space);
+	if (set >= 0)
+		H5Dclose(set);
+	for (int d = 0; d < 4 && !rc; d++)
+		if (H5Lexists(file, sets[d].name, H5P_DEFAULT) > 0)
+			rc = fail("%s already holds %s", path, sets[d].name);
+	H5Fclose(file);
+	return rc ? rc : write_side_sets(path, NULL, 0, false, sets, 4);
+}
+
 /* The score graph as CSR (include/seqalign_hip.h: sa_hip_edges): /edge_offsets N + 1 I64LE, /edge_indices and /edge_scores
  * E = offsets[N] I32LE each (extent 0 when there is no edge).  create: as write_side_sets has it.  The arrays are checked before
  * anything is opened: offsets[0] == 0, offsets non-decreasing, every index in [0, N). */

@@ -116,6 +116,14 @@ int sa_host_write_search_list(const char *path, const struct sa_host_store *db, 
 			      const int32_t *index, const int32_t *score, int32_t min_value, const int32_t *value, int32_t kind, int32_t source,
 			      int32_t rule_or_denom, const int32_t *denominators, const int32_t *rect, const int32_t *vrect, int alignments,
 			      const struct sa_aln *records, const uint32_t *cigar, int64_t runs);
+/* --query --strands both: the strands of a folded search (sa_hip_search_strands / sa_hip_search_above_strands), added to the finished
+ * file of sa_host_write_search (k >= 1, count < 0: /hit_strands, M x k U8, from hit_strands) or of sa_host_write_search_list (k = 0,
+ * count = E >= 0: /hitlist_strands, E U8, from list_strands; extent 0 when E = 0); with rect_strands /query_strands (M x N U8), with
+ * reverse_denominators /query_reverse_denominators (M I32LE).  0 = forward, 1 = reverse; another byte, a file without the hits of
+ * that shape or one that holds a dataset already give an error and leave the file as it was. */
+int sa_host_write_search_strands(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
+				 const uint8_t *hit_strands, int64_t count, const uint8_t *list_strands, const uint8_t *rect_strands,
+				 const int32_t *reverse_denominators);
 /* --min-score: /edge_offsets (N + 1 I64LE), /edge_indices and /edge_scores (E = offsets[N] I32LE each; extent 0 when E = 0),
  * the CSR arrays of sa_hip_edges / sa_zjob_edges.  `create` as in sa_host_write_neighbors: 0 adds the three datasets to the
  * finished file at `path`, 1 writes a new file with /sequences and the three (--edges-only).  offsets[0] != 0, decreasing

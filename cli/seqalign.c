@@ -37,6 +37,9 @@
  *             --hits-min T  (with --query, in place of -k: every hit whose value is at least T, as CSR: /hitlist_offsets,
  *             /hitlist_indices, /hitlist_scores, /hitlist_min, under --hits-by /hitlist_values, with --alignments
  *             /hitlist_alignment_records, /hitlist_cigar_offsets and /hitlist_cigars)
+ *             --strands forward|both  (with --query, both: every query also reverse-complemented, the two searches folded on the device
+ *             by the larger value: /hit_strands or /hitlist_strands beside the hits of the folded search, with --query-scores
+ *             /query_strands; forward, the default, writes what a run without the option writes)
  * Flow (main, one function per phase): options -> banner -> load + filter -> output plan -> the first pass (tile job | one selection only |
  * host matrix | the search) -> per selection, in the order of the file: its second pass where the first left it unanswered, then its
  * datasets (a search: its alignments, then its one file) -> -B report.
@@ -155,6 +158,9 @@ struct options {
 	/* --hits-min T: with --query, in place of -k: every hit whose value (the quantity of --hits-by, or the raw score) is at least T */
 	bool has_hits_min;
 	int32_t hits_min;
+	/* --strands forward|both: with --query, both: every query is searched as written and reverse-complemented, the two folded on the
+	 * device (include/seqalign_hip.h: sa_hip_search_strands); forward, the default: the output of a run without the option */
+	bool strands_both;
 };
 
 static void usage(const char *argv0)
@@ -278,6 +284,17 @@ static void usage(const char *argv0)
 	       "                           --alignments /hitlist_alignment_records (E x 8), /hitlist_cigar_offsets (E + 1) and\n"
 	       "                           /hitlist_cigars; with --query-scores /query_scores and, under a quantity, /query_values,\n"
 	       "                           which cost a second alignment of the rectangle (the hit list does not keep it)\n"
+	       "      --strands WHICH      With --query: forward (the default: every query as written) | both: every query is also\n"
+	       "                           searched reverse-complemented (IUPAC: A-T, G-C, R-Y, K-M, B-V, H-D; S, W, N, * themselves;\n"
+	       "                           U as A) and the two results are folded on the device -- per query and database sequence\n"
+	       "                           the strand with the larger value (of --hits-by, or the raw score) wins, the forward one on\n"
+	       "                           a tie.  /hit_indices, /hit_scores and /hit_values are those of the folded search;\n"
+	       "                           /hit_strands (M x K, 8-bit: 0 forward, 1 reverse) is added, under --hits-min\n"
+	       "                           /hitlist_strands (E); --query-scores writes the folded /query_scores and /query_values and\n"
+	       "                           adds /query_strands (M x N, 8-bit); --alignments traces every hit on its own strand: for\n"
+	       "                           a reverse hit a = the REVERSE COMPLEMENT of the query (position p there is position\n"
+	       "                           length - 1 - p of the query as given).  /query_sequences stays the queries as given; -f\n"
+	       "                           filters the database only.  Needs a nucleotide matrix and queries of the alphabet above\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -340,7 +357,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
 		     { "quantiles", 12, true }, { "normalize", 13, true }, { "identity", 14, true },
 		     { "linkage-method", 15, true }, { "query", 16, true }, { "query-scores", 17, false }, { "hits-by", 18, true },
-		     { "hits-min", 19, true },
+		     { "hits-min", 19, true }, { "strands", 20, true },
 	     { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
@@ -560,6 +577,13 @@ static int parse_args(int argc, char **argv, struct options *o)
 				o->has_hits_min = true;
 				o->hits_min = (int32_t)v;
 				break;
+			case 20:
+				if (strcmp(val, "forward") && strcmp(val, "both")) {
+					err("Strands must be one of forward, both: %s", val);
+					return 1;
+				}
+				o->strands_both = !strcmp(val, "both");
+				break;
 			case 16: o->query = val; break;
 			case 17: o->query_scores = true; break;
 			case 18: {
@@ -703,6 +727,9 @@ struct run {
 	struct { int32_t *index, *score, *rect, *value, *vrect; sa_alns *alns; double hits_seconds, gather_seconds; int32_t batches; } sr;
 	/* --query --hits-min: the hits of every query as CSR (E of them), in arrays the library owns */
 	struct { sa_hitlist *list; long long count; double rect_seconds; } ab;
+	/* --query --strands both: the strand of every hit (M x K) and, with --query-scores, of every cell (M x N); the device time of
+	 * fold + strand take */
+	struct { uint8_t *hit, *rect; double seconds; } st;
 	struct { double seconds; long long runs; } trace;
 	struct { /* the fractions' ranks: one select call answers all of them, where the matrix is */
 		int64_t ranks[SA_HIP_SELECT_MAX], below[SA_HIP_SELECT_MAX];
@@ -827,6 +854,15 @@ static const char *query_conflict(const struct options *o)
 	     : o->normalize ? "--normalize" : o->identity ? "--identity" : o->compression ? "-z, --compression" : NULL;
 }
 
+/* is the matrix of -m one of the nucleotide tables?  (sa_matrix_load has accepted the name: it compares without case) */
+static bool matrix_is_nucleotide(const char *name)
+{
+	for (int k = 0; k < sa_matrix_count(); k++)
+		if (!strcasecmp(name, sa_matrix_name(k)))
+			return sa_matrix_is_nucleotide(k) != 0;
+	return false;
+}
+
 /* ---- the phases of main, in its order ------------------------------------------------------------------------------------------ */
 /* options, -l, validation in the reference's terms (src/bio/align.c:130-201, ga.c:70-88, output.c:126-148) and the scoring.
  * returns 0 ok, 1 error, 2 handled-and-exit-success */
@@ -868,6 +904,8 @@ static int set_up(int argc, char **argv, struct run *r)
 	if (ok && o->has_hits_min && o->neighbors)
 		ok = (err("Options --hits-min and -k, --neighbors conflict: a search writes the K best hits of every query or every hit at or "
 			  "above T, not both"), false);
+	if (ok && o->strands_both && !o->query)
+		ok = (err("Option --strands both requires --query: it searches every query on both strands"), false);
 	if (ok && o->query && !o->neighbors && !o->has_hits_min)
 		ok = (err("Option --query requires -k, --neighbors (the number of hits per query) or --hits-min (the threshold of the hits)"), false);
 	if (ok && o->query && query_conflict(o))
@@ -905,6 +943,9 @@ static int set_up(int argc, char **argv, struct run *r)
 			  "--clusters-quantile or --quantiles (the similarity matrix itself stays raw)"), false);
 	if (ok && sa_matrix_load(o->matrix, sc->lut, sc->sub))
 		ok = (err("Invalid substitution matrix name"), false);
+	if (ok && o->strands_both && !matrix_is_nucleotide(o->matrix))
+		ok = (err("Options --strands both and -m %s conflict: only a nucleotide sequence has a reverse complement, and %s is an amino-acid "
+			  "matrix", o->matrix, o->matrix), false);
 	if (ok && (sc->method = sa_method_parse(o->align)) < 0)
 		ok = (err("Invalid alignment method"), false);
 	if (ok && o->gap_pen >= 0 && (o->gap_open >= 0 || o->gap_ext >= 0))
@@ -977,6 +1018,8 @@ static void banner(const struct run *r)
 			info("Hits ranked by %s, in parts per million (the hit scores stay raw)", o->hits_name);
 	} else if (o->neighbors)
 		info("Neighbors: %d per sequence%s", o->neighbors, o->neighbors_only ? " (no similarity matrix)" : "");
+	if (o->strands_both)
+		info("Strands: both -- every query as written and reverse-complemented, folded on the device (the forward strand on a tie)");
 	if (o->min_q >= 0)
 		info("Score graph: pairs that score at least the %g quantile of the scores%s", o->quantiles[o->min_q],
 		     o->edges_only ? " (no similarity matrix)" : "");
@@ -1018,7 +1061,25 @@ static bool load_queries(struct run *r)
 		fprintf(stderr, "Use %s -h, --help for usage information\n", r->argv0);
 		return false;
 	}
-	r->npairs = (long long)m * (long long)r->n;
+	r->npairs = (long long)m * (long long)r->n * (o->strands_both ? 2 : 1);
+	if (o->strands_both) { /* every query has a reverse complement the matrix takes, or the run ends here with the residue named */
+		uint8_t *rc = malloc(r->queries.blob_bytes ? r->queries.blob_bytes : 1);
+		if (!rc)
+			return failed("Out of memory allocating search results");
+		const bool can = sa_reverse_complement(r->queries.in, NULL, &r->sc, rc);
+		free(rc);
+		if (!can) {
+			err("Options --strands both and --query %s conflict: %s", o->query, sa_last_error());
+			fprintf(stderr, "Use %s -h, --help for usage information\n", r->argv0);
+			return false;
+		}
+		if (!o->has_hits_min)
+			r->st.hit = malloc(m * (size_t)o->neighbors);
+		if (o->query_scores)
+			r->st.rect = malloc(m * r->n);
+		if ((!o->has_hits_min && !r->st.hit) || (o->query_scores && !r->st.rect))
+			return failed("Out of memory allocating search results");
+	}
 	/* (--hits-min: the hits come back in arrays the library owns) */
 	if (!o->has_hits_min) {
 		r->sr.index = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
@@ -1036,7 +1097,7 @@ static bool load_queries(struct run *r)
 		if (o->query_scores)
 			r->sr.vrect = malloc(sizeof(int32_t) * m * r->n);
 		if (o->hits_kind == 1) {
-			r->norm_spec.denominators = malloc(sizeof(int32_t) * (r->n + m));
+			r->norm_spec.denominators = malloc(sizeof(int32_t) * (r->n + m * (o->strands_both ? 2 : 1))); /* (both strands: N + 2 M) */
 			r->q.norm = &r->norm_spec;
 		} else
 			r->q.pid = &o->hits_denom;
@@ -1283,12 +1344,17 @@ static bool run_search(struct run *r)
 	const double t0 = now();
 	/* the one call that fits (the *_norm call with norm == NULL is sa_hip_search itself) */
 	if (o->has_hits_min) {
-		r->ab.list = sa_hip_search_above(r->store.in, r->queries.in, &r->sc, o->hits_min, r->q.norm, r->q.pid);
+		r->ab.list = o->strands_both ? sa_hip_search_above_strands(r->store.in, r->queries.in, &r->sc, NULL, o->hits_min, r->q.norm, r->q.pid)
+					     : sa_hip_search_above(r->store.in, r->queries.in, &r->sc, o->hits_min, r->q.norm, r->q.pid);
 		if (!r->ab.list)
 			return failed(sa_last_error());
 		int64_t count = 0;
 		(void)sa_hitlist_index(r->ab.list, &count);
 		r->ab.count = (long long)count;
+	} else if (o->strands_both) {
+		if (!sa_hip_search_strands(r->store.in, r->queries.in, &r->sc, NULL, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->st.hit,
+					   r->sr.rect, r->sr.vrect, r->st.rect, r->q.norm, r->q.pid))
+			return failed(sa_last_error());
 	} else if (!(r->q.pid ? sa_hip_search_pid(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->sr.rect,
 					   r->sr.vrect, *r->q.pid)
 		       : sa_hip_search_norm(r->store.in, r->queries.in, &r->sc, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->sr.rect,
@@ -1297,15 +1363,18 @@ static bool run_search(struct run *r)
 	const double call = now() - t0;
 	stamp("sa_hip_search returned");
 	r->t_quantity = sa_hip_last_search_quantity_seconds();
+	r->st.seconds = o->strands_both ? sa_hip_last_search_strands_seconds() : 0.0;
 	finish_progress(r);
 	sa_hip_last_search_breakdown(&r->t_align, &r->sr.gather_seconds, &r->sr.hits_seconds, &r->sr.batches);
-	const double device = sa_hip_last_search_seconds() + (r->q.norm ? r->t_quantity : 0.0);
+	const double device = sa_hip_last_search_seconds() + (r->q.norm ? r->t_quantity : 0.0) + r->st.seconds;
 	r->t_setup = call > device ? call - device : 0.0;
 	if (o->has_hits_min && o->query_scores) {
 		/* the rectangles do not come back with the hit list: a second alignment, index NULL, delivers them */
 		const double t1 = now();
-		if (!(r->q.pid ? sa_hip_search_pid(r->store.in, r->queries.in, &r->sc, 0, NULL, NULL, NULL, r->sr.rect, r->sr.vrect, *r->q.pid)
-			       : sa_hip_search_norm(r->store.in, r->queries.in, &r->sc, 0, NULL, NULL, NULL, r->sr.rect, r->sr.vrect, r->q.norm)))
+		if (!(o->strands_both ? sa_hip_search_strands(r->store.in, r->queries.in, &r->sc, NULL, 0, NULL, NULL, NULL, NULL, r->sr.rect, r->sr.vrect,
+							      r->st.rect, r->q.norm, r->q.pid)
+		      : r->q.pid    ? sa_hip_search_pid(r->store.in, r->queries.in, &r->sc, 0, NULL, NULL, NULL, r->sr.rect, r->sr.vrect, *r->q.pid)
+				    : sa_hip_search_norm(r->store.in, r->queries.in, &r->sc, 0, NULL, NULL, NULL, r->sr.rect, r->sr.vrect, r->q.norm)))
 			return failed(sa_last_error());
 		r->ab.rect_seconds = now() - t1;
 		stamp("sa_hip_search (rectangles) returned");
@@ -1328,14 +1397,18 @@ static bool trace_hits(struct run *r)
 	int32_t *pa = malloc(sizeof(int32_t) * np);
 	if (!pa)
 		return failed("Out of memory allocating alignment pairs");
+	/* --strands both: a reverse hit is traced on the row of the query's reverse complement, M rows on (include/seqalign_hip.h) */
+	const uint8_t *strand = !o->strands_both ? NULL : o->has_hits_min ? sa_hitlist_strand(r->ab.list) : r->st.hit;
+	const int32_t m = r->queries.in.num;
 	if (o->has_hits_min) { /* the E pairs (query q, its hits) in the order of the hit list */
 		for (int32_t q = 0; q < r->queries.in.num; q++)
 			for (int64_t t = offsets[q]; t < offsets[q + 1]; t++)
-				pa[t] = (int32_t)r->n + q;
+				pa[t] = (int32_t)r->n + q + (strand && strand[t] ? m : 0);
 	} else
 		for (size_t t = 0; t < np; t++)
-			pa[t] = (int32_t)(r->n + t / (size_t)o->neighbors);
-	sa_ctx *ctx = sa_ctx_create_search(0, r->store.in, r->queries.in, &r->sc);
+			pa[t] = (int32_t)(r->n + t / (size_t)o->neighbors) + (strand && strand[t] ? m : 0);
+	sa_ctx *ctx = o->strands_both ? sa_ctx_create_search_strands(0, r->store.in, r->queries.in, &r->sc, NULL)
+				      : sa_ctx_create_search(0, r->store.in, r->queries.in, &r->sc);
 	r->sr.alns = ctx ? sa_ctx_alignments(ctx, pa, index, (int64_t)np) : NULL;
 	free(pa);
 	if (ctx)
@@ -1347,6 +1420,8 @@ static bool trace_hits(struct run *r)
 	return true;
 }
 
+static bool write_search_plain(struct run *r, const uint32_t *cigar, int64_t runs);
+
 /* --query: everything of a search into one file of its own */
 static bool write_search(struct run *r)
 {
@@ -1354,6 +1429,18 @@ static bool write_search(struct run *r)
 	int64_t runs = 0;
 	const uint32_t *cigar = r->sr.alns ? sa_alns_cigar(r->sr.alns, &runs) : NULL;
 	r->trace.runs = (long long)runs;
+	if (o->strands_both) /* the files of a search, then the strands added to them */
+		return write_search_plain(r, cigar, runs) &&
+		       WRITE_OUT(r, sa_host_write_search_strands(o->output, &r->store, &r->queries, o->has_hits_min ? 0 : o->neighbors, r->st.hit,
+								 o->has_hits_min ? (int64_t)r->ab.count : -1, o->has_hits_min ? sa_hitlist_strand(r->ab.list) : NULL,
+								 r->st.rect, r->q.norm ? r->q.norm->denominators + r->n + r->queries.in.num : NULL),
+				 "strands written");
+	return write_search_plain(r, cigar, runs);
+}
+
+static bool write_search_plain(struct run *r, const uint32_t *cigar, int64_t runs)
+{
+	const struct options *o = &r->o;
 	if (o->has_hits_min)
 		return WRITE_OUT(r, sa_host_write_search_list(o->output, &r->store, &r->queries, sa_hitlist_offsets(r->ab.list, NULL),
 							      sa_hitlist_index(r->ab.list, NULL), sa_hitlist_score(r->ab.list), o->hits_min,
@@ -1579,6 +1666,9 @@ static void report(const struct run *r)
 		} else
 			printf("  (hit selection on the device, K = %d: %.6f sec; rows gathered in %.6f sec; %d batches of queries)\n", o->neighbors,
 			       r->sr.hits_seconds, r->sr.gather_seconds, r->sr.batches);
+		if (o->strands_both)
+			printf("  (both strands searched: every query as written and reverse-complemented; fold + strands of the hits on the device: %.6f sec)\n",
+			       r->st.seconds);
 		if (r->q.norm)
 			printf("  (hits by %s on the device: denominators + sweep over %lld pairs, %.6f sec)\n", o->hits_name, r->npairs, r->t_quantity);
 		if (r->q.pid)
@@ -1629,6 +1719,8 @@ static void release(struct run *r)
 	free(r->sr.rect);
 	free(r->sr.value);
 	free(r->sr.vrect);
+	free(r->st.hit);
+	free(r->st.rect);
 	sa_host_store_free(&r->queries);
 	sa_host_store_free(&r->store);
 	stamp("released");

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls, then the *_search* / *_hits calls, then the *_rect / _hits_take / sa_hip_search_norm / _pid calls, then the *_hits_above_* / sa_hip_search_above / sa_hitlist_* calls */
+#define SA_ABI_VERSION 4 /* 4: the sa_zjob_* / sa_hip_tiles_begin entry points; since then, additions only: the *_neighbors, *_alignments, *_edge*, *_linkage and *_select calls, then the *_norm* / *_denominators / *_normalize calls, then the *_identity* / *_pid* calls, then the *_agglo* calls, then the *_search* / *_hits calls, then the *_rect / _hits_take / sa_hip_search_norm / _pid calls, then the *_hits_above_* / sa_hip_search_above / sa_hitlist_* calls, then the *_strand* / sa_dna_complement / sa_reverse_complement calls */
 
 /* ---- data types shared with the reference ------------------------------- */
 
@@ -448,6 +448,87 @@ const int32_t *sa_hitlist_value(const sa_hitlist *h);
 const int32_t *sa_hitlist_score(const sa_hitlist *h);
 void sa_hitlist_destroy(sa_hitlist *h);
 double sa_hip_last_search_above_seconds(void);
+
+/* ---- search: both strands of DNA queries, folded on the device ------------------------------------------------------------------
+ * No reference counterpart.  A read comes from either strand of its source; a search that aligns every query as written finds no
+ * homologue for about half of a sequencing run.  A STRANDS context holds db (N), the M queries and the M reverse complements of
+ * the queries as one search context: sa_ctx_search_queries answers 2 M, row M + q of any rectangle is query q reversed and
+ * complemented, and every search call above (sa_ctx_search_range, _normalize_rect, _identity_rect, sa_ctx_denominators -- N + 2 M
+ * values --, sa_ctx_hits, _hits_take, _hits_above_*, sa_ctx_alignments) works on those rows unchanged: they are simply more rows.
+ * No alignment kernel knows of strands.
+ *
+ * Complement: sa_dna_complement fills the IUPAC table over the upper-case nucleotide alphabet of the shipped tables,
+ * ATGCSWRYKMBVHDN*: A<->T, G<->C, R<->Y, K<->M, B<->V, H<->D; S, W, N and * map to themselves; U -> A; every other byte maps to
+ * 0, "no complement".  sa_reverse_complement writes, for every sequence of `in`, its residues reversed and mapped through comp
+ * (NULL: sa_dna_complement's) into blob_out at the SAME offsets, the NUL terminators included: the same meta serves, blob_out
+ * spans what in.seqs spans and may not be in.seqs.  false + sa_last_error naming the sequence (#1 is the first), the residue and the
+ * byte for a residue whose complement is 0, and for one whose complement sc->lut rejects (sc may be NULL: not checked).
+ *
+ * Fold: v_fwd = value of row q, v_rev = value of row M + q, for the same d.  The cell is REVERSE iff v_rev > v_fwd; equal values
+ * keep the forward strand, whatever the raw scores are.  The folded value is the larger value, the folded raw score the raw score
+ * of the strand that won.  Strand bitmap: (N + 63) / 64 uint64 words per row; bit d & 63 of word d >> 6 of row r is the strand of
+ * cell (r, d), SA_STRAND_FORWARD = 0, SA_STRAND_REVERSE = 1; bits at or beyond N are zero.
+ *
+ * sa_ctx_create_search_strands   builds the reverse complements on the host (comp == NULL: sa_dna_complement) and is otherwise
+ *          sa_ctx_create_search.  NULL + sa_last_error, before a device is looked for: a residue that cannot be complemented, as
+ *          above; N + 2 M or the concatenated blob past the int32 of struct sa_meta.
+ * sa_ctx_search_strands   2 for such a context, 1 for a context of sa_ctx_create_search, 0 otherwise.
+ * The three device-resident calls are asynchronous on `stream`, allocate nothing, never synchronise with the host, use no
+ * atomics and give the same bytes run after run.  Each refuses, before any launch: a context that is not a strands context, a
+ * null required pointer, nq outside [1, M], a bitmap pointer that is not 8-byte aligned, a rectangle or index that is not 4-byte
+ * aligned (offsets: 8-byte).  Rectangles need no more than 4-byte alignment (an offset view will do).
+ * sa_ctx_strand_fold   rows [0, nq) at pitch N: d_vfwd / d_vrev are the value rectangles of the two strands and decide; d_sfwd /
+ *          d_srev / d_sbest, the raw-score rectangles, are carried along -- all three given or all three NULL (the raw-score
+ *          search, where value is score).  d_vbest may be d_vfwd and d_sbest may be d_sfwd (in place); any other overlap is the
+ *          caller's error.  d_bits (nq * ((N + 63) / 64) uint64) may be NULL.  One streaming kernel.
+ * sa_ctx_hits_strand   d_strand[r * k + t] (uint8) = the bit of cell (r, d_index[r * k + t]) for rows [0, nq) of an M x k hit list;
+ *          an index outside [0, N) reads nothing and gives SA_STRAND_NONE = 255.  nq and k as sa_ctx_hits.
+ * sa_ctx_hits_above_strand   the same for a CSR: row r owns entries d_offsets[r] .. d_offsets[r + 1] of d_index / d_strand;
+ *          offsets are 64-bit throughout, and E is read on the device only.
+ * sa_hip_search_strands   one call, host in / host out, first device.  index, value, score are M x k int32, strand M x k uint8;
+ *          rect and vrect are the FOLDED M x N rectangles of raw scores and values, srect the M x N strands, one uint8 per cell.
+ *          Any output may be NULL; index may be NULL only when nothing M x k is wanted.  norm and pid_denom both NULL: raw scores,
+ *          value == score; norm: normalised scores (norm->denominators, when not NULL, receives N + 2 M values: database, queries,
+ *          reverse complements); pid_denom: percent identity under *pid_denom; both: refused.  Order inside a row: value descending,
+ *          then index ascending -- the key of sa_ctx_hits.  Stream order per batch of queries [q0, q0 + nq): the forward rows, the
+ *          rows M + q0 .., each through the calls of sa_hip_search / _norm / _pid; fold in place; sa_ctx_hits on the folded values;
+ *          the raw scores and the strands of the hits.  Batches are sized as sa_hip_search sizes them, with both strands counted --
+ *          per query 4 (N + 2 M) bytes (the range row, which the two halves use in turn; not under percent identity) + 8 N (raw
+ *          scores) or 16 N (a quantity: two rectangles per strand) + 8 ((N + 63) / 64) (the bitmap) + 21 k (with hits) -- and
+ *          SA_HIP_SEARCH_BATCH_BYTES caps a batch.  Every argument is checked before a device is looked for.
+ * sa_hip_search_above_strands   the threshold form over the folded values: sa_hip_search_above with both strands.  Stream order per
+ *          batch: both halves of the rows, the quantity's sweeps, fold in place, count + scan, the host reads E, fill, the strands of
+ *          the entries.  Per query 4 (N + 2 M) bytes (not under percent identity) + 8 N (raw scores) or 16 N (a quantity) + 8 ((N + 63) / 64) (the
+ *          bitmap) + 8 (scratch).
+ *          sa_hitlist_strand: uint8[E], the strand of every hit; NULL for a list of sa_hip_search_above.  value and score are those
+ *          of the strand that won.
+ * sa_hip_last_search_strands_seconds   device time of fold + strand take, summed over the batches of the last successful
+ *          sa_hip_search_strands / sa_hip_search_above_strands.  sa_hip_last_search_seconds / _breakdown / _quantity_seconds answer for the rest as after
+ *          sa_hip_search_norm / _pid, with both halves of the alignment (and of the gather, and of the quantity) summed.
+ * Alignments of hits need no new call: on a strands context sa_ctx_alignments with a = N + q, b = d aligns a forward hit and
+ *          a = N + M + q, b = d a reverse hit; `score` equals the folded rect[q * N + d] when the strand is the hit's own.  For a
+ *          reverse hit the a_* spans and the CIGAR refer to the REVERSE COMPLEMENT of the query: position p there is position
+ *          len - 1 - p of the query as given.
+ * Non-zero / false / NULL + sa_last_error on failure. */
+#define SA_STRAND_FORWARD 0
+#define SA_STRAND_REVERSE 1
+#define SA_STRAND_NONE 255
+void sa_dna_complement(uint8_t comp[SA_LUT_SIZE]);
+bool sa_reverse_complement(struct sa_input in, const uint8_t *comp, const struct sa_scoring *sc, uint8_t *blob_out);
+sa_ctx *sa_ctx_create_search_strands(int device, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp);
+int32_t sa_ctx_search_strands(const sa_ctx *ctx);
+int sa_ctx_strand_fold(sa_ctx *ctx, const int32_t *d_vfwd, const int32_t *d_vrev, const int32_t *d_sfwd, const int32_t *d_srev, int32_t nq,
+		       int32_t *d_vbest, int32_t *d_sbest, uint64_t *d_bits, void *stream);
+int sa_ctx_hits_strand(sa_ctx *ctx, const uint64_t *d_bits, int32_t nq, int32_t k, const int32_t *d_index, uint8_t *d_strand, void *stream);
+int sa_ctx_hits_above_strand(sa_ctx *ctx, const uint64_t *d_bits, int32_t nq, const int64_t *d_offsets, const int32_t *d_index, uint8_t *d_strand,
+			     void *stream);
+bool sa_hip_search_strands(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp, int32_t k, int32_t *index,
+			   int32_t *value, int32_t *score, uint8_t *strand, int32_t *rect, int32_t *vrect, uint8_t *srect, const struct sa_norm *norm,
+			   const int32_t *pid_denom);
+sa_hitlist *sa_hip_search_above_strands(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp,
+					int32_t min_value, const struct sa_norm *norm, const int32_t *pid_denom);
+const uint8_t *sa_hitlist_strand(const sa_hitlist *h);
+double sa_hip_last_search_strands_seconds(void);
 
 /* ---- alignments for chosen pairs: traceback on the device, run-length CIGARs ----------------------------------------
  * No reference counterpart: the reference keeps scores only.  For an explicit list of pairs (a[t], b[t]) of one store,

@@ -76,6 +76,9 @@ ABI_SYMBOLS = (
     "sa_hip_last_search_quantity_seconds",
     "sa_hits_above_scratch_bytes", "sa_ctx_hits_above_offsets", "sa_ctx_hits_above_fill", "sa_hip_search_above", "sa_hitlist_offsets",
     "sa_hitlist_index", "sa_hitlist_value", "sa_hitlist_score", "sa_hitlist_destroy", "sa_hip_last_search_above_seconds",
+    "sa_dna_complement", "sa_reverse_complement", "sa_ctx_create_search_strands", "sa_ctx_search_strands", "sa_ctx_strand_fold",
+    "sa_ctx_hits_strand", "sa_ctx_hits_above_strand", "sa_hip_search_strands", "sa_hip_search_above_strands", "sa_hitlist_strand",
+    "sa_hip_last_search_strands_seconds",
 )
 
 
@@ -387,6 +390,28 @@ def load_library() -> C.CDLL:
     lib.sa_hitlist_destroy.argtypes = [C.c_void_p]
     lib.sa_hitlist_destroy.restype = None
     lib.sa_hip_last_search_above_seconds.restype = C.c_double
+    lib.sa_dna_complement.argtypes = [C.c_void_p]
+    lib.sa_dna_complement.restype = None
+    lib.sa_reverse_complement.argtypes = [_Input, C.c_void_p, C.POINTER(_Scoring), C.c_void_p]
+    lib.sa_reverse_complement.restype = C.c_bool
+    lib.sa_ctx_create_search_strands.argtypes = [C.c_int, _Input, _Input, C.POINTER(_Scoring), C.c_void_p]
+    lib.sa_ctx_create_search_strands.restype = C.c_void_p
+    lib.sa_ctx_search_strands.argtypes = [C.c_void_p]
+    lib.sa_ctx_search_strands.restype = C.c_int32
+    lib.sa_ctx_strand_fold.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 4
+    lib.sa_ctx_strand_fold.restype = C.c_int
+    lib.sa_ctx_hits_strand.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_hits_strand.restype = C.c_int
+    lib.sa_ctx_hits_above_strand.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sa_ctx_hits_above_strand.restype = C.c_int
+    lib.sa_hip_search_strands.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_void_p, C.c_int32] + [C.c_void_p] * 7 + [C.POINTER(_Norm),
+                                                                                                                 C.POINTER(C.c_int32)]
+    lib.sa_hip_search_strands.restype = C.c_bool
+    lib.sa_hip_last_search_strands_seconds.restype = C.c_double
+    lib.sa_hip_search_above_strands.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_void_p, C.c_int32, C.POINTER(_Norm), C.POINTER(C.c_int32)]
+    lib.sa_hip_search_above_strands.restype = C.c_void_p
+    lib.sa_hitlist_strand.argtypes = [C.c_void_p]
+    lib.sa_hitlist_strand.restype = C.c_void_p
     _lib = lib
     return lib
 
@@ -1331,12 +1356,48 @@ class SearchContext(Context):
     sequences of every row; alignments takes pairs (N + q, d).  The packed-range calls inherited from Context are refused by the
     library on such a context."""
 
-    def __init__(self, db: SequenceStore, queries: SequenceStore, scoring: Scoring, device: int = 0):
+    def __init__(self, db: SequenceStore, queries: SequenceStore, scoring: Scoring, device: int = 0, strands: bool = False,
+                 comp: Optional[np.ndarray] = None):
+        """strands=True: a strands context (sa_ctx_create_search_strands) -- the query rows are the M queries followed by their M
+        reverse complements under `comp` (128 uint8; None: dna_complement()), n_queries answers 2 M and n_strand_queries M"""
         sc = scoring._as_c()
-        self._adopt(lambda lib: lib.sa_ctx_create_search(int(device), db._as_c(), queries._as_c(), C.byref(sc)), (db, queries),
-                    db.num + queries.num, device)
+        if strands:
+            table = None if comp is None else _comp_table(comp)
+            self._adopt(lambda lib: lib.sa_ctx_create_search_strands(int(device), db._as_c(), queries._as_c(), C.byref(sc),
+                                                                     None if table is None else table.ctypes.data),
+                        (db, queries), db.num + 2 * queries.num, device)
+        else:
+            self._adopt(lambda lib: lib.sa_ctx_create_search(int(device), db._as_c(), queries._as_c(), C.byref(sc)), (db, queries),
+                        db.num + queries.num, device)
         self.n_db = int(self._lib.sa_ctx_search_db(self._h))
         self.n_queries = int(self._lib.sa_ctx_search_queries(self._h))
+        self.strands = int(self._lib.sa_ctx_search_strands(self._h))
+        self.n_strand_queries = self.n_queries // 2 if self.strands == 2 else self.n_queries
+
+    def strand_fold(self, d_vfwd_ptr: int, d_vrev_ptr: int, nq: int, d_vbest_ptr: int, d_bits_ptr: int = 0, d_sfwd_ptr: int = 0,
+                    d_srev_ptr: int = 0, d_sbest_ptr: int = 0, stream: int = 0) -> None:
+        """sa_ctx_strand_fold: rows [0, nq) at pitch N of the value rectangles of the two strands folded into d_vbest (the larger
+        value; the forward one on a tie), the raw scores d_sfwd / d_srev carried along into d_sbest (all three or none), the strand
+        of every cell into the bitmap d_bits (nq * strand_words(N) uint64, 8-byte aligned; 0: not asked for).  d_vbest may be
+        d_vfwd and d_sbest may be d_sfwd."""
+        if self._lib.sa_ctx_strand_fold(self._h, C.c_void_p(d_vfwd_ptr or None), C.c_void_p(d_vrev_ptr or None), C.c_void_p(d_sfwd_ptr or None),
+                                        C.c_void_p(d_srev_ptr or None), _int32("nq", nq), C.c_void_p(d_vbest_ptr or None),
+                                        C.c_void_p(d_sbest_ptr or None), C.c_void_p(d_bits_ptr or None), C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def hits_strand(self, d_bits_ptr: int, nq: int, k: int, d_index_ptr: int, d_strand_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_hits_strand: d_strand[r, t] (uint8) = the strand of cell (r, d_index[r, t]) for rows [0, nq) of an (nq, k) hit
+        list; STRAND_NONE for an index outside [0, N)"""
+        if self._lib.sa_ctx_hits_strand(self._h, C.c_void_p(d_bits_ptr or None), _int32("nq", nq), _int32("k", k), C.c_void_p(d_index_ptr or None),
+                                        C.c_void_p(d_strand_ptr or None), C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def hits_above_strand(self, d_bits_ptr: int, nq: int, d_offsets_ptr: int, d_index_ptr: int, d_strand_ptr: int, stream: int = 0) -> None:
+        """sa_ctx_hits_above_strand: the strand (uint8) of every entry of a CSR over rows [0, nq): row r owns entries
+        offsets[r] .. offsets[r + 1] (int64) of d_index / d_strand"""
+        if self._lib.sa_ctx_hits_above_strand(self._h, C.c_void_p(d_bits_ptr or None), _int32("nq", nq), C.c_void_p(d_offsets_ptr or None),
+                                              C.c_void_p(d_index_ptr or None), C.c_void_p(d_strand_ptr or None), C.c_void_p(stream)):
+            raise AlignError(_err())
 
     def cells(self, start: int = 0, count: Optional[int] = None) -> int:
         raise AlignError("a search context has no packed pair space")
@@ -1486,10 +1547,13 @@ def hip_search(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: O
 
 class HitList:
     """what hip_search_above returns: the hits of every query as a CSR -- offsets (M + 1, int64), and per hit index (ascending
-    within a query), value (the thresholded quantity) and score (the raw score), int32[E]; denominators (N + M) under a norm"""
+    within a query), value (the thresholded quantity) and score (the raw score), int32[E]; denominators (N + M) under a norm;
+    strand (uint8[E], 0 forward, 1 reverse) from hip_search_above_strands, None otherwise"""
 
-    def __init__(self, offsets: np.ndarray, index: np.ndarray, value: np.ndarray, score: np.ndarray, denominators: Optional[np.ndarray] = None):
+    def __init__(self, offsets: np.ndarray, index: np.ndarray, value: np.ndarray, score: np.ndarray, denominators: Optional[np.ndarray] = None,
+                 strand: Optional[np.ndarray] = None):
         self.offsets, self.index, self.value, self.score, self.denominators = offsets, index, value, score, denominators
+        self.strand = strand
 
     def __len__(self) -> int:
         return int(self.index.shape[0])
@@ -1503,15 +1567,31 @@ def hip_search_above(db: SequenceStore, queries: SequenceStore, scoring: Scoring
     """sa_hip_search_above: every database sequence whose value against a query is at least min_value, on the first device.  The
     value is the raw score, or with norm=Norm(source, rule) the normalised score, or with pid=PID_* percent identity, both in
     parts per million.  Any int32 threshold is valid.  Asking for both quantities is the library's to refuse."""
+    return _search_above(db, queries, scoring, min_value, norm, pid, False, None)
+
+
+def hip_search_above_strands(db: SequenceStore, queries: SequenceStore, scoring: Scoring, min_value: int, norm: Optional["Norm"] = None,
+                             pid: Optional[int] = None, comp: Optional[np.ndarray] = None) -> HitList:
+    """sa_hip_search_above_strands: hip_search_above over the values of both strands of DNA queries, folded on the device; the
+    HitList carries strand (0 forward, 1 reverse), and under a norm the N + 2 M denominators"""
+    return _search_above(db, queries, scoring, min_value, norm, pid, True, comp)
+
+
+def _search_above(db, queries, scoring, min_value, norm, pid, strands: bool, comp) -> HitList:
     lib = load_library()
     sc = scoring._as_c()
     t = _int32("min_value", min_value)
     cn = den = None
+    dens = db.num + (2 if strands else 1) * queries.num
     if norm is not None:
-        cn, den = norm._as_c(db.num + queries.num)
+        cn, den = norm._as_c(dens)
     cd = None if pid is None else C.c_int32(_denom(pid))
-    handle = lib.sa_hip_search_above(db._as_c(), queries._as_c(), C.byref(sc), t, None if cn is None else C.byref(cn),
-                                     None if cd is None else C.byref(cd))
+    quantity = (None if cn is None else C.byref(cn), None if cd is None else C.byref(cd))
+    if strands:
+        table = None if comp is None else _comp_table(comp)
+        handle = lib.sa_hip_search_above_strands(db._as_c(), queries._as_c(), C.byref(sc), None if table is None else table.ctypes.data, t, *quantity)
+    else:
+        handle = lib.sa_hip_search_above(db._as_c(), queries._as_c(), C.byref(sc), t, *quantity)
     if not handle:
         raise AlignError(_err())
     try:
@@ -1521,14 +1601,97 @@ def hip_search_above(db: SequenceStore, queries: SequenceStore, scoring: Scoring
         e = count.value
         offsets = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_int64)), (m.value + 1,)).copy()
         index, value, score = (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (e,)).copy() if e else np.zeros(0, np.int32) for p in ptrs)
+        strand = None
+        sp = lib.sa_hitlist_strand(handle)
+        if sp:
+            strand = np.ctypeslib.as_array(C.cast(sp, C.POINTER(C.c_uint8)), (e,)).copy() if e else np.zeros(0, np.uint8)
     finally:
         lib.sa_hitlist_destroy(handle)
-    return HitList(offsets, index, value, score, None if den is None else den[:db.num + queries.num])
+    return HitList(offsets, index, value, score, None if den is None else den[:dens], strand)
 
 
 def last_search_above_seconds() -> float:
     """device time of count + scan + fill in the last hip_search_above call, summed over its batches"""
     return float(load_library().sa_hip_last_search_above_seconds())
+
+
+STRAND_FORWARD, STRAND_REVERSE, STRAND_NONE = 0, 1, 255
+
+
+def strand_words(n_db: int) -> int:
+    """uint64 words per row of the strand bitmap: bit d & 63 of word d >> 6 is the strand of database sequence d"""
+    return (int(n_db) + 63) // 64
+
+
+def _comp_table(comp) -> np.ndarray:
+    table = np.ascontiguousarray(comp, dtype=np.uint8)
+    if table.shape != (128,):
+        raise AlignError(f"a complement table is 128 uint8, not {table.shape}")
+    return table
+
+
+def dna_complement() -> np.ndarray:
+    """sa_dna_complement: the IUPAC complement table, 128 uint8 indexed by the residue's byte; 0: no complement"""
+    comp = np.zeros(128, np.uint8)
+    load_library().sa_dna_complement(comp.ctypes.data)
+    return comp
+
+
+def reverse_complement(store: SequenceStore, comp: Optional[np.ndarray] = None, scoring: Optional[Scoring] = None) -> SequenceStore:
+    """sa_reverse_complement: a store of the same layout whose every sequence is reversed and mapped through `comp` (None:
+    dna_complement()).  Raises AlignError naming the sequence and the byte for a residue without a complement, or -- with a
+    scoring -- one whose complement the scoring's alphabet does not hold."""
+    table = None if comp is None else _comp_table(comp)
+    sc = None if scoring is None else scoring._as_c()
+    blob = np.zeros_like(store.blob)
+    if not load_library().sa_reverse_complement(store._as_c(), None if table is None else table.ctypes.data, None if sc is None else C.byref(sc),
+                                                blob.ctypes.data):
+        raise AlignError(_err())
+    return SequenceStore(blob=blob, meta=store.meta.copy(), num=store.num, max=store.max)
+
+
+def hip_search_strands(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: Optional[int] = None, rect: bool = False,
+                       norm: Optional["Norm"] = None, pid: Optional[int] = None, comp: Optional[np.ndarray] = None):
+    """sa_hip_search_strands: DNA queries against a database on both strands, folded on the first device.  With k: (index, value,
+    score, strand) -- three (M, k) int32 arrays and one (M, k) uint8 (0 forward, 1 reverse); row q lists the database sequences by
+    folded value descending, then index ascending.  With rect=True (rect, vrect, srect) follow: the folded (M, N) raw scores and
+    values and the (M, N) uint8 strands.  The value is the raw score, or with norm=Norm(source, rule) the normalised score (the
+    N + 2 M denominators are appended), or with pid=PID_* percent identity.  A cell is reverse iff its reverse value is larger."""
+    n, m = db.num, queries.num
+    if k is None and not rect:
+        raise AlignError("hip_search_strands: nothing asked for (k is None and rect is False)")
+    kk = 0 if k is None else _int32("k", k)
+    index = value = score = strand = out = vout = sout = None
+    if k is not None:
+        rows = max(m, 1) * max(min(kk, NEIGHBORS_MAX), 1)
+        index, value, score = (np.empty(rows, np.int32) for _ in range(3))
+        strand = np.empty(rows, np.uint8)
+    if rect:
+        out, vout = (np.empty((max(m, 0), max(n, 0)), np.int32) for _ in range(2))
+        sout = np.empty((max(m, 0), max(n, 0)), np.uint8)
+    ptr = [None if a is None else a.ctypes.data for a in (index, value, score, strand, out, vout, sout)]
+    table = None if comp is None else _comp_table(comp)
+    sc = scoring._as_c()
+    cn = den = None
+    if norm is not None:
+        cn, den = norm._as_c(n + 2 * m)
+    cd = None if pid is None else C.c_int32(_denom(pid))
+    if not load_library().sa_hip_search_strands(db._as_c(), queries._as_c(), C.byref(sc), None if table is None else table.ctypes.data, kk, *ptr,
+                                                None if cn is None else C.byref(cn), None if cd is None else C.byref(cd)):
+        raise AlignError(_err())
+    res = ()
+    if k is not None:
+        res += tuple(a[:m * kk].reshape(m, kk) for a in (index, value, score, strand))
+    if rect:
+        res += (out, vout, sout)
+    if den is not None:
+        res += (den[:n + 2 * m],)
+    return res
+
+
+def last_search_strands_seconds() -> float:
+    """device time of fold + strand take in the last hip_search_strands call, summed over its batches"""
+    return float(load_library().sa_hip_last_search_strands_seconds())
 
 
 def last_search_seconds() -> float:

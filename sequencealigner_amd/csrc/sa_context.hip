@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "sa_ctx.h"
+#include "sa_strands_core.h"
 
 bool sa_device_ready(int device)
 {
@@ -295,45 +296,68 @@ extern "C" sa_ctx *sa_ctx_create(int device, struct sa_input in, const struct sa
 
 /* The concatenated store of a search: db followed by queries, copied into one blob with fresh offsets (the inputs may
  * overlap, share a blob or lie anywhere); everything else is sa_ctx_create with the plans bounded to the rows below N. */
-static sa_ctx *ctx_create_search_impl(int device, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc)
+/* comp != nullptr: a strands context -- the store is db, the queries, and the reverse complements of the queries under comp */
+static sa_ctx *ctx_create_search_impl(const char *who, int device, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc,
+				      const uint8_t *comp = nullptr)
 {
 	if (!sc) {
-		sa_set_error("sa_ctx_create_search: null scoring");
+		sa_set_error("%s: null scoring", who);
 		return nullptr;
 	}
 	if (db.num < 1 || queries.num < 1) {
-		sa_set_error("sa_ctx_create_search: empty store (%d database sequences, %d queries; min: 1 each)", db.num, queries.num);
+		sa_set_error("%s: empty store (%d database sequences, %d queries; min: 1 each)", who, db.num, queries.num);
 		return nullptr;
 	}
 	if (!db.seqs || !db.meta || !queries.seqs || !queries.meta) {
-		sa_set_error("sa_ctx_create_search: null sequence store");
+		sa_set_error("%s: null sequence store", who);
 		return nullptr;
 	}
-	if ((int64_t)db.num + queries.num > INT32_MAX) {
-		sa_set_error("sa_ctx_create_search: %lld sequences exceed 32-bit sequence indices", (long long)db.num + queries.num);
+	const int64_t rows = (int64_t)queries.num * (comp ? 2 : 1);
+	if ((int64_t)db.num + rows > INT32_MAX) {
+		sa_set_error("%s: %lld sequences exceed 32-bit sequence indices", who, (long long)db.num + rows);
 		return nullptr;
 	}
-	const struct sa_input parts[2] = { db, queries };
-	int64_t bytes = 0;
-	for (const auto &st : parts)
-		for (int32_t k = 0; k < st.num; k++) {
-			const sa_meta m = st.meta[k];
+	std::vector<uint8_t> rc_blob;
+	struct sa_input rc = queries;
+	if (comp) { /* the reverse complements, in the layout of the queries' own blob: the same meta serves */
+		int64_t extent = 0;
+		for (int32_t k = 0; k < queries.num; k++) {
+			const sa_meta m = queries.meta[k];
 			if (m.len < 1 || m.off < 0) {
-				sa_set_error("%s sequence #%d has invalid offset/length (%d/%d)", &st == &parts[0] ? "Database" : "Query", k + 1, m.off, m.len);
+				sa_set_error("Query sequence #%d has invalid offset/length (%d/%d)", k + 1, m.off, m.len);
+				return nullptr;
+			}
+			extent = std::max<int64_t>(extent, (int64_t)m.off + m.len + 1);
+		}
+		if (!sa_strands_rc_checked(who, queries, comp, sc))
+			return nullptr;
+		rc_blob.resize((size_t)extent);
+		sa_strands_rc_write(queries, comp, rc_blob.data());
+		rc.seqs = rc_blob.data();
+	}
+	const struct sa_input parts[3] = { db, queries, rc };
+	const struct sa_input *const parts_end = parts + (comp ? 3 : 2);
+	int64_t bytes = 0;
+	for (const struct sa_input *st = parts; st != parts_end; st++)
+		for (int32_t k = 0; k < st->num; k++) {
+			const sa_meta m = st->meta[k];
+			if (m.len < 1 || m.off < 0) {
+				sa_set_error("%s sequence #%d has invalid offset/length (%d/%d)", st == parts ? "Database" : "Query", k + 1, m.off, m.len);
 				return nullptr;
 			}
 			bytes += (int64_t)m.len + 1;
 			if (bytes > INT32_MAX) {
-				sa_set_error("sa_ctx_create_search: the concatenated sequence store exceeds 2 GiB");
+				sa_set_error("%s: the concatenated sequence store exceeds 2 GiB", who);
 				return nullptr;
 			}
 		}
 	std::vector<uint8_t> blob((size_t)bytes);
-	std::vector<sa_meta> meta((size_t)db.num + (size_t)queries.num);
+	std::vector<sa_meta> meta((size_t)db.num + (size_t)rows);
 	int64_t at = 0;
 	size_t n = 0;
-	for (const auto &st : parts)
-		for (int32_t k = 0; k < st.num; k++) {
+	for (const struct sa_input *stp = parts; stp != parts_end; stp++)
+		for (int32_t k = 0; k < stp->num; k++) {
+			const struct sa_input &st = *stp;
 			const sa_meta m = st.meta[k];
 			memcpy(blob.data() + at, st.seqs + m.off, (size_t)m.len + 1); /* (the terminator too: validate_and_encode checks it) */
 			meta[n++] = sa_meta{ (int32_t)at, m.len };
@@ -342,14 +366,33 @@ static sa_ctx *ctx_create_search_impl(int device, struct sa_input db, struct sa_
 	struct sa_input cat{};
 	cat.seqs = blob.data();
 	cat.meta = meta.data();
-	cat.num = db.num + queries.num;
+	cat.num = db.num + (int32_t)rows;
 	cat.max = std::max(db.max, queries.max);
-	return ctx_create_impl(device, cat, sc, db.num);
+	sa_ctx *ctx = ctx_create_impl(device, cat, sc, db.num);
+	if (ctx)
+		ctx->search_strands = comp ? 2 : 1;
+	return ctx;
 }
 
 extern "C" sa_ctx *sa_ctx_create_search(int device, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc)
 {
-	return sa_guard("sa_ctx_create_search", (sa_ctx *)nullptr, [&] { return ctx_create_search_impl(device, db, queries, sc); });
+	return sa_guard("sa_ctx_create_search", (sa_ctx *)nullptr,
+			[&] { return ctx_create_search_impl("sa_ctx_create_search", device, db, queries, sc); });
+}
+
+extern "C" sa_ctx *sa_ctx_create_search_strands(int device, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc,
+						const uint8_t *comp)
+{
+	return sa_guard("sa_ctx_create_search_strands", (sa_ctx *)nullptr, [&] {
+		uint8_t dna[SA_LUT_SIZE];
+		sa_strands_complement_table(dna);
+		return ctx_create_search_impl("sa_ctx_create_search_strands", device, db, queries, sc, comp ? comp : dna);
+	});
+}
+
+extern "C" int32_t sa_ctx_search_strands(const sa_ctx *ctx)
+{
+	return sa_guard("sa_ctx_search_strands", (int32_t)0, [&] { return ctx ? ctx->search_strands : (int32_t)0; });
 }
 
 extern "C" int32_t sa_ctx_search_db(const sa_ctx *ctx)

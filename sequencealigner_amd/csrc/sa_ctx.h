@@ -34,6 +34,9 @@ struct sa_ctx {
 	/* search context (sa_ctx_create_search): the store is db followed by queries, num = search_db + search_queries, and every
 	 * plan is bounded to the rows below search_db (SaPlanInputs::row_end); both 0 on an ordinary context */
 	int32_t search_db = 0, search_queries = 0;
+	/* strands context (sa_ctx_create_search_strands): the query rows are the M queries followed by their M reverse complements,
+	 * search_queries = 2 M and search_strands = 2; 1 on a context of sa_ctx_create_search, 0 on an ordinary one */
+	int32_t search_strands = 0;
 	sa_scoring sc{};
 	SaEnv env;                     /* the switches, as they were when the context was created             */
 	std::vector<sa_meta> meta;     /* device-side (tight) layout: off[k] = sum_{i<k}(len_i+1)          */
@@ -241,5 +244,22 @@ int sa_normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, in
 			     hipStream_t s);
 /* what sa_hip_last_search_quantity_seconds reports from now on */
 void sa_search_quantity_last_set(double seconds);
+
+/* ---- what sa_strands.hip (both strands of DNA queries) takes from its neighbours ------------------------------------------------- */
+/* sa_strands.hip: can every residue of `in` be reverse-complemented under comp, and does sc->lut (sc may be NULL: not checked)
+ * take the complement?  false + sa_set_error naming the sequence, the position and the byte otherwise */
+bool sa_strands_rc_checked(const char *who, struct sa_input in, const uint8_t *comp, const struct sa_scoring *sc);
+/* sa_strands.hip: what sa_ctx_create_search_strands would refuse -- N + 2 M or the blob past int32, a residue that cannot be
+ * complemented -- said under the caller's name before a device is looked for (the stores are not null) */
+bool sa_strands_inputs_check(const char *who, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp);
+/* sa_strands.hip: the launches of sa_ctx_strand_fold and sa_ctx_hits_above_strand, their arguments checked by the caller; what
+ * sa_hip_last_search_strands_seconds reports from now on */
+int sa_strand_fold_launch(const int32_t *vf, const int32_t *vr, const int32_t *sf, const int32_t *sr, int32_t n_db, int32_t nq, int32_t *vbest,
+			  int32_t *sbest, uint64_t *bits, hipStream_t s);
+int sa_hits_above_strand_launch(const uint64_t *bits, int32_t n_db, int32_t nq, const int64_t *offsets, const int32_t *index, uint8_t *strand,
+				hipStream_t s);
+void sa_strands_last_set(double seconds);
+/* sa_search_quantity.hip: the launch of sa_ctx_hits_take, its arguments checked by the caller */
+int sa_hits_take_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, const int32_t *d_index, int32_t *d_out, hipStream_t s);
 
 #endif /* SA_CTX_H */

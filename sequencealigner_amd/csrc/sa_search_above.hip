@@ -28,6 +28,7 @@
 
 #include "sa_ctx.h"
 #include "sa_search_above_core.h"
+#include "sa_strands_core.h"
 
 struct sa_hitlist {
 	int32_t queries = 0;
@@ -36,10 +37,12 @@ struct sa_hitlist {
 	int32_t *index = nullptr;   /* count (room for one element when count == 0: never a null pointer for a valid result) */
 	int32_t *value = nullptr;
 	int32_t *score = nullptr; /* raw scores asked for: the same array as value */
+	uint8_t *strand = nullptr; /* sa_hip_search_above_strands only */
 	~sa_hitlist()
 	{
 		free(offsets);
 		free(index);
+		free(strand);
 		if (score != value)
 			free(score);
 		free(value);
@@ -228,11 +231,21 @@ bool grow(int32_t **p, size_t elems)
 	return true;
 }
 
-/* norm != NULL: normalised scores; pid_denom != NULL: percent identity; neither: raw scores */
-sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t min_value, const struct sa_norm *norm,
-		       const int32_t *pid_denom)
+bool grow8(uint8_t **p, size_t elems)
 {
-	const char *who = "sa_hip_search_above";
+	void *q = realloc(*p, std::max<size_t>(elems, 1));
+	if (!q)
+		return false;
+	*p = static_cast<uint8_t *>(q);
+	return true;
+}
+
+/* norm != NULL: normalised scores; pid_denom != NULL: percent identity; neither: raw scores.  strands: sa_hip_search_above_strands
+ * -- both strands of every query (the reverse complements under comp_in; NULL: sa_dna_complement's), folded before the count */
+sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t min_value, const struct sa_norm *norm,
+		       const int32_t *pid_denom, bool strands = false, const uint8_t *comp_in = nullptr)
+{
+	const char *who = strands ? "sa_hip_search_above_strands" : "sa_hip_search_above";
 	if (!sc) {
 		sa_set_error("%s: null argument", who);
 		return nullptr;
@@ -253,6 +266,11 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 		return nullptr;
 	if (pid_denom && !sa_identity_denom_check(who, *pid_denom))
 		return nullptr;
+	uint8_t dna[SA_LUT_SIZE];
+	sa_strands_complement_table(dna);
+	const uint8_t *comp = comp_in ? comp_in : dna;
+	if (strands && !sa_strands_inputs_check(who, db, queries, sc, comp))
+		return nullptr;
 	if (sa_hip_device_count() <= 0) {
 		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
 		return nullptr;
@@ -261,11 +279,11 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 		sa_ctx *c = nullptr;
 		~Ctx() { sa_ctx_destroy(c); }
 	} cx;
-	cx.c = sa_ctx_create_search(0, db, queries, sc);
+	cx.c = strands ? sa_ctx_create_search_strands(0, db, queries, sc, comp) : sa_ctx_create_search(0, db, queries, sc);
 	if (!cx.c)
 		return nullptr;
 	sa_ctx *ctx = cx.c;
-	const int64_t n = db.num, m = queries.num;
+	const int64_t n = db.num, m = queries.num, words = sa_strand_words(n);
 	const bool quantity = norm || pid_denom, aligned = !pid_denom;
 	/* Batch: as sa_hip_search_norm / _pid size it, with the scratch of this call in place of the hit lists.  Per query: the
 	 * range row (the longest, N + M - 1 elements; none under percent identity), a row of each rectangle (raw scores: the one),
@@ -275,7 +293,10 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 		return nullptr;
 	size_t free_b = 0, total_b = 0;
 	SA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b), return nullptr);
-	const int64_t per_query = (aligned ? 4 * (n + m) : 0) + (quantity ? 8 : 4) * n + 8;
+	/* Both strands: the range row is N + 2 M - 1 elements at most (the two halves use the one buffer in turn), every rectangle has a
+	 * reverse twin, and a row of the strand bitmap is added. */
+	const int64_t per_query = strands ? (aligned ? 4 * (n + 2 * m) : 0) + (quantity ? 16 : 8) * n + 8 * words + 8
+					  : (aligned ? 4 * (n + m) : 0) + (quantity ? 8 : 4) * n + 8;
 	int64_t budget = (int64_t)(free_b - free_b / 4);
 	if (ctx->env.search_batch_bytes > 0)
 		budget = std::min<int64_t>(budget, ctx->env.search_batch_bytes);
@@ -284,12 +305,16 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
 		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
 		if (aligned)
-			range_bytes = std::max(range_bytes, sa_search_scratch_bytes(ctx, (int32_t)q0, nq));
+			range_bytes = std::max(range_bytes, sa_search_scratch_bytes(ctx, (int32_t)(strands ? m + q0 : q0), nq));
 		scratch_bytes = std::max(scratch_bytes, sizeof(int64_t) * (size_t)sa_above_scratch_elems((int32_t)n, nq));
 	}
-	DevBuf d_range, d_rect, d_vrect, d_den, d_scratch, d_offsets, d_out;
+	DevBuf d_range, d_rect, d_vrect, d_den, d_scratch, d_offsets, d_out, d_rrev, d_vrev, d_bits;
+	const size_t dens = (size_t)(strands ? n + 2 * m : n + m);
 	if ((aligned && !d_range.alloc(who, range_bytes, "the packed range of a query batch")) ||
-	    (norm && !d_den.alloc(who, sizeof(int32_t) * (size_t)(n + m), "the denominators")) ||
+	    (norm && !d_den.alloc(who, sizeof(int32_t) * dens, "the denominators")) ||
+	    (strands && (!d_rrev.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the reverse rectangle of a query batch") ||
+			 (quantity && !d_vrev.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the reverse value rectangle of a query batch")) ||
+			 !d_bits.alloc(who, sizeof(uint64_t) * (size_t)nqb * (size_t)words, "the strand bitmap of a query batch"))) ||
 	    !d_rect.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the rectangle of a query batch") ||
 	    (quantity && !d_vrect.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the value rectangle of a query batch")) ||
 	    !d_scratch.alloc(who, scratch_bytes, "the segment counts") ||
@@ -298,6 +323,9 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 	struct Sync { /* the stream is drained before the buffers above are freed (declared after them) */
 		hipStream_t s = nullptr;
 		hipEvent_t ev[7] = {}; /* start, range aligned, rows moved, values done, counted + scanned, fill begins, filled */
+		/* both strands: values done (the fold begins; ev[3] is then "folded"), reverse range aligned, forward rows moved, strand take
+		 * begins, strands taken */
+		hipEvent_t evs[5] = {};
 		~Sync()
 		{
 			if (s) {
@@ -307,11 +335,18 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 			for (hipEvent_t e : ev)
 				if (e)
 					(void)hipEventDestroy(e);
+			for (hipEvent_t e : evs)
+				if (e)
+					(void)hipEventDestroy(e);
 		}
 	} sy;
 	SA_HIP_CHECK(hipStreamCreateWithFlags(&sy.s, hipStreamNonBlocking), return nullptr);
 	for (hipEvent_t &e : sy.ev)
 		SA_HIP_CHECK(hipEventCreate(&e), return nullptr);
+	if (strands) {
+		for (hipEvent_t &e : sy.evs)
+			SA_HIP_CHECK(hipEventCreate(&e), return nullptr);
+	}
 	struct Res {
 		sa_hitlist *h = nullptr;
 		~Res() { delete h; }
@@ -326,18 +361,25 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 	}
 	h->offsets[0] = 0;
 	const size_t arrays = quantity ? 3 : 2; /* device: index, value and, under a quantity, score */
-	std::vector<int32_t> h_den(norm && norm->denominators ? (size_t)(n + m) : 0);
+	std::vector<int32_t> h_den(norm && norm->denominators ? dens : 0);
 	std::vector<int64_t> h_off((size_t)nqb + 1);
-	double t_align = 0.0, t_gather = 0.0, t_quantity = 0.0, t_above = 0.0;
+	double t_align = 0.0, t_gather = 0.0, t_quantity = 0.0, t_above = 0.0, t_strands = 0.0;
 	int32_t batches = 0;
 	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
 		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
 		int32_t *const dr = static_cast<int32_t *>(d_rect.p), *const dv = quantity ? static_cast<int32_t *>(d_vrect.p) : dr;
 		int64_t *const dsc = static_cast<int64_t *>(d_scratch.p), *const doff = static_cast<int64_t *>(d_offsets.p);
+		int32_t *const drr = static_cast<int32_t *>(d_rrev.p), *const dvr = quantity ? static_cast<int32_t *>(d_vrev.p) : drr;
+		uint64_t *const dbits = static_cast<uint64_t *>(d_bits.p);
 		SA_HIP_CHECK(hipEventRecord(sy.ev[0], sy.s), return nullptr);
 		if (aligned) {
 			if (sa_search_range_launch(ctx, (int32_t)q0, nq, dr, d_range.p, sy.s, sy.ev[1]) != 0)
 				return nullptr;
+			if (strands) { /* the rows M + q0 .. through the same buffer of the range */
+				SA_HIP_CHECK(hipEventRecord(sy.evs[2], sy.s), return nullptr);
+				if (sa_search_range_launch(ctx, (int32_t)(m + q0), nq, drr, d_range.p, sy.s, sy.evs[1]) != 0)
+					return nullptr;
+			}
 			SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return nullptr);
 			if (norm) {
 				if (q0 == 0) { /* once per call */
@@ -345,12 +387,25 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 				}
 				if (sa_normalize_rect_launch(dr, (int32_t)n, (int32_t)q0, nq, static_cast<const int32_t *>(d_den.p), norm->rule, dv, sy.s) != 0)
 					return nullptr;
+				if (strands && sa_normalize_rect_launch(drr, (int32_t)n, (int32_t)(m + q0), nq, static_cast<const int32_t *>(d_den.p), norm->rule,
+									 dvr, sy.s) != 0)
+					return nullptr;
 			}
 		} else {
-			const struct sa_identity_out out = { dr, nullptr, nullptr, dv, *pid_denom };
+			const struct sa_identity_out out = { dr, nullptr, nullptr, dv, *pid_denom }, rev = { drr, nullptr, nullptr, dvr, *pid_denom };
 			SA_HIP_CHECK(hipEventRecord(sy.ev[1], sy.s), return nullptr);
+			if (strands) {
+				SA_HIP_CHECK(hipEventRecord(sy.evs[2], sy.s), return nullptr);
+				SA_HIP_CHECK(hipEventRecord(sy.evs[1], sy.s), return nullptr);
+			}
 			SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return nullptr);
-			if (!sa_identity_rect(who, ctx, (int32_t)q0, nq, &out, sy.s))
+			if (!sa_identity_rect(who, ctx, (int32_t)q0, nq, &out, sy.s) || (strands && !sa_identity_rect(who, ctx, (int32_t)(m + q0), nq, &rev, sy.s)))
+				return nullptr;
+		}
+		if (strands) { /* in place: the folded values replace the forward values, the folded raw scores the forward raw scores */
+			SA_HIP_CHECK(hipEventRecord(sy.evs[0], sy.s), return nullptr);
+			if (sa_strand_fold_launch(dv, dvr, quantity ? dr : nullptr, quantity ? drr : nullptr, (int32_t)n, nq, dv, quantity ? dr : nullptr, dbits,
+						  sy.s) != 0)
 				return nullptr;
 		}
 		SA_HIP_CHECK(hipEventRecord(sy.ev[3], sy.s), return nullptr);
@@ -365,22 +420,23 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 		const int64_t e = h_off[(size_t)nq], at = h->count;
 		const size_t elems = (size_t)e, total = (size_t)(at + e);
 		const double gib = (double)elems * 4.0 * (double)arrays / (double)(1 << 30);
-		float ms_fill = 0.f;
+		float ms_fill = 0.f, ms_take = 0.f;
 		if (elems) {
-			if (d_out.bytes < sizeof(int32_t) * arrays * elems) { /* exact; the largest so far is kept */
+			const size_t out_bytes = sizeof(int32_t) * arrays * elems + (strands ? elems : 0); /* (the strands: one byte per hit, last) */
+			if (d_out.bytes < out_bytes) { /* exact; the largest so far is kept */
 				(void)hipFree(d_out.p);
 				d_out.p = nullptr;
 				d_out.bytes = 0;
-				if (hipMalloc(&d_out.p, sizeof(int32_t) * arrays * elems) != hipSuccess) {
+				if (hipMalloc(&d_out.p, out_bytes) != hipSuccess) {
 					(void)hipGetLastError();
 					d_out.p = nullptr;
 					sa_set_error("%s: the %lld hits of queries [%lld,+%d) (%.2f GiB) do not fit the device's memory", who, (long long)e,
 						     (long long)q0, nq, gib);
 					return nullptr;
 				}
-				d_out.bytes = sizeof(int32_t) * arrays * elems;
+				d_out.bytes = out_bytes;
 			}
-			if (!grow(&h->index, total) || !grow(&h->value, total) || (quantity && !grow(&h->score, total))) {
+			if (!grow(&h->index, total) || !grow(&h->value, total) || (quantity && !grow(&h->score, total)) || (strands && !grow8(&h->strand, total))) {
 				sa_set_error("%s: the %lld hits of queries [%lld,+%d) (%.2f GiB, %lld hits before them) do not fit the host's memory", who,
 					     (long long)e, (long long)q0, nq, gib, (long long)at);
 				return nullptr;
@@ -390,6 +446,14 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 			if (fill_launch(dv, dr, (int32_t)n, nq, min_value, doff, dsc, di, dval, dscore, sy.s) != 0)
 				return nullptr;
 			SA_HIP_CHECK(hipEventRecord(sy.ev[6], sy.s), return nullptr);
+			if (strands) {
+				uint8_t *const dstrand = reinterpret_cast<uint8_t *>(di + arrays * elems);
+				SA_HIP_CHECK(hipEventRecord(sy.evs[3], sy.s), return nullptr);
+				if (sa_hits_above_strand_launch(dbits, (int32_t)n, nq, doff, di, dstrand, sy.s) != 0)
+					return nullptr;
+				SA_HIP_CHECK(hipEventRecord(sy.evs[4], sy.s), return nullptr);
+				SA_HIP_CHECK(hipMemcpyAsync(h->strand + at, dstrand, elems, hipMemcpyDeviceToHost, sy.s), return nullptr);
+			}
 			SA_HIP_CHECK(hipMemcpyAsync(h->index + at, di, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return nullptr);
 			SA_HIP_CHECK(hipMemcpyAsync(h->value + at, dval, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return nullptr);
 			if (quantity) {
@@ -397,6 +461,9 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 			}
 			SA_HIP_CHECK(hipStreamSynchronize(sy.s), return nullptr); /* (the next batch reuses the buffers) */
 			SA_HIP_CHECK(hipEventElapsedTime(&ms_fill, sy.ev[5], sy.ev[6]), return nullptr);
+			if (strands) {
+				SA_HIP_CHECK(hipEventElapsedTime(&ms_take, sy.evs[3], sy.evs[4]), return nullptr);
+			}
 		}
 		for (int32_t r = 0; r < nq; r++)
 			h->offsets[q0 + r + 1] = at + h_off[(size_t)r + 1];
@@ -404,11 +471,30 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 		float ms[4] = {};
 		for (int t = 0; t < 4; t++)
 			SA_HIP_CHECK(hipEventElapsedTime(&ms[t], sy.ev[t], sy.ev[t + 1]), return nullptr);
+		if (strands) { /* the reverse half of alignment and gather; the fold is no part of the quantity */
+			float a = 0.f, g0 = 0.f, g1 = 0.f, q = 0.f, f = 0.f;
+			SA_HIP_CHECK(hipEventElapsedTime(&g0, sy.ev[1], sy.evs[2]), return nullptr);
+			SA_HIP_CHECK(hipEventElapsedTime(&a, sy.evs[2], sy.evs[1]), return nullptr);
+			SA_HIP_CHECK(hipEventElapsedTime(&g1, sy.evs[1], sy.ev[2]), return nullptr);
+			SA_HIP_CHECK(hipEventElapsedTime(&q, sy.ev[2], sy.evs[0]), return nullptr);
+			SA_HIP_CHECK(hipEventElapsedTime(&f, sy.evs[0], sy.ev[3]), return nullptr);
+			ms[0] += a;
+			ms[1] = g0 + g1;
+			ms[2] = q;
+			t_strands += ((double)f + (double)ms_take) * 1e-3;
+		}
 		t_align += (double)ms[0] * 1e-3;
 		t_gather += (double)ms[1] * 1e-3;
 		t_quantity += (double)ms[2] * 1e-3;
 		t_above += ((double)ms[3] + (double)ms_fill) * 1e-3;
 		batches++;
+	}
+	if (strands) {
+		if (!h->strand && !grow8(&h->strand, 0)) { /* (never a null pointer for a valid result) */
+			sa_set_error("%s: out of host memory", who);
+			return nullptr;
+		}
+		sa_strands_last_set(t_strands);
 	}
 	if (!quantity)
 		h->score = h->value; /* raw scores: value == score, one array */
@@ -502,6 +588,18 @@ extern "C" const int32_t *sa_hitlist_value(const sa_hitlist *h)
 extern "C" const int32_t *sa_hitlist_score(const sa_hitlist *h)
 {
 	return sa_guard("sa_hitlist_score", (const int32_t *)nullptr, [&] { return h ? (const int32_t *)h->score : nullptr; });
+}
+
+extern "C" sa_hitlist *sa_hip_search_above_strands(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp,
+						   int32_t min_value, const struct sa_norm *norm, const int32_t *pid_denom)
+{
+	return sa_guard("sa_hip_search_above_strands", (sa_hitlist *)nullptr,
+			[&] { return above_impl(db, queries, sc, min_value, norm, pid_denom, true, comp); });
+}
+
+extern "C" const uint8_t *sa_hitlist_strand(const sa_hitlist *h)
+{
+	return sa_guard("sa_hitlist_strand", (const uint8_t *)nullptr, [&] { return h ? (const uint8_t *)h->strand : nullptr; });
 }
 
 extern "C" void sa_hitlist_destroy(sa_hitlist *h)

@@ -315,6 +315,11 @@ int sa_normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, in
 	return normalize_rect_launch(d_rect, n_db, q0, nq, d_den, rule, d_out, s);
 }
 void sa_search_quantity_last_set(double seconds) { g_last_quantity_seconds.store(seconds); }
+/* for sa_strands.hip (sa_ctx.h) */
+int sa_hits_take_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, const int32_t *d_index, int32_t *d_out, hipStream_t s)
+{
+	return take_launch(d_rect, n_db, nq, k, d_index, d_out, s);
+}
 
 extern "C" int sa_ctx_normalize_rect(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, int32_t q0, const int32_t *d_den, int32_t rule,
 				     int32_t *d_out, void *stream)
