@@ -1082,6 +1082,57 @@ int sa_host_write_search_strands(const char *path, const struct sa_host_store *d
 	return rc ? rc : write_side_sets(path, NULL, 0, false, sets, 4);
 }
 
+/* --query --fit (include/seqalign_hip.h: sa_hip_search_fit): where every hit's query sits in its database sequence, added to the
+ * finished file of sa_host_write_search: /hit_db_begin and /hit_db_end (M x k I32LE: the half-open span [begin, end) of database
+ * sequence index[q][t]) and /search_ends (1 I32LE: 1 = the database's ends are free).  Everything that can be refused is refused
+ * while the file is open read-only: 0 <= begin <= end <= the length of the hit; the file holds /hit_indices of M x k and none of
+ * the datasets yet. */
+int sa_host_write_search_fit(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
+			     const int32_t *index, const int32_t *db_begin, const int32_t *db_end)
+{
+	if (!path || !db || !queries || !index || !db_begin || !db_end)
+		return fail("Fit data missing");
+	if (db->in.num < 1 || queries->in.num < 1)
+		return fail("A search needs a database and queries");
+	const size_t n = (size_t)db->in.num, m = (size_t)queries->in.num;
+	if (k < 1 || k > SA_HIP_NEIGHBORS_MAX || (size_t)k > n)
+		return fail("Hit count must be between 1 and %d and at most the number of database sequences", SA_HIP_NEIGHBORS_MAX);
+	for (size_t t = 0; t < m * (size_t)k; t++) {
+		if (index[t] < 0 || (size_t)index[t] >= n)
+			return fail("Hit index %d of query %zu outside the %zu database sequences", index[t], t / (size_t)k, n);
+		const int32_t len = db->in.meta[index[t]].len;
+		if (db_begin[t] < 0 || db_begin[t] > db_end[t] || db_end[t] > len)
+			return fail("Span [%d, %d) of hit %zu of query %zu is outside its database sequence of %d residues", db_begin[t], db_end[t],
+				    t % (size_t)k, t / (size_t)k, len);
+	}
+	const int32_t ends = 1;
+	const struct side_set sets[3] = { { "/hit_db_begin", 2, { m, (hsize_t)k }, SIDE_I32, db_begin, false },
+					  { "/hit_db_end", 2, { m, (hsize_t)k }, SIDE_I32, db_end, false },
+					  { "/search_ends", 1, { 1 }, SIDE_I32, &ends, false } };
+	hid_t file;
+	H5E_BEGIN_TRY { file = H5Fopen(path, H5F_ACC_RDONLY, H5P_DEFAULT); } H5E_END_TRY
+	if (file < 0)
+		return fail("Failed to open HDF5 file: %s", path);
+	int rc = 0;
+	hsize_t dims[2] = { 0, 0 };
+	hid_t set = -1, space = -1;
+	H5E_BEGIN_TRY {
+		set = H5Lexists(file, "/hit_indices", H5P_DEFAULT) > 0 ? H5Dopen2(file, "/hit_indices", H5P_DEFAULT) : -1;
+		space = set >= 0 ? H5Dget_space(set) : -1;
+	} H5E_END_TRY
+	if (space < 0 || H5Sget_simple_extent_ndims(space) != 2 || H5Sget_simple_extent_dims(space, dims, NULL) != 2 || dims[0] != m || dims[1] != (hsize_t)k)
+		rc = fail("%s holds no /hit_indices of %zu x %d hits: the spans belong to the file of a search", path, m, k);
+	if (space >= 0)
+		H5Sclose(space);
+	if (set >= 0)
+		H5Dclose(set);
+	for (int d = 0; d < 3 && !rc; d++)
+		if (H5Lexists(file, sets[d].name, H5P_DEFAULT) > 0)
+			rc = fail("%s already holds %s", path, sets[d].name);
+	H5Fclose(file);
+	return rc ? rc : write_side_sets(path, NULL, 0, false, sets, 3);
+}
+
 /* The score graph as CSR (include/seqalign_hip.h: sa_hip_edges): /edge_offsets N + 1 I64LE, /edge_indices and /edge_scores
  * E = offsets[N] I32LE each (extent 0 when there is no edge).  create: as write_side_sets has it.  The arrays are checked before
  * anything is opened: offsets[0] == 0, offsets non-decreasing, every index in [0, N). */

@@ -124,6 +124,12 @@ int sa_host_write_search_list(const char *path, const struct sa_host_store *db, 
 int sa_host_write_search_strands(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
 				 const uint8_t *hit_strands, int64_t count, const uint8_t *list_strands, const uint8_t *rect_strands,
 				 const int32_t *reverse_denominators);
+/* --query --fit: where the query of every hit sits in its database sequence (sa_hip_search_fit), added to the finished file of
+ * sa_host_write_search: /hit_db_begin and /hit_db_end (M x k I32LE, the half-open span of database sequence index[q][t]) and
+ * /search_ends (1 I32LE: 1 = the database's ends are free).  A span outside its database sequence, a file without /hit_indices of
+ * M x k or one that holds a dataset already give an error and leave the file as it was. */
+int sa_host_write_search_fit(const char *path, const struct sa_host_store *db, const struct sa_host_store *queries, int32_t k,
+			     const int32_t *index, const int32_t *db_begin, const int32_t *db_end);
 /* --min-score: /edge_offsets (N + 1 I64LE), /edge_indices and /edge_scores (E = offsets[N] I32LE each; extent 0 when E = 0),
  * the CSR arrays of sa_hip_edges / sa_zjob_edges.  `create` as in sa_host_write_neighbors: 0 adds the three datasets to the
  * finished file at `path`, 1 writes a new file with /sequences and the three (--edges-only).  offsets[0] != 0, decreasing

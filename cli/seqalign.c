@@ -40,6 +40,9 @@
  *             --strands forward|both  (with --query, both: every query also reverse-complemented, the two searches folded on the device
  *             by the larger value: /hit_strands or /hitlist_strands beside the hits of the folded search, with --query-scores
  *             /query_strands; forward, the default, writes what a run without the option writes)
+ *             --fit  (with --query and -k, NW or Gotoh: every query fitted INSIDE the database sequence -- the whole query, the
+ *             database's overhang free: /hit_scores are the fit scores, /hit_db_begin and /hit_db_end the span of the database sequence
+ *             the query sits in, /search_ends 1; --alignments the fitted alignments)
  * Flow (main, one function per phase): options -> banner -> load + filter -> output plan -> the first pass (tile job | one selection only |
  * host matrix | the search) -> per selection, in the order of the file: its second pass where the first left it unanswered, then its
  * datasets (a search: its alignments, then its one file) -> -B report.
@@ -161,6 +164,8 @@ struct options {
 	/* --strands forward|both: with --query, both: every query is searched as written and reverse-complemented, the two folded on the
 	 * device (include/seqalign_hip.h: sa_hip_search_strands); forward, the default: the output of a run without the option */
 	bool strands_both;
+	/* --fit: with --query and -k: the queries fitted inside the database sequences (include/seqalign_hip.h: sa_hip_search_fit) */
+	bool fit;
 };
 
 static void usage(const char *argv0)
@@ -295,6 +300,16 @@ static void usage(const char *argv0)
 	       "                           a reverse hit a = the REVERSE COMPLEMENT of the query (position p there is position\n"
 	       "                           length - 1 - p of the query as given).  /query_sequences stays the queries as given; -f\n"
 	       "                           filters the database only.  Needs a nucleotide matrix and queries of the alphabet above\n"
+	       "      --fit                With --query and -k, -a nw or ga: fit every query INSIDE the database sequence -- the whole\n"
+	       "                           query is aligned, the residues of the database sequence before and behind it cost nothing\n"
+	       "                           (semi-global, \"glocal\": a read inside a long entry, a domain inside a protein).\n"
+	       "                           /hit_scores are then the fit scores; /hit_db_begin and /hit_db_end (M x K) give the\n"
+	       "                           half-open span of the database sequence the query sits in, /search_ends (1) is 1.\n"
+	       "                           --hits-by score | identity-* keeps its datasets (the identity is that of the fitted\n"
+	       "                           alignment); --query-scores writes the fit scores (and /query_values); --alignments writes\n"
+	       "                           the fitted alignments (a = the query, always whole: a_begin 0, a_end its length; b_begin\n"
+	       "                           and b_end the span).  Not together with -a sw (local already), --hits-min, --strands both\n"
+	       "                           or the normalised kinds of --hits-by\n"
 	       "      --column N           DSV: 1-based sequence column when no header names it\n"
 	       "      --no-header          DSV: with --column, the first row is data\n"
 	       "  -h, --help               Display this help message\n",
@@ -357,7 +372,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 		     { "linkage-only", 9, false }, { "min-quantile", 10, true }, { "clusters-quantile", 11, true },
 		     { "quantiles", 12, true }, { "normalize", 13, true }, { "identity", 14, true },
 		     { "linkage-method", 15, true }, { "query", 16, true }, { "query-scores", 17, false }, { "hits-by", 18, true },
-		     { "hits-min", 19, true }, { "strands", 20, true },
+		     { "hits-min", 19, true }, { "strands", 20, true }, { "fit", 21, false },
 	     { NULL, 0, false } };
 	*o = (struct options){ .gap_pen = -1, .gap_open = -1, .gap_ext = -1, .dsv_column = -1, .dsv_has_header = 1, .min_q = -1, .clusters_q = -1 };
 	for (int k = 1; k < argc; k++) {
@@ -584,6 +599,7 @@ static int parse_args(int argc, char **argv, struct options *o)
 				}
 				o->strands_both = !strcmp(val, "both");
 				break;
+			case 21: o->fit = true; break;
 			case 16: o->query = val; break;
 			case 17: o->query_scores = true; break;
 			case 18: {
@@ -724,7 +740,7 @@ struct run {
 	struct { int32_t *index, *score; bool done, second_pass; double seconds; } nb;
 	/* --query: the queries, the hits (M x K), with --query-scores the rectangle (M x N), with --alignments the M x K records */
 	struct sa_host_store queries;
-	struct { int32_t *index, *score, *rect, *value, *vrect; sa_alns *alns; double hits_seconds, gather_seconds; int32_t batches; } sr;
+	struct { int32_t *index, *score, *rect, *value, *vrect, *db_begin, *db_end; sa_alns *alns; double hits_seconds, gather_seconds; int32_t batches; } sr;
 	/* --query --hits-min: the hits of every query as CSR (E of them), in arrays the library owns */
 	struct { sa_hitlist *list; long long count; double rect_seconds; } ab;
 	/* --query --strands both: the strand of every hit (M x K) and, with --query-scores, of every cell (M x N); the device time of
@@ -906,6 +922,15 @@ static int set_up(int argc, char **argv, struct run *r)
 			  "above T, not both"), false);
 	if (ok && o->strands_both && !o->query)
 		ok = (err("Option --strands both requires --query: it searches every query on both strands"), false);
+	if (ok && o->fit && !o->query)
+		ok = (err("Option --fit requires --query: it fits the queries of a search inside the database sequences"), false);
+	if (ok && o->fit && o->has_hits_min)
+		ok = (err("Options --fit and --hits-min conflict: the fitted search writes the K best hits of every query (-k)"), false);
+	if (ok && o->fit && o->strands_both)
+		ok = (err("Options --fit and --strands both conflict: the fitted search runs on the queries as written"), false);
+	if (ok && o->fit && o->hits_by && o->hits_kind == 1)
+		ok = (err("Options --fit and --hits-by %s conflict: the fitted hits are ranked by score or by one of identity-columns, identity-shorter, "
+			  "identity-longer, identity-mean", o->hits_name), false);
 	if (ok && o->query && !o->neighbors && !o->has_hits_min)
 		ok = (err("Option --query requires -k, --neighbors (the number of hits per query) or --hits-min (the threshold of the hits)"), false);
 	if (ok && o->query && query_conflict(o))
@@ -948,6 +973,8 @@ static int set_up(int argc, char **argv, struct run *r)
 			  "matrix", o->matrix, o->matrix), false);
 	if (ok && (sc->method = sa_method_parse(o->align)) < 0)
 		ok = (err("Invalid alignment method"), false);
+	if (ok && o->fit && sc->method == SA_METHOD_SW)
+		ok = (err("Options --fit and -a %s conflict: Smith-Waterman is local already; fit the queries with nw or ga", o->align), false);
 	if (ok && o->gap_pen >= 0 && (o->gap_open >= 0 || o->gap_ext >= 0))
 		ok = (err("Options -p and -s/-e conflict"), false);
 	if (ok && sa_method_gap_kind(sc->method) == SA_GAP_LINEAR) {
@@ -1018,6 +1045,8 @@ static void banner(const struct run *r)
 			info("Hits ranked by %s, in parts per million (the hit scores stay raw)", o->hits_name);
 	} else if (o->neighbors)
 		info("Neighbors: %d per sequence%s", o->neighbors, o->neighbors_only ? " (no similarity matrix)" : "");
+	if (o->fit)
+		info("Fit: every query whole, inside the database sequence (the database's overhang is free)");
 	if (o->strands_both)
 		info("Strands: both -- every query as written and reverse-complemented, folded on the device (the forward strand on a tie)");
 	if (o->min_q >= 0)
@@ -1089,6 +1118,12 @@ static bool load_queries(struct run *r)
 		r->sr.rect = malloc(sizeof(int32_t) * m * r->n);
 	if ((!o->has_hits_min && (!r->sr.index || !r->sr.score)) || (o->query_scores && !r->sr.rect))
 		return failed("Out of memory allocating search results");
+	if (o->fit) {
+		r->sr.db_begin = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+		r->sr.db_end = malloc(sizeof(int32_t) * m * (size_t)o->neighbors);
+		if (!r->sr.db_begin || !r->sr.db_end)
+			return failed("Out of memory allocating search results");
+	}
 	/* --hits-by: the quantity of the search, carried as the quantity of every selection is (kind 0: the scores, q stays empty) */
 	if (o->hits_by && o->hits_kind) {
 		r->norm_spec = (struct sa_norm){ o->hits_source, o->hits_rule, NULL };
@@ -1351,6 +1386,10 @@ static bool run_search(struct run *r)
 		int64_t count = 0;
 		(void)sa_hitlist_index(r->ab.list, &count);
 		r->ab.count = (long long)count;
+	} else if (o->fit) {
+		if (!sa_hip_search_fit(r->store.in, r->queries.in, &r->sc, o->neighbors, r->q.pid ? *r->q.pid : -1, r->sr.index, r->sr.value, r->sr.score,
+				       r->sr.db_begin, r->sr.db_end, r->sr.rect, r->sr.vrect))
+			return failed(sa_last_error());
 	} else if (o->strands_both) {
 		if (!sa_hip_search_strands(r->store.in, r->queries.in, &r->sc, NULL, o->neighbors, r->sr.index, r->sr.value, r->sr.score, r->st.hit,
 					   r->sr.rect, r->sr.vrect, r->st.rect, r->q.norm, r->q.pid))
@@ -1362,7 +1401,7 @@ static bool run_search(struct run *r)
 		return failed(sa_last_error());
 	const double call = now() - t0;
 	stamp("sa_hip_search returned");
-	r->t_quantity = sa_hip_last_search_quantity_seconds();
+	r->t_quantity = o->fit ? 0.0 : sa_hip_last_search_quantity_seconds(); /* (--fit: the one sweep delivers score and identity) */
 	r->st.seconds = o->strands_both ? sa_hip_last_search_strands_seconds() : 0.0;
 	finish_progress(r);
 	sa_hip_last_search_breakdown(&r->t_align, &r->sr.gather_seconds, &r->sr.hits_seconds, &r->sr.batches);
@@ -1405,11 +1444,11 @@ static bool trace_hits(struct run *r)
 			for (int64_t t = offsets[q]; t < offsets[q + 1]; t++)
 				pa[t] = (int32_t)r->n + q + (strand && strand[t] ? m : 0);
 	} else
-		for (size_t t = 0; t < np; t++)
-			pa[t] = (int32_t)(r->n + t / (size_t)o->neighbors) + (strand && strand[t] ? m : 0);
+		for (size_t t = 0; t < np; t++) /* (--fit: sa_ctx_fit_alignments takes the query itself, not its place in the store) */
+			pa[t] = (int32_t)((o->fit ? 0 : r->n) + t / (size_t)o->neighbors) + (strand && strand[t] ? m : 0);
 	sa_ctx *ctx = o->strands_both ? sa_ctx_create_search_strands(0, r->store.in, r->queries.in, &r->sc, NULL)
 				      : sa_ctx_create_search(0, r->store.in, r->queries.in, &r->sc);
-	r->sr.alns = ctx ? sa_ctx_alignments(ctx, pa, index, (int64_t)np) : NULL;
+	r->sr.alns = !ctx ? NULL : o->fit ? sa_ctx_fit_alignments(ctx, pa, index, (int64_t)np) : sa_ctx_alignments(ctx, pa, index, (int64_t)np);
 	free(pa);
 	if (ctx)
 		sa_ctx_destroy(ctx);
@@ -1435,6 +1474,10 @@ static bool write_search(struct run *r)
 								 o->has_hits_min ? (int64_t)r->ab.count : -1, o->has_hits_min ? sa_hitlist_strand(r->ab.list) : NULL,
 								 r->st.rect, r->q.norm ? r->q.norm->denominators + r->n + r->queries.in.num : NULL),
 				 "strands written");
+	if (o->fit) /* the file of a search, then where the queries sit */
+		return write_search_plain(r, cigar, runs) &&
+		       WRITE_OUT(r, sa_host_write_search_fit(o->output, &r->store, &r->queries, o->neighbors, r->sr.index, r->sr.db_begin, r->sr.db_end),
+				 "fit spans written");
 	return write_search_plain(r, cigar, runs);
 }
 
@@ -1719,6 +1762,8 @@ static void release(struct run *r)
 	free(r->sr.rect);
 	free(r->sr.value);
 	free(r->sr.vrect);
+	free(r->sr.db_begin);
+	free(r->sr.db_end);
 	free(r->st.hit);
 	free(r->st.rect);
 	sa_host_store_free(&r->queries);

@@ -827,6 +827,71 @@ sa_linkage *sa_hip_linkage_with_ranks_pid(struct sa_input in, const struct sa_sc
 /* device time (seconds) of the identity sweep in the last successful sa_hip_identity / *_pid / sa_zjob_identity call */
 double sa_hip_last_identity_seconds(void);
 
+/* ---- queries fitted inside database sequences: the whole query, the database's overhang free ----------------------------------
+ * No reference counterpart.  What a search asks -- a read against a database entry, a domain against a full-length protein -- is
+ * the WHOLE query placed anywhere inside the database sequence: "fit", "glocal" or semi-global alignment.  NW and Gotoh charge the
+ * query for every database residue that overhangs it; SW may drop the ends of the query.  Here the query's ends are fixed and the
+ * database's are free, and the call also says where in the database sequence the query sits.
+ * Orientation: canonical, as everywhere on a search context.  The database sequence d (length m) is the row sequence, r = 0 .. m;
+ *   the query (length n) is the column sequence, c = 0 .. n.  The substitution table is indexed as struct sa_scoring documents for
+ *   the method.
+ * Methods: SA_METHOD_NW (linear gap g) and SA_METHOD_GA (open o, extend e).  SA_METHOD_SW is refused: it is already local.
+ * Tables: the reference's recurrences for the method, unchanged (nw.c:29-35, ga.c:46-63).  Row 0 is the method's: M[0][c] =
+ *   border(c), Y[0][c] = SCORE_MIN.  The one difference: M[r][0] = 0 for every r = 0 .. m (X[r][0] = SCORE_MIN as before) --
+ *   leaving the database's first residues costs nothing.
+ * End cell: among the cells (r, n), r = 0 .. m, the one with the largest M, on a tie the smallest r.  score = M there, db_end = r.
+ *   Row 0 takes part: M[0][n] = border(n), the query against nothing.
+ * Walk: start in state M at (db_end, n); the records are those of the alignment contract above, so the tie rule exists once.
+ *   At c == 0: stop, db_begin = r there.  At r == 0, c > 0: one step left.  Elsewhere: as the alignment contract walks the method.
+ * Spans: the query's is always [0, n); the database's is [db_begin, db_end), 0 <= db_begin <= db_end <= m.
+ * identities, columns: of that walk, as struct sa_aln counts them; they travel forward with the scores together with db_begin
+ *   (csrc/sa_fit.hip, csrc/sa_fit_core.h): payload borders P(r, 0) = (0, 0, r), P(0, c) = (0, c, 0); no decision scratch, no walk.
+ *   pid is the value rule of "percent identity of every pair" over (identities, columns, m, n).
+ * What the score means: the best global score of the query against any substring d[s, e), 0 <= s <= e <= m; the empty substring
+ *   counts and gives border(n).  Hence NW / Gotoh score <= fit score, and under Gotoh fit score <= the SW score of the same gaps.
+ * The rectangle of fit scores is a dense rect[q * N + d] like that of sa_ctx_search_range: sa_ctx_hits, sa_ctx_hits_above_*,
+ * sa_ctx_normalize_rect and sa_ctx_strand_fold read it unchanged.  The same input gives the same bytes run after run. */
+struct sa_fit_out {
+	int32_t *score, *db_begin, *db_end, *identities, *columns, *pid; /* any subset non-NULL */
+	int32_t denom;                                                   /* SA_PID_*; read iff pid != NULL */
+};
+/* device-resident, asynchronous on `stream`, search contexts only (a strands context is one: its rows M .. 2 M are the reverse
+ * complements): queries [q0, q0 + nq) against every database sequence into the DEVICE arrays of *d_out (the struct itself is host
+ * memory), nq * N int32 each, element (q - q0) * N + d.  One wavefront per pair over the context's strip-boundary scratch plus the
+ * boundary payloads the context allocates at its first fit call -- the identity sweep's buffer (twice the bytes of that scratch,
+ * shared with it) and one of its own for the third payload word (once its bytes) -- and never afterwards: the rule of sa_ctx_alignments applies -- not beside sa_ctx_align_range / sa_ctx_search_range or another sweep of the
+ * SAME context on another stream; in order on one stream is fine.  Non-zero + sa_last_error, nothing launched, for a null
+ * argument, an ordinary context, a context whose method is SW, every output NULL, a denom outside the enum (when pid is asked
+ * for), q0 / nq out of range. */
+int sa_ctx_fit_rect(sa_ctx *ctx, int32_t q0, int32_t nq, const struct sa_fit_out *d_out, void *stream);
+/* the list form: item w is the query d_query[w] (0 .. the context's queries - 1) against the database sequence d_db[w]
+ * (0 .. N - 1), both DEVICE int32 arrays of npairs entries read by the kernel in stream order, element w of every non-NULL output;
+ * any order, duplicates allowed (the natural list: the nq x k hits).  An index outside its range reads nothing and gives
+ * INT32_MIN in every output asked for.  npairs == 0 launches nothing.  Refusals as above, and npairs < 0. */
+int sa_ctx_fit_pairs(sa_ctx *ctx, const int32_t *d_query, const int32_t *d_db, int64_t npairs, const struct sa_fit_out *d_out,
+		     void *stream);
+/* the fitted alignments of chosen pairs, as sa_ctx_alignments returns alignments: HOST index arrays in (query[t] in [0, the
+ * context's queries), db[t] in [0, N)), host result out, one record and one CIGAR per pair in the caller's order.  The fill and
+ * the walk are those of "alignments for chosen pairs" with the fit borders, end cell and walk step; batching, scan and compaction
+ * are shared (SA_HIP_TRACE_BATCH_BYTES caps a batch; sa_hip_last_alignments_seconds / _breakdown report the call).  Record
+ * layout, with a = the query and b = the database sequence: a_begin = 0, a_end = n; b_begin = db_begin, b_end = db_end; SA_ALN_I
+ * is a residue of the query only, SA_ALN_D of the database sequence only; score, columns and identities are those of
+ * sa_ctx_fit_pairs for the pair.  The CIGAR scores `score` as the alignment contract prices an alignment.  NULL + sa_last_error
+ * for an ordinary context, SW, an index out of range, npairs < 0; npairs == 0 gives a valid empty result. */
+sa_alns *sa_ctx_fit_alignments(sa_ctx *ctx, const int32_t *query, const int32_t *db, int64_t npairs);
+/* host in / host out, one device (the first): the fit search.  index, value, score, db_begin, db_end are (M, k) HOST arrays, rect
+ * and vrect (M, N), as sa_hip_search_pid lays them out; value, score, db_begin, db_end belong to the hits of index.  denom == -1:
+ * the hits are ranked by the fit score (value, when asked for, is a copy of score; vrect of rect); denom = SA_PID_*: by the
+ * percent identity of the fitted alignment.  Ties: index ascending.  Per batch of queries the rectangle sweep gives the score
+ * (and pid), sa_ctx_hits selects, and the list form over the nq x k hits gives db_begin / db_end and the raw score: no begin or
+ * end rectangle is ever made.  Batches are sized from the free device memory (SA_HIP_SEARCH_BATCH_BYTES caps a batch; a query
+ * costs 8 N + 32 k bytes).  The arguments are checked before a device is looked for: null arguments, SW, a denom that is neither
+ * -1 nor in the enum, a bad k, empty stores. */
+bool sa_hip_search_fit(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t k, int32_t denom,
+		       int32_t *index, int32_t *value, int32_t *score, int32_t *db_begin, int32_t *db_end, int32_t *rect, int32_t *vrect);
+/* device time (seconds) of the fit sweeps -- rectangle and list -- summed over the batches of the last successful sa_hip_search_fit */
+double sa_hip_last_search_fit_seconds(void);
+
 /* ---- complete and average linkage: the two other hierarchies of the device matrix ------------------------------------------
  * No reference counterpart.  The flat clusters of single linkage are connected components, and on protein families connected
  * components chain: one bridging sequence joins two unrelated groups.  Complete linkage promises that EVERY pair inside a

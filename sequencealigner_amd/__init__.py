@@ -89,6 +89,8 @@ from .binding import (  # noqa: F401
     hip_search_strands,
     hip_search_above_strands,
     last_search_strands_seconds,
+    hip_search_fit,
+    last_search_fit_seconds,
     dna_complement,
     reverse_complement,
     strand_words,
@@ -105,5 +107,5 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "AlignError", "Context", "PinnedMatrix", "Scoring", "SequenceStore", "device_count", "device_name", "last_align_breakdown", "last_align_path", "last_align_seconds", "hip_align", "hip_filter",
-    "hip_memory", "hip_neighbors", "Alignments", "hip_alignments", "last_alignments_seconds", "last_alignments_breakdown", "last_neighbors_seconds", "hip_edges", "last_edges_seconds", "hip_linkage", "linkage_labels", "linkage_merges", "linkage_scratch_bytes", "last_linkage_rounds", "last_linkage_seconds", "hip_select", "hip_edges_at_rank", "hip_linkage_with_ranks", "score_rank", "select_scratch_bytes", "last_select_seconds", "Norm", "NORM_SELF", "NORM_LENGTH", "NORM_MIN", "NORM_MAX", "NORM_MEAN", "NORM_SCALE", "norm_value", "last_normalize_seconds", "PID_COLUMNS", "PID_SHORTER", "PID_LONGER", "PID_MEAN", "pid_value", "hip_identity", "last_identity_seconds", "AGGLO_COMPLETE", "AGGLO_AVERAGE", "hip_agglomerate", "hip_agglomerate_with_ranks", "agglo_scratch_bytes", "agglo_labels", "last_agglomerate_seconds", "last_agglomerate_rescans", "SearchContext", "hip_search", "hits_scratch_bytes", "last_search_seconds", "last_search_breakdown", "last_search_quantity_seconds", "HitList", "hip_search_above", "hits_above_scratch_bytes", "last_search_above_seconds", "hip_search_strands", "hip_search_above_strands", "last_search_strands_seconds", "dna_complement", "reverse_complement", "strand_words", "STRAND_FORWARD", "STRAND_REVERSE", "STRAND_NONE", "library_path", "load_library", "matrix_names", "method_names", "pair_count", "set_progress",
+    "hip_memory", "hip_neighbors", "Alignments", "hip_alignments", "last_alignments_seconds", "last_alignments_breakdown", "last_neighbors_seconds", "hip_edges", "last_edges_seconds", "hip_linkage", "linkage_labels", "linkage_merges", "linkage_scratch_bytes", "last_linkage_rounds", "last_linkage_seconds", "hip_select", "hip_edges_at_rank", "hip_linkage_with_ranks", "score_rank", "select_scratch_bytes", "last_select_seconds", "Norm", "NORM_SELF", "NORM_LENGTH", "NORM_MIN", "NORM_MAX", "NORM_MEAN", "NORM_SCALE", "norm_value", "last_normalize_seconds", "PID_COLUMNS", "PID_SHORTER", "PID_LONGER", "PID_MEAN", "pid_value", "hip_identity", "last_identity_seconds", "AGGLO_COMPLETE", "AGGLO_AVERAGE", "hip_agglomerate", "hip_agglomerate_with_ranks", "agglo_scratch_bytes", "agglo_labels", "last_agglomerate_seconds", "last_agglomerate_rescans", "SearchContext", "hip_search", "hits_scratch_bytes", "last_search_seconds", "last_search_breakdown", "last_search_quantity_seconds", "HitList", "hip_search_above", "hits_above_scratch_bytes", "last_search_above_seconds", "hip_search_strands", "hip_search_above_strands", "last_search_strands_seconds", "hip_search_fit", "last_search_fit_seconds", "dna_complement", "reverse_complement", "strand_words", "STRAND_FORWARD", "STRAND_REVERSE", "STRAND_NONE", "library_path", "load_library", "matrix_names", "method_names", "pair_count", "set_progress",
 ]

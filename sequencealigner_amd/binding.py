@@ -79,6 +79,7 @@ ABI_SYMBOLS = (
     "sa_dna_complement", "sa_reverse_complement", "sa_ctx_create_search_strands", "sa_ctx_search_strands", "sa_ctx_strand_fold",
     "sa_ctx_hits_strand", "sa_ctx_hits_above_strand", "sa_hip_search_strands", "sa_hip_search_above_strands", "sa_hitlist_strand",
     "sa_hip_last_search_strands_seconds",
+    "sa_ctx_fit_rect", "sa_ctx_fit_pairs", "sa_ctx_fit_alignments", "sa_hip_search_fit", "sa_hip_last_search_fit_seconds",
 )
 
 
@@ -88,6 +89,11 @@ class _Norm(C.Structure):  # struct sa_norm
 
 class _IdentityOut(C.Structure):  # struct sa_identity_out
     _fields_ = [("score", C.c_void_p), ("identities", C.c_void_p), ("columns", C.c_void_p), ("pid", C.c_void_p), ("denom", C.c_int32)]
+
+
+class _FitOut(C.Structure):  # struct sa_fit_out
+    _fields_ = [("score", C.c_void_p), ("db_begin", C.c_void_p), ("db_end", C.c_void_p), ("identities", C.c_void_p), ("columns", C.c_void_p),
+                ("pid", C.c_void_p), ("denom", C.c_int32)]
 
 
 def library_path() -> pathlib.Path:
@@ -371,6 +377,15 @@ def load_library() -> C.CDLL:
     lib.sa_hip_search_pid.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_int32] + [C.c_void_p] * 5 + [C.c_int32]
     lib.sa_hip_search_pid.restype = C.c_bool
     lib.sa_hip_last_search_quantity_seconds.restype = C.c_double
+    lib.sa_ctx_fit_rect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_FitOut), C.c_void_p]
+    lib.sa_ctx_fit_rect.restype = C.c_int
+    lib.sa_ctx_fit_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(_FitOut), C.c_void_p]
+    lib.sa_ctx_fit_pairs.restype = C.c_int
+    lib.sa_ctx_fit_alignments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sa_ctx_fit_alignments.restype = C.c_void_p
+    lib.sa_hip_search_fit.argtypes = [_Input, _Input, C.POINTER(_Scoring), C.c_int32, C.c_int32] + [C.c_void_p] * 7
+    lib.sa_hip_search_fit.restype = C.c_bool
+    lib.sa_hip_last_search_fit_seconds.restype = C.c_double
     lib.sa_hits_above_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.sa_hits_above_scratch_bytes.restype = C.c_size_t
     lib.sa_ctx_hits_above_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1437,6 +1452,33 @@ class SearchContext(Context):
         if self._lib.sa_ctx_identity_rect(self._h, _int32("q0", q0), _int32("nq", nq), C.byref(out), C.c_void_p(stream)):
             raise AlignError(_err())
 
+    def fit_rect(self, q0: int, nq: int, score: int = 0, db_begin: int = 0, db_end: int = 0, identities: int = 0, columns: int = 0, pid: int = 0,
+                 denom: int = 0, stream: int = 0) -> None:
+        """sa_ctx_fit_rect: queries [q0, q0 + nq) fitted inside every database sequence -- the whole query, the database's overhang
+        free -- into the device arrays given (nq * N int32 each, element (q - q0) * N + d; 0: not asked for; `denom` is read iff pid),
+        asynchronously on `stream`; not beside another sweep of this context on another stream.  NW and Gotoh contexts only."""
+        out = _FitOut(score or None, db_begin or None, db_end or None, identities or None, columns or None, pid or None, _denom(denom))
+        if self._lib.sa_ctx_fit_rect(self._h, _int32("q0", q0), _int32("nq", nq), C.byref(out), C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def fit_pairs(self, d_query_ptr: int, d_db_ptr: int, npairs: int, score: int = 0, db_begin: int = 0, db_end: int = 0, identities: int = 0,
+                  columns: int = 0, pid: int = 0, denom: int = 0, stream: int = 0) -> None:
+        """sa_ctx_fit_pairs: the list form of fit_rect -- item w is query d_query[w] against database sequence d_db[w] (device int32
+        arrays, read in stream order), element w of every output given; an index out of range gives INT32_MIN"""
+        out = _FitOut(score or None, db_begin or None, db_end or None, identities or None, columns or None, pid or None, _denom(denom))
+        if self._lib.sa_ctx_fit_pairs(self._h, C.c_void_p(d_query_ptr or None), C.c_void_p(d_db_ptr or None), C.c_int64(int(npairs)), C.byref(out),
+                                      C.c_void_p(stream)):
+            raise AlignError(_err())
+
+    def fit_alignments(self, pairs) -> Alignments:
+        """sa_ctx_fit_alignments: the fitted alignments of the listed pairs (query, database sequence) -- query in [0, n_queries),
+        database sequence in [0, n_db), any order, duplicates allowed.  In the records a is the query (a_begin = 0, a_end = its
+        length) and b the database sequence (b_begin = db_begin, b_end = db_end); "I" is a residue of the query only.  `pairs` of the
+        result holds (query, database sequence) as given."""
+        arr = _pairs_array(pairs)
+        q, d = np.ascontiguousarray(arr[:, 0]), np.ascontiguousarray(arr[:, 1])
+        return _take_alignments(self._lib, self._lib.sa_ctx_fit_alignments(self._h, q.ctypes.data, d.ctypes.data, len(arr)), arr)
+
     def hits_take(self, d_rect_ptr: int, nq: int, k: int, d_index_ptr: int, d_out_ptr: int, stream: int = 0) -> None:
         """sa_ctx_hits_take: d_out[r, t] = d_rect[r, d_index[r, t]] for rows [0, nq) -- the raw scores of hits selected on a value
         rectangle"""
@@ -1543,6 +1585,42 @@ def hip_search(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: O
     if rect:
         res += (out,)
     return res[0] if len(res) == 1 else res
+
+
+def hip_search_fit(db: SequenceStore, queries: SequenceStore, scoring: Scoring, k: Optional[int] = None, rect: bool = False,
+                   pid: Optional[int] = None):
+    """sa_hip_search_fit: every query fitted inside every database sequence (the whole query, the database's overhang free; NW or
+    Gotoh) on the first device.  With k: (index, value, score, db_begin, db_end), five (M, k) int32 arrays -- row q lists the
+    database sequences by value descending, then index ascending; value is the fit score, or with pid=PID_* the percent identity
+    of the fitted alignment in parts per million; score is the fit score of each hit and [db_begin, db_end) the span of the
+    database sequence the query sits in.  With rect=True the (M, N) rectangles rect (fit scores) and vrect (values) follow (alone
+    when k is None)."""
+    n, m = db.num, queries.num
+    if k is None and not rect:
+        raise AlignError("hip_search_fit: nothing asked for (k is None and rect is False)")
+    kk = 0 if k is None else _int32("k", k)
+    hits = [None] * 5
+    out = vout = None
+    if k is not None:
+        rows = max(m, 1) * max(min(kk, NEIGHBORS_MAX), 1)
+        hits = [np.empty(rows, np.int32) for _ in range(5)]
+    if rect:
+        out, vout = np.empty((max(m, 0), max(n, 0)), np.int32), np.empty((max(m, 0), max(n, 0)), np.int32)
+    ptr = [None if a is None else a.ctypes.data for a in (*hits, out, vout)]
+    sc = scoring._as_c()
+    if not load_library().sa_hip_search_fit(db._as_c(), queries._as_c(), C.byref(sc), kk, -1 if pid is None else _denom(pid), *ptr):
+        raise AlignError(_err())
+    res = ()
+    if k is not None:
+        res += tuple(a[:m * kk].reshape(m, kk) for a in hits)
+    if rect:
+        res += (out, vout)
+    return res
+
+
+def last_search_fit_seconds() -> float:
+    """device time of the fit sweeps (rectangle and list) of the last hip_search_fit call, summed over its batches"""
+    return float(load_library().sa_hip_last_search_fit_seconds())
 
 
 class HitList:

@@ -435,6 +435,7 @@ extern "C" void sa_ctx_destroy(sa_ctx *ctx)
 	(void)hipFree(ctx->d_sub8);
 	(void)hipFree(ctx->d_scratch);
 	(void)hipFree(ctx->d_id_scratch);
+	(void)hipFree(ctx->d_fit_scratch);
 	(void)hipFree(ctx->d_counters);
 	for (hipEvent_t ev : ctx->slot_done)
 		if (ev)

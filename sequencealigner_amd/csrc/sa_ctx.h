@@ -8,6 +8,7 @@
  *   sa_identity.hip: sa_ctx_identity_range, sa_hip_identity (percent identity of every pair)
  *   sa_search.hip  : sa_ctx_search_range, sa_ctx_hits, sa_hip_search (queries against a database: search contexts)
  *   sa_search_quantity.hip, sa_search_above.hip : the hits of a search by a value; every hit at or above a threshold
+ *   sa_fit.hip     : sa_ctx_fit_rect, sa_ctx_fit_pairs, sa_hip_search_fit (queries fitted inside database sequences)
  *   sa_abi.hip     : sa_hip_align, sa_hip_memory, sa_hip_filter, progress, side channels
  */
 #ifndef SA_CTX_H
@@ -51,6 +52,7 @@ struct sa_ctx {
 	int64_t scratch_stride = 0;
 	int generic_blocks = 0;
 	void *d_id_scratch = nullptr; /* strip-boundary payloads of sa_k_identity (sa_identity.hip): one per int of d_scratch, allocated on first use */
+	void *d_fit_scratch = nullptr; /* strip-boundary payloads of sa_k_fit (sa_fit.hip), their third word (identities and columns sit in d_id_scratch): one int per int of d_scratch, allocated on first use */
 	/* Tile counters of the persistent launches: one slot of COUNTERS_PER_SLOT counters per sa_ctx_align_range call, taken
 	 * round-robin from a ring so that ranges issued back to back on DIFFERENT streams never share a counter.
 	 * INVARIANT: a slot's counters are zero whenever no launch is using them -- zeroed at context creation, and every

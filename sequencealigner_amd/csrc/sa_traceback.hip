@@ -14,6 +14,9 @@
  *                            wave fetches the kilobyte that ends at the current record in one load per lane, parks it in LDS
  *                            and takes the next eight to sixteen steps from there.  Runs are written end-first, downwards
  *                            from the end of the pair's area of m + n words.
+ *   FIT = true               the fit contract (sa_fit_core.h; sa_ctx_fit_alignments): the fill feeds M[r][0] = 0 in lane 0 of strip 0
+ *                            and the lane that owns column n keeps the end cell (M descending, r ascending, row 0 included); the walk
+ *                            takes its steps through sa_tb_step_fit.  Everything else is the one body.
  *   sa_k_trace_scan          exclusive scan of cigar_len in the caller's pair order -> cigar_off
  *   sa_k_trace_compact       the runs of every pair from its area into the flat array
  */
@@ -22,6 +25,7 @@
 #include <mutex>
 
 #include "sa_ctx.h"
+#include "sa_fit_core.h"
 #include "sa_traceback_core.h"
 
 struct sa_alns {
@@ -77,7 +81,7 @@ __device__ __forceinline__ int32_t from_left(int32_t v)
 	return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false);
 }
 
-template <int METHOD>
+template <int METHOD, bool FIT>
 __global__ __launch_bounds__(256) void sa_k_trace_fill(SaTbFillArgs A)
 {
 	__shared__ int32_t s_sub[SA_SUB_DIM * SA_SUB_DIM];
@@ -113,6 +117,8 @@ __global__ __launch_bounds__(256) void sa_k_trace_fill(SaTbFillArgs A)
 		const int32_t nstrips = (n + 63) >> 6;
 		const int64_t strip_groups = sa_tb_strip_lines(m, 64) >> 2; /* 256-byte groups of a full strip */
 		int32_t best = 0, best_r = 0, best_c = 0; /* SW end cell of this lane */
+		if (FIT)
+			best = border(n); /* FIT: the end cell of column n, row 0's to begin with (kept by the lane that owns the column) */
 		int32_t h = 0;
 
 		for (int32_t s = 0; s < nstrips; s++) {
@@ -137,7 +143,7 @@ __global__ __launch_bounds__(256) void sa_k_trace_fill(SaTbFillArgs A)
 					lx = from_left(x);
 				if (lane == 0) {
 					if (s == 0) {
-						lm = border(r);
+						lm = FIT ? 0 : border(r); /* (FIT: the row sequence's first residues are free) */
 						lx = SCORE_MIN;
 					} else if (r <= m) {
 						lm = bndM[r];
@@ -181,6 +187,10 @@ __global__ __launch_bounds__(256) void sa_k_trace_fill(SaTbFillArgs A)
 						best_r = r;
 						best_c = c;
 					}
+					if (FIT && c == n && nm > best) { /* (rows arrive in ascending order: strictly greater only) */
+						best = nm;
+						best_r = r;
+					}
 					if (lane == 63 && !last_strip) {
 						bndM[r] = nm;
 						if (METHOD != SA_METHOD_NW)
@@ -194,7 +204,11 @@ __global__ __launch_bounds__(256) void sa_k_trace_fill(SaTbFillArgs A)
 
 		SaTbEnd E;
 		E.pad = 0;
-		if (METHOD == SA_METHOD_SW) {
+		if (FIT) {
+			E.score = __shfl(best, (n - 1) & 63, 64);
+			E.r = __shfl(best_r, (n - 1) & 63, 64);
+			E.c = n;
+		} else if (METHOD == SA_METHOD_SW) {
 #pragma unroll
 			for (int d = 32; d >= 1; d >>= 1) {
 				const int32_t ov = __shfl_xor(best, d, 64), orr = __shfl_xor(best_r, d, 64), oc = __shfl_xor(best_c, d, 64);
@@ -219,7 +233,7 @@ __global__ __launch_bounds__(256) void sa_k_trace_fill(SaTbFillArgs A)
 
 constexpr int WIN_BYTES = 1024; /* 64 lanes x 16 bytes */
 
-template <int METHOD>
+template <int METHOD, bool FIT>
 __global__ __launch_bounds__(256) void sa_k_trace_walk(SaTbWalkArgs A)
 {
 	__shared__ __attribute__((aligned(16))) uint8_t s_win[4][WIN_BYTES];
@@ -256,7 +270,7 @@ __global__ __launch_bounds__(256) void sa_k_trace_walk(SaTbWalkArgs A)
 				}
 				rec = win[at - win_lo];
 			}
-			const int op = sa_tb_step(&w, METHOD, rec);
+			const int op = FIT ? sa_tb_step_fit(&w, METHOD, rec) : sa_tb_step(&w, METHOD, rec);
 			if (op < 0)
 				break;
 			if (op == SA_TB_OP_M)
@@ -375,16 +389,16 @@ bool check_pairs(const char *who, int32_t num, const int32_t *a, const int32_t *
 	return true;
 }
 
-template <int METHOD> void launch_batch(const SaTbFillArgs &f, const SaTbWalkArgs &w, int blocks, hipStream_t s, hipEvent_t mid)
+template <int METHOD, bool FIT = false> void launch_batch(const SaTbFillArgs &f, const SaTbWalkArgs &w, int blocks, hipStream_t s, hipEvent_t mid)
 {
-	hipLaunchKernelGGL(sa_k_trace_fill<METHOD>, dim3(blocks), dim3(256), 0, s, f);
+	hipLaunchKernelGGL((sa_k_trace_fill<METHOD, FIT>), dim3(blocks), dim3(256), 0, s, f);
 	(void)hipEventRecord(mid, s);
-	hipLaunchKernelGGL(sa_k_trace_walk<METHOD>, dim3(blocks), dim3(256), 0, s, w);
+	hipLaunchKernelGGL((sa_k_trace_walk<METHOD, FIT>), dim3(blocks), dim3(256), 0, s, w);
 }
 
-sa_alns *alignments_impl(sa_ctx *ctx, const int32_t *a, const int32_t *b, int64_t npairs)
+/* fit: the pairs are (N + query, database sequence) of a search context whose method is NW or Gotoh, checked by the caller */
+sa_alns *alignments_impl(sa_ctx *ctx, const int32_t *a, const int32_t *b, int64_t npairs, bool fit = false, const char *who = "sa_ctx_alignments")
 {
-	const char *who = "sa_ctx_alignments";
 	if (!ctx) {
 		sa_set_error("%s: null context", who);
 		return nullptr;
@@ -514,10 +528,16 @@ sa_alns *alignments_impl(sa_ctx *ctx, const int32_t *a, const int32_t *b, int64_
 		SA_HIP_CHECK(hipEventRecord(sy.ev[3 * k], sy.s), return nullptr);
 		switch (ctx->sc.method) {
 		case SA_METHOD_NW:
-			launch_batch<SA_METHOD_NW>(f, w, blocks, sy.s, sy.ev[3 * k + 1]);
+			if (fit)
+				launch_batch<SA_METHOD_NW, true>(f, w, blocks, sy.s, sy.ev[3 * k + 1]);
+			else
+				launch_batch<SA_METHOD_NW>(f, w, blocks, sy.s, sy.ev[3 * k + 1]);
 			break;
 		case SA_METHOD_GA:
-			launch_batch<SA_METHOD_GA>(f, w, blocks, sy.s, sy.ev[3 * k + 1]);
+			if (fit)
+				launch_batch<SA_METHOD_GA, true>(f, w, blocks, sy.s, sy.ev[3 * k + 1]);
+			else
+				launch_batch<SA_METHOD_GA>(f, w, blocks, sy.s, sy.ev[3 * k + 1]);
 			break;
 		default:
 			launch_batch<SA_METHOD_SW>(f, w, blocks, sy.s, sy.ev[3 * k + 1]);
@@ -588,7 +608,42 @@ sa_alns *hip_alignments_impl(struct sa_input in, const struct sa_scoring *sc, co
 	return res;
 }
 
+/* host index arrays: query[t] in [0, the context's queries), db[t] in [0, N); the pair is (a, b) = (N + query[t], db[t]) */
+sa_alns *fit_alignments_impl(sa_ctx *ctx, const int32_t *query, const int32_t *db, int64_t npairs)
+{
+	const char *who = "sa_ctx_fit_alignments";
+	if (!sa_search_ctx_check(who, ctx))
+		return nullptr;
+	if (ctx->sc.method != SA_METHOD_NW && ctx->sc.method != SA_METHOD_GA) {
+		sa_set_error("%s: the context's method is SW, which is local already; fit is defined for NW and Gotoh", who);
+		return nullptr;
+	}
+	if (npairs < 0) {
+		sa_set_error("%s: npairs = %lld is negative", who, (long long)npairs);
+		return nullptr;
+	}
+	if (npairs > 0 && (!query || !db)) {
+		sa_set_error("%s: null pair list", who);
+		return nullptr;
+	}
+	std::vector<int32_t> a((size_t)npairs);
+	for (int64_t t = 0; t < npairs; t++) {
+		if (query[t] < 0 || query[t] >= ctx->search_queries || db[t] < 0 || db[t] >= ctx->search_db) {
+			sa_set_error("%s: pair %lld = (query %d, database sequence %d): index out of range (%d queries, %d database sequences)", who, (long long)t,
+				     query[t], db[t], ctx->search_queries, ctx->search_db);
+			return nullptr;
+		}
+		a[(size_t)t] = ctx->search_db + query[t];
+	}
+	return alignments_impl(ctx, a.data(), db, npairs, true, who);
+}
+
 } // namespace
+
+extern "C" sa_alns *sa_ctx_fit_alignments(sa_ctx *ctx, const int32_t *query, const int32_t *db, int64_t npairs)
+{
+	return sa_guard("sa_ctx_fit_alignments", (sa_alns *)nullptr, [&] { return fit_alignments_impl(ctx, query, db, npairs); });
+}
 
 extern "C" sa_alns *sa_ctx_alignments(sa_ctx *ctx, const int32_t *a, const int32_t *b, int64_t npairs)
 {
