@@ -4,7 +4,7 @@ the end cell, the walk, the run-length CIGAR.  Shares no code with the library o
 The database sequence is the row sequence (r = 0 .. m), the query the column sequence (c = 0 .. n).  The tables are the method's
 (NW: one table with a linear gap; Gotoh: M, X from the left, Y from above) with column 0 of M set to 0 in every row.
 
-fit_pair(scoring, db_seq, query_seq) -> dict(score, db_begin, db_end, identities, columns, cigar): cigar a list of (length, op),
+fit_pair(scoring, db_seq, query_seq) -> dict(score, db_begin, db_end, identities, columns, cigar, plateau): cigar a list of (length, op),
 "M" a residue of each, "I" a residue of the query only, "D" a residue of the database sequence only (the record layout of the
 hits: a = the query, b = the database sequence).
 rescore(scoring, db_seq, query_seq, result) prices that CIGAR as the alignment contract prices an alignment.
@@ -70,9 +70,14 @@ def global_score(scoring, db: list, qy: list) -> int:
     return fill(scoring, db, qy, free_column=False)[0][len(db)][len(qy)]
 
 
-def fit_codes(scoring, db: list, qy: list) -> dict:
+def fit_codes(scoring, db: list, qy: list, flipped_ties: bool = False, last_end_row: bool = False, tabs=None) -> dict:
+    """the contract's result, plus `plateau`: the number of rows r with M[r][n] equal to the maximum of column n.
+    The two switches exist for the sensitivity of tests only (what ANOTHER rule would give on the same tables), both off by default:
+    flipped_ties walks with the other order among equally good moves (NW: up before diagonal before left; Gotoh: X, then Y, before
+    diagonal when leaving M -- the open / extend test unchanged), last_end_row takes the largest row among equal maxima of column n.
+    tabs = fill(scoring, db, qy): one fill serves several walks."""
     m, n = len(db), len(qy)
-    M, X, Y = fill(scoring, db, qy)
+    M, X, Y = fill(scoring, db, qy) if tabs is None else tabs
     g, o = scoring.gap_pen, scoring.gap_opn
     S = _table(scoring)
     # end cell: the largest M of column n, the smallest row on a tie; row 0 takes part
@@ -80,6 +85,9 @@ def fit_codes(scoring, db: list, qy: list) -> dict:
     for r in range(1, m + 1):
         if M[r][n] > M[end][n]:
             end = r
+        elif last_end_row and M[r][n] == M[end][n]:  # (the other rule)
+            end = r
+    plateau = sum(1 for r in range(m + 1) if M[r][n] == M[end][n])
     r, c, state = end, n, "M"
     ops = []  # end first
     ident = 0
@@ -89,6 +97,12 @@ def fit_codes(scoring, db: list, qy: list) -> dict:
             c -= 1
             state = "M"
             continue
+        if flipped_ties and scoring.method == NW and M[r][c] == M[r - 1][c] + g:  # (the other order: up first)
+            ops.append("D")
+            r -= 1
+            continue
+        if flipped_ties and scoring.method != NW and state == "M" and M[r][c] in (X[r][c], Y[r][c]):  # (the other order: X, then Y, first)
+            state = "X" if M[r][c] == X[r][c] else "Y"
         if scoring.method == NW:
             if M[r][c] == M[r - 1][c - 1] + S[db[r - 1]][qy[c - 1]]:
                 ops.append("M")
@@ -123,11 +137,11 @@ def fit_codes(scoring, db: list, qy: list) -> dict:
             cigar[-1] = (cigar[-1][0] + 1, op)
         else:
             cigar.append((1, op))
-    return dict(score=M[end][n], db_begin=r, db_end=end, identities=ident, columns=len(ops), cigar=cigar)
+    return dict(score=M[end][n], db_begin=r, db_end=end, identities=ident, columns=len(ops), cigar=cigar, plateau=plateau)
 
 
-def fit_pair(scoring, db_seq: bytes, query_seq: bytes) -> dict:
-    return fit_codes(scoring, encode(scoring, db_seq), encode(scoring, query_seq))
+def fit_pair(scoring, db_seq: bytes, query_seq: bytes, flipped_ties: bool = False, last_end_row: bool = False, tabs=None) -> dict:
+    return fit_codes(scoring, encode(scoring, db_seq), encode(scoring, query_seq), flipped_ties, last_end_row, tabs)
 
 
 def rescore(scoring, db_seq: bytes, query_seq: bytes, res: dict) -> int:

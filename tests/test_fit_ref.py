@@ -2,11 +2,16 @@
 oracle: what the fit score means.  For short pairs the fit score must equal the largest global score of the query against any
 substring of the database sequence, the empty substring (closed form: the query against gaps) included.  Every substring and the
 query go through the oracle's alignment as one store; the query is its last sequence, so every pair (substring, query) is in the
-canonical orientation of the contract."""
+canonical orientation of the contract.
+
+And the conditions of tests/test_gpu_fit_strips.py where no GPU runs: the store of tests/fit_strip_cases.py must keep its ties,
+plateaus, strip-edge runs and row-0 walks under the reference, or that file compares the device on inputs that decide nothing."""
+import types
+
 import numpy as np
 import pytest
 
-from tests import fit_ref
+from tests import fit_ref, fit_strip_cases
 
 SCORINGS = [("nw", dict(gap_pen=4)), ("ga", dict(gap_open=10, gap_extend=1)), ("ga", dict(gap_open=3, gap_extend=7)), ("nw", dict(gap_pen=1))]
 LETTERS = b"ACDEW"  # few letters: ties; C / E scores -4
@@ -57,3 +62,36 @@ def test_fit_score_is_the_best_global_score_over_substrings(method, gaps, sa, or
         end0 += got["db_end"] == 0
         inside += got["db_begin"] > 0 and got["db_end"] < m
     assert end0 >= 1 and inside >= 2
+
+
+# ---- the strip store keeps its conditions ------------------------------------------------------------------------------------------------
+def plus5_minus4(method: str, gaps: dict):
+    """a stand-in for a Scoring, fit_ref needs no library: A, C, G, T -> 0 .. 3, +5 / -4, the gaps negative as the library holds them"""
+    lut = np.full(128, -1, np.int32)
+    for code, ch in enumerate(b"ACGT"):
+        lut[ch] = code
+    sub = np.full((24, 24), -4, np.int32)
+    np.fill_diagonal(sub, 5)
+    return types.SimpleNamespace(lut=lut, sub=sub.reshape(-1), method={"nw": fit_ref.NW, "ga": fit_ref.GA}[method], gap_pen=-gaps.get("gap_pen", 0),
+                                 gap_opn=-gaps.get("gap_open", 0), gap_ext=-gaps.get("gap_extend", 0))
+
+
+@pytest.mark.parametrize("method,gaps,begin_flips", [("nw", dict(gap_pen=2), None), ("ga", dict(gap_open=0, gap_extend=0), 16)], ids=["nw-2", "ga-0-0"])
+def test_strip_store_keeps_its_conditions(method, gaps, begin_flips):
+    """The floors of tests/test_gpu_fit_strips.py on the 99 pairs with m <= 257 (a few seconds of Python), two of its seven scorings.
+    Counts of these pairs (of 99): NW 2: CIGAR flips 83, end-row moves 6, strip-edge runs 24, inside 38, row-0 runs 8; Gotoh 0/0: 96, 49,
+    db_begin flips 16, inside 29, row-0 runs 3.  One floor is lower here than over the whole store: under Gotoh 0/0 the other tie order
+    moves db_begin in 33 of the 124 pairs (the floor is 20 %), but 17 of those are against the entries of 400, 700 and 3000 residues,
+    where a query has room to start elsewhere; the 99 pairs left hold 16, and 16 is asked for."""
+    db, queries, notes = fit_strip_cases.strip_store()
+    scoring = plus5_minus4(method, gaps)
+    which = [(q, d) for q, d in fit_strip_cases.pairs(db, queries, notes) if len(db[d]) <= 257]
+    assert len(which) == 99
+    ref = fit_strip_cases.references(scoring, db, queries, which)
+    n = fit_strip_cases.counts(ref, db, queries)
+    print(f"{method} {gaps}: {n}")
+    fit_strip_cases.check_floors(n, method, gaps, begin_flips)
+    fit_strip_cases.check_all_t(ref, scoring, notes)
+    for (q, d), (want, flipped, last) in ref.items():  # the other rules give alignments of the same score: only an exact comparison tells them apart
+        for res in (want, flipped, last):
+            assert fit_ref.rescore(scoring, db[d], queries[q], res) == want["score"]
