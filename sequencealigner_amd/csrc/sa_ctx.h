@@ -5,10 +5,13 @@
  *   sa_launch.hip  : plan cache + upload, sa_ctx_align_range, shares and placement
  *   sa_deliver.hip : sa_ctx_align_host (the launch/copy loop towards host memory)
  *   sa_gather.hip  : several devices of one process through dense shares + RCCL all-gather
- *   sa_identity.hip: sa_ctx_identity_range, sa_hip_identity (percent identity of every pair)
+ *   sa_normalize.hip, sa_identity.hip : normalised scores and percent identity of every pair
  *   sa_search.hip  : sa_ctx_search_range, sa_ctx_hits, sa_hip_search (queries against a database: search contexts)
- *   sa_search_quantity.hip, sa_search_above.hip : the hits of a search by a value; every hit at or above a threshold
+ *   sa_search_quantity.hip : sa_ctx_normalize_rect, sa_ctx_identity_rect, sa_ctx_hits_take, sa_hip_search_norm / _pid (hits by a value)
+ *   sa_search_above.hip    : sa_ctx_hits_above_offsets / _fill, sa_hip_search_above (every hit at or above a threshold)
+ *   sa_strands.hip : sa_ctx_strand_fold, sa_ctx_hits_strand, sa_ctx_hits_above_strand, sa_hip_search_strands (both strands of DNA queries)
  *   sa_fit.hip     : sa_ctx_fit_rect, sa_ctx_fit_pairs, sa_hip_search_fit (queries fitted inside database sequences)
+ *   sa_search_run.h: what the one-call search forms of the five files above share (header-only; includes this file)
  *   sa_abi.hip     : sa_hip_align, sa_hip_memory, sa_hip_filter, progress, side channels
  */
 #ifndef SA_CTX_H
@@ -213,55 +216,52 @@ bool sa_rccl_available(std::string *why);
  * when not null, receives d[0 .. N); the device time goes to sa_hip_last_normalize_seconds. */
 bool sa_norm_check(const char *who, const struct sa_norm *norm);
 bool sa_normalize_in_place(const char *who, sa_ctx *ctx, int32_t *d_packed, const struct sa_norm *norm, hipStream_t s);
+/* the rule inside its enum, or sa_set_error; the denominators of ctx's whole store (N + M on a search context, N + 2 M on a strands
+ * context) into d_den on `s`, the current device being the context's */
+bool sa_norm_rule_check(const char *who, int32_t rule);
+hipError_t sa_denominators_launch(sa_ctx *ctx, int32_t source, int32_t *d_den, hipStream_t s);
 
 /* sa_identity.hip: denom inside its enum, or sa_set_error; the identity sweep over the whole pair space of ctx's store with pid
  * written to d_packed[p] -- in place of whatever the matrix held -- in order on `s`, which is synchronised (the *_pid calls,
  * sa_zjob_identity); the device time goes to sa_hip_last_identity_seconds. */
 bool sa_identity_denom_check(const char *who, int32_t denom);
 bool sa_identity_in_place(const char *who, sa_ctx *ctx, int32_t *d_packed, int32_t denom, hipStream_t s);
-
-/* ---- what sa_search_quantity.hip (values of the hits: normalised scores, percent identity) takes from its neighbours ---------- */
-/* sa_normalize.hip: the rule inside its enum, or sa_set_error; the denominators of ctx's whole store (N + M on a search context)
- * into d_den on `s`, the current device being the context's */
-bool sa_norm_rule_check(const char *who, int32_t rule);
-hipError_t sa_denominators_launch(sa_ctx *ctx, int32_t source, int32_t *d_den, hipStream_t s);
-/* sa_identity.hip: the rectangle form of the identity sweep on a search context whose queries [q0, q0 + nq) have been checked:
- * element (q - q0) * N + d of every non-null output; the outputs are checked as sa_ctx_identity_range checks them */
+/* the rectangle form of the identity sweep on a search context whose queries [q0, q0 + nq) have been checked: element
+ * (q - q0) * N + d of every non-null output; the outputs are checked as sa_ctx_identity_range checks them */
 bool sa_identity_rect(const char *who, sa_ctx *ctx, int32_t q0, int32_t nq, const struct sa_identity_out *d_out, hipStream_t s);
 /* the boundary payloads of ctx's identity sweeps, allocated now (they are allocated at the first sweep otherwise) */
 bool sa_identity_payload_scratch(sa_ctx *ctx);
-/* sa_search.hip: the checks and launches of sa_ctx_search_range / sa_ctx_hits under another caller's name */
+
+/* sa_search.hip: the checks and launches of sa_ctx_search_range / sa_ctx_hits under another caller's name, the arguments of the
+ * launches checked by the caller */
 bool sa_search_ctx_check(const char *who, const sa_ctx *ctx);
 bool sa_search_queries_check(const char *who, const sa_ctx *ctx, int32_t q0, int32_t nq);
 bool sa_hits_check(const char *who, int64_t n_db, int64_t nq, int32_t k);
 /* (`mid`, when not null, is recorded between the alignment of the range and the move of its rows) */
 int sa_search_range_launch(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void *d_scratch, hipStream_t s, hipEvent_t mid);
+int sa_hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, hipStream_t s);
 /* what sa_hip_last_search_seconds / _breakdown report from now on */
 void sa_search_last_set(double align, double gather, double hits, int32_t batches);
-int sa_hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, hipStream_t s);
 
-/* ---- what sa_search_above.hip (every hit at or above a threshold) takes from sa_search_quantity.hip ------------------------------ */
-/* the sweep of sa_ctx_normalize_rect, its arguments checked by the caller */
+/* sa_search_quantity.hip: the launches of sa_ctx_normalize_rect and sa_ctx_hits_take, their arguments checked by the caller; what
+ * sa_hip_last_search_quantity_seconds reports from now on */
 int sa_normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, int32_t nq, const int32_t *d_den, int32_t rule, int32_t *d_out,
 			     hipStream_t s);
-/* what sa_hip_last_search_quantity_seconds reports from now on */
+int sa_hits_take_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, const int32_t *d_index, int32_t *d_out, hipStream_t s);
 void sa_search_quantity_last_set(double seconds);
 
-/* ---- what sa_strands.hip (both strands of DNA queries) takes from its neighbours ------------------------------------------------- */
 /* sa_strands.hip: can every residue of `in` be reverse-complemented under comp, and does sc->lut (sc may be NULL: not checked)
  * take the complement?  false + sa_set_error naming the sequence, the position and the byte otherwise */
 bool sa_strands_rc_checked(const char *who, struct sa_input in, const uint8_t *comp, const struct sa_scoring *sc);
-/* sa_strands.hip: what sa_ctx_create_search_strands would refuse -- N + 2 M or the blob past int32, a residue that cannot be
- * complemented -- said under the caller's name before a device is looked for (the stores are not null) */
+/* what sa_ctx_create_search_strands would refuse -- N + 2 M or the blob past int32, a residue that cannot be complemented -- said
+ * under the caller's name before a device is looked for (the stores are not null) */
 bool sa_strands_inputs_check(const char *who, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp);
-/* sa_strands.hip: the launches of sa_ctx_strand_fold and sa_ctx_hits_above_strand, their arguments checked by the caller; what
+/* the launches of sa_ctx_strand_fold and sa_ctx_hits_above_strand, their arguments checked by the caller; what
  * sa_hip_last_search_strands_seconds reports from now on */
 int sa_strand_fold_launch(const int32_t *vf, const int32_t *vr, const int32_t *sf, const int32_t *sr, int32_t n_db, int32_t nq, int32_t *vbest,
 			  int32_t *sbest, uint64_t *bits, hipStream_t s);
 int sa_hits_above_strand_launch(const uint64_t *bits, int32_t n_db, int32_t nq, const int64_t *offsets, const int32_t *index, uint8_t *strand,
 				hipStream_t s);
 void sa_strands_last_set(double seconds);
-/* sa_search_quantity.hip: the launch of sa_ctx_hits_take, its arguments checked by the caller */
-int sa_hits_take_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, const int32_t *d_index, int32_t *d_out, hipStream_t s);
 
 #endif /* SA_CTX_H */

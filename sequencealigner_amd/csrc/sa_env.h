@@ -30,8 +30,8 @@ struct SaEnv {
 	long long trace_batch_bytes = 0; /* SA_HIP_TRACE_BATCH_BYTES=n : cap on the decision scratch of one batch of pairs (0: from the free device memory) */
 	/* percent identity (sa_identity.hip) */
 	long long identity_batch_bytes = 0; /* SA_HIP_IDENTITY_BATCH_BYTES=n : cap on the device buffers of one column range of sa_hip_identity (0: from the free device memory) */
-	/* search (sa_search.hip) */
-	long long search_batch_bytes = 0; /* SA_HIP_SEARCH_BATCH_BYTES=n : cap on the device buffers of one query batch of sa_hip_search (0: from the free device memory) */
+	/* search (sa_search_run.h) */
+	long long search_batch_bytes = 0; /* SA_HIP_SEARCH_BATCH_BYTES=n : cap on the device buffers of one query batch of every one-call search form (0: from the free device memory) */
 	/* diagnostics */
 	bool verbose = false;             /* SA_HIP_VERBOSE                                                               */
 	bool stamps = false;              /* SA_HIP_STAMPS : per-tile clocks of every launch (synchronous)                */

@@ -22,7 +22,7 @@
 #include <algorithm>
 #include <atomic>
 
-#include "sa_ctx.h"
+#include "sa_search_run.h"
 #include "sa_fit_core.h"
 #include "sa_search_quantity_core.h"
 
@@ -359,21 +359,6 @@ int fit_pairs_impl(sa_ctx *ctx, const int32_t *d_query, const int32_t *d_db, int
 	return launch_fit(who, ctx, 0, d_query, d_db, npairs, *d_out, (hipStream_t)stream) ? 0 : 1;
 }
 
-struct DevBuf {
-	void *p = nullptr;
-	~DevBuf() { (void)hipFree(p); }
-	bool alloc(const char *who, size_t bytes, const char *what)
-	{
-		if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) {
-			(void)hipGetLastError();
-			p = nullptr;
-			sa_set_error("%s: %s (%.2f GiB) does not fit the device's memory", who, what, (double)bytes / (double)(1 << 30));
-			return false;
-		}
-		return true;
-	}
-};
-
 bool search_fit_impl(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t k, int32_t denom, int32_t *index, int32_t *value,
 		     int32_t *score, int32_t *db_begin, int32_t *db_end, int32_t *rect, int32_t *vrect)
 {
@@ -395,122 +380,73 @@ bool search_fit_impl(struct sa_input db, struct sa_input queries, const struct s
 		sa_set_error("%s: nothing asked for (index, rect and vrect are all null)", who);
 		return false;
 	}
-	if (db.num < 1 || queries.num < 1) {
-		sa_set_error("%s: empty store (%d database sequences, %d queries; min: 1 each)", who, db.num, queries.num);
+	if (!sa_run_stores_not_empty(who, db, queries) || !sa_run_stores_not_null(who, db, queries))
 		return false;
-	}
-	if (!db.seqs || !db.meta || !queries.seqs || !queries.meta) {
-		sa_set_error("%s: null sequence store", who);
-		return false;
-	}
 	if (want_hits && !sa_hits_check(who, db.num, queries.num, k))
 		return false;
 	const bool by_pid = denom != -1;
 	if (by_pid && !sa_identity_denom_check(who, denom))
 		return false;
-	if (sa_hip_device_count() <= 0) {
-		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
+	if (!sa_run_device_check())
 		return false;
-	}
-	struct Ctx {
-		sa_ctx *c = nullptr;
-		~Ctx() { sa_ctx_destroy(c); }
-	} cx;
-	cx.c = sa_ctx_create_search(0, db, queries, sc);
-	if (!cx.c)
+	SearchRun run(who);
+	if (!run.adopt(sa_ctx_create_search(0, db, queries, sc), db, queries))
 		return false;
-	sa_ctx *ctx = cx.c;
+	sa_ctx *ctx = run.ctx;
 	SA_HIP_CHECK(hipSetDevice(ctx->device), return false);
-	const int64_t n = db.num, m = queries.num;
-	if (!fit_scratch(who, ctx)) /* (before the free memory is read) */
+	if (!fit_scratch(who, ctx) || !run.size(sa_batch_per_query_fit(run.n, want_hits, k))) /* (the scratch: before the free memory is read) */
 		return false;
-	/* Batch, per query: a row of the rectangle and of the value rectangle; with hits index, value, score, db_begin, db_end, the
-	 * query of every hit and one partial list */
-	size_t free_b = 0, total_b = 0;
-	SA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b), return false);
-	const int64_t per_query = 8 * n + (want_hits ? 32 * (int64_t)k : 0);
-	int64_t budget = (int64_t)(free_b - free_b / 4);
-	if (ctx->env.search_batch_bytes > 0)
-		budget = std::min<int64_t>(budget, ctx->env.search_batch_bytes);
-	const int32_t nqb = (int32_t)std::max<int64_t>(1, std::min<int64_t>(m, budget / per_query));
-	size_t part_bytes = 0;
-	if (want_hits)
-		for (int64_t q0 = 0; q0 < m; q0 += nqb)
-			part_bytes = std::max(part_bytes, sa_hits_scratch_bytes((int32_t)n, (int32_t)std::min<int64_t>(nqb, m - q0), k));
-	DevBuf d_rect, d_vrect, d_hits, d_part;
-	if (!d_rect.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the rectangle of a query batch") ||
-	    (by_pid && !d_vrect.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the value rectangle of a query batch")) ||
-	    (want_hits && (!d_hits.alloc(who, 6 * sizeof(int32_t) * (size_t)nqb * (size_t)k, "the hits of a query batch") ||
-			   !d_part.alloc(who, part_bytes, "the partial hit lists"))))
+	const int32_t n = (int32_t)run.n;
+	const size_t rect_bytes = sizeof(int32_t) * (size_t)run.nqb * (size_t)n, cap = (size_t)run.nqb * (size_t)k;
+	int32_t *dr = nullptr, *dvr = nullptr, *di = nullptr;
+	void *d_part = nullptr;
+	if (!run.alloc(dr, rect_bytes, "the rectangle of a query batch") || (by_pid && !run.alloc(dvr, rect_bytes, "the value rectangle of a query batch")) ||
+	    (want_hits && (!run.alloc(di, 6 * sizeof(int32_t) * cap, "the hits of a query batch") ||
+			   !run.alloc(d_part, run.largest([&](int32_t, int32_t nq) { return sa_hits_scratch_bytes(n, nq, k); }), "the partial hit lists"))))
 		return false;
-	struct Sync { /* the stream is drained before the buffers above are freed (declared last) */
-		hipStream_t s = nullptr;
-		hipEvent_t ev[4] = {}; /* start, rectangle swept, hits selected, list swept */
-		~Sync()
-		{
-			if (s) {
-				(void)hipStreamSynchronize(s);
-				(void)hipStreamDestroy(s);
-			}
-			for (hipEvent_t e : ev)
-				if (e)
-					(void)hipEventDestroy(e);
-		}
-	} sy;
-	SA_HIP_CHECK(hipStreamCreateWithFlags(&sy.s, hipStreamNonBlocking), return false);
-	for (hipEvent_t &e : sy.ev)
-		SA_HIP_CHECK(hipEventCreate(&e), return false);
-	double seconds = 0.0, t_hits = 0.0;
-	int32_t batches = 0;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
-		const size_t hits = (size_t)nq * (size_t)k, cap = (size_t)nqb * (size_t)k, elems = (size_t)nq * (size_t)n;
-		int32_t *const dr = static_cast<int32_t *>(d_rect.p), *const dv = by_pid ? static_cast<int32_t *>(d_vrect.p) : dr;
-		int32_t *const di = static_cast<int32_t *>(d_hits.p);
-		int32_t *const dval = di ? di + cap : nullptr, *const dsc = di ? di + 2 * cap : nullptr, *const dbeg = di ? di + 3 * cap : nullptr,
-			       *const dend = di ? di + 4 * cap : nullptr, *const dqy = di ? di + 5 * cap : nullptr;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[0], sy.s), return false);
+	int32_t *const dv = by_pid ? dvr : dr;
+	int32_t *const dval = di ? di + cap : nullptr, *const dsc = di ? di + 2 * cap : nullptr, *const dbeg = di ? di + 3 * cap : nullptr,
+		       *const dend = di ? di + 4 * cap : nullptr, *const dqy = di ? di + 5 * cap : nullptr;
+	if (!run.start())
+		return false;
+	const bool ok = run.each_batch([&](int64_t q0, int32_t nq) {
+		hipStream_t s = run.sy.s;
+		const size_t hits = (size_t)nq * (size_t)k, elems = (size_t)nq * (size_t)n;
 		const struct sa_fit_out sweep = { dr, nullptr, nullptr, nullptr, nullptr, by_pid ? dv : nullptr, by_pid ? denom : 0 };
-		if (!launch_fit(who, ctx, (int32_t)q0, nullptr, nullptr, (int64_t)elems, sweep, sy.s))
+		if (!run.stamp(SA_PH_FIT) || !launch_fit(who, ctx, (int32_t)q0, nullptr, nullptr, (int64_t)elems, sweep, s))
 			return false;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[1], sy.s), return false);
 		if (want_hits) {
-			if (sa_hits_launch(dv, (int32_t)n, nq, k, di, dval, d_part.p, sy.s) != 0)
+			if (!run.stamp(SA_PH_SELECT) || sa_hits_launch(dv, n, nq, k, di, dval, d_part, s) != 0)
 				return false;
-			hipLaunchKernelGGL(sa_k_fit_hit_queries, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, sy.s, (int32_t)q0, k, (int64_t)hits, dqy);
+			hipLaunchKernelGGL(sa_k_fit_hit_queries, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, s, (int32_t)q0, k, (int64_t)hits, dqy);
 			SA_HIP_CHECK(hipGetLastError(), return false);
-		}
-		SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return false);
-		if (want_hits) {
 			const struct sa_fit_out list = { dsc, dbeg, dend, nullptr, nullptr, nullptr, 0 };
-			if (!launch_fit(who, ctx, 0, dqy, di, (int64_t)hits, list, sy.s))
+			if (!run.stamp(SA_PH_FIT) || !launch_fit(who, ctx, 0, dqy, di, (int64_t)hits, list, s))
 				return false;
 		}
-		SA_HIP_CHECK(hipEventRecord(sy.ev[3], sy.s), return false);
+		if (!run.stamp(SA_PH_END))
+			return false;
 		if (want_hits) {
 			int32_t *const host[5] = { index, value, score, db_begin, db_end };
 			const int32_t *const dev[5] = { di, dval, dsc, dbeg, dend };
 			for (int t = 0; t < 5; t++)
 				if (host[t]) {
-					SA_HIP_CHECK(hipMemcpyAsync(host[t] + q0 * k, dev[t], sizeof(int32_t) * hits, hipMemcpyDeviceToHost, sy.s), return false);
+					SA_HIP_CHECK(hipMemcpyAsync(host[t] + q0 * k, dev[t], sizeof(int32_t) * hits, hipMemcpyDeviceToHost, s), return false);
 				}
 		}
 		if (rect) {
-			SA_HIP_CHECK(hipMemcpyAsync(rect + q0 * n, dr, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(rect + q0 * n, dr, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, s), return false);
 		}
 		if (vrect) {
-			SA_HIP_CHECK(hipMemcpyAsync(vrect + q0 * n, dv, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(vrect + q0 * n, dv, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, s), return false);
 		}
-		SA_HIP_CHECK(hipStreamSynchronize(sy.s), return false); /* (the next batch reuses the buffers) */
-		float ms[3] = {};
-		for (int t = 0; t < 3; t++)
-			SA_HIP_CHECK(hipEventElapsedTime(&ms[t], sy.ev[t], sy.ev[t + 1]), return false);
-		seconds += ((double)ms[0] + (double)ms[2]) * 1e-3;
-		t_hits += (double)ms[1] * 1e-3;
-		batches++;
-	}
-	g_last_fit_seconds.store(seconds);
-	sa_search_last_set(seconds, 0.0, t_hits, batches); /* (the sweep is the alignment: it is what delivers the scores) */
+		return true;
+	});
+	if (!ok)
+		return false;
+	const PhaseClock &t = run.sy.clock;
+	g_last_fit_seconds.store(t[SA_PH_FIT]);
+	sa_search_last_set(t[SA_PH_FIT], 0.0, t[SA_PH_SELECT], run.batches); /* (the sweep is the alignment: it is what delivers the scores) */
 	return true;
 }
 

@@ -21,8 +21,8 @@
 #include <cstdint>
 #include <mutex>
 
-#include "sa_ctx.h"
 #include "sa_search_core.h"
+#include "sa_search_run.h"
 
 namespace {
 
@@ -153,7 +153,9 @@ struct Last {
 	int32_t batches = 0;
 } g_last;
 
-bool hits_check(const char *who, int64_t n_db, int64_t nq, int32_t k)
+} // namespace
+
+bool sa_hits_check(const char *who, int64_t n_db, int64_t nq, int32_t k)
 {
 	if (n_db < 1 || nq < 1 || n_db > INT32_MAX || nq > INT32_MAX) {
 		sa_set_error("%s: %lld queries against %lld database sequences: both must be in [1, 2^31)", who, (long long)nq, (long long)n_db);
@@ -166,7 +168,7 @@ bool hits_check(const char *who, int64_t n_db, int64_t nq, int32_t k)
 	return true;
 }
 
-bool search_ctx_check(const char *who, const sa_ctx *ctx)
+bool sa_search_ctx_check(const char *who, const sa_ctx *ctx)
 {
 	if (!ctx) {
 		sa_set_error("%s: null context", who);
@@ -179,7 +181,7 @@ bool search_ctx_check(const char *who, const sa_ctx *ctx)
 	return true;
 }
 
-bool queries_check(const char *who, const sa_ctx *ctx, int32_t q0, int32_t nq)
+bool sa_search_queries_check(const char *who, const sa_ctx *ctx, int32_t q0, int32_t nq)
 {
 	if (q0 < 0 || nq < 1 || q0 > ctx->search_queries - nq) {
 		sa_set_error("%s: queries [%d,+%d) of %d", who, q0, nq, ctx->search_queries);
@@ -189,10 +191,10 @@ bool queries_check(const char *who, const sa_ctx *ctx, int32_t q0, int32_t nq)
 }
 
 /* the range into d_scratch, the rows into d_rect; `mid`, when not null, is recorded between the two */
-int search_range_impl(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void *d_scratch, hipStream_t s, hipEvent_t mid)
+int sa_search_range_launch(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void *d_scratch, hipStream_t s, hipEvent_t mid)
 {
 	const char *who = "sa_ctx_search_range";
-	if (!search_ctx_check(who, ctx) || !queries_check(who, ctx, q0, nq))
+	if (!sa_search_ctx_check(who, ctx) || !sa_search_queries_check(who, ctx, q0, nq))
 		return 1;
 	if (!d_rect || !d_scratch) {
 		sa_set_error("%s: null buffer", who);
@@ -213,7 +215,7 @@ int search_range_impl(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void
 	return 0;
 }
 
-int hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, hipStream_t s)
+int sa_hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, hipStream_t s)
 {
 	const int32_t S = sa_hits_segments(n_db, nq, k);
 	constexpr int WPB = SR_THREADS / 64;
@@ -229,20 +231,16 @@ int hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int3
 	return 0;
 }
 
-struct DevBuf {
-	void *p = nullptr;
-	~DevBuf() { (void)hipFree(p); }
-	bool alloc(size_t bytes, const char *what)
-	{
-		if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) {
-			(void)hipGetLastError();
-			p = nullptr;
-			sa_set_error("sa_hip_search: %s (%.2f GiB) does not fit the device's memory", what, (double)bytes / (double)(1 << 30));
-			return false;
-		}
-		return true;
-	}
-};
+void sa_search_last_set(double align, double gather, double hits, int32_t batches)
+{
+	std::lock_guard<std::mutex> g(g_last_mutex);
+	g_last.align = align;
+	g_last.gather = gather;
+	g_last.hits = hits;
+	g_last.batches = batches;
+}
+
+namespace {
 
 bool search_impl(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, int32_t k, int32_t *index, int32_t *score, int32_t *rect)
 {
@@ -260,126 +258,54 @@ bool search_impl(struct sa_input db, struct sa_input queries, const struct sa_sc
 		sa_set_error("%s: nothing asked for (index / score and rect are all null)", who);
 		return false;
 	}
-	if (db.num < 1 || queries.num < 1) {
-		sa_set_error("%s: empty store (%d database sequences, %d queries; min: 1 each)", who, db.num, queries.num);
+	if (!sa_run_stores_not_empty(who, db, queries) || !sa_run_stores_not_null(who, db, queries))
 		return false;
-	}
-	if (!db.seqs || !db.meta || !queries.seqs || !queries.meta) {
-		sa_set_error("%s: null sequence store", who);
+	if (want_hits && !sa_hits_check(who, db.num, queries.num, k))
 		return false;
-	}
-	if (want_hits && !hits_check(who, db.num, queries.num, k))
+	if (!sa_run_device_check())
 		return false;
-	if (sa_hip_device_count() <= 0) {
-		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
+	SearchRun run(who);
+	if (!run.adopt(sa_ctx_create_search(0, db, queries, sc), db, queries))
 		return false;
-	}
-	struct Ctx {
-		sa_ctx *c = nullptr;
-		~Ctx() { sa_ctx_destroy(c); }
-	} cx;
-	cx.c = sa_ctx_create_search(0, db, queries, sc);
-	if (!cx.c)
+	RectStage stage(run, nullptr, nullptr, false);
+	if (!stage.begin(sa_batch_tail_topk(want_hits, false, false, k)))
 		return false;
-	sa_ctx *ctx = cx.c;
-	const int64_t n = db.num, m = queries.num;
-	/* Batch: as many queries as the free memory holds of what grows with the batch (range row + rectangle row + hits + one
-	 * partial list; the partial lists of a batch are at most SA_HITS_WAVES + nq, the rest is inside the quarter left free).
-	 * The range row of the LAST query is the longest (N + M - 1 elements): sized by it, every batch fits. */
-	size_t free_b = 0, total_b = 0;
-	SA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b), return false);
-	const int32_t kk = want_hits ? k : 1;
-	const int64_t per_query = 4 * (n + m) + 4 * n + (want_hits ? 16 * (int64_t)k : 0);
-	int64_t budget = (int64_t)(free_b - free_b / 4);
-	if (ctx->env.search_batch_bytes > 0)
-		budget = std::min<int64_t>(budget, ctx->env.search_batch_bytes);
-	const int32_t nqb = (int32_t)std::max<int64_t>(1, std::min<int64_t>(m, budget / per_query));
-	size_t scratch_bytes = 0, hits_bytes = 0;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
-		scratch_bytes = std::max(scratch_bytes, sa_search_scratch_bytes(ctx, (int32_t)q0, nq));
-		if (want_hits)
-			hits_bytes = std::max(hits_bytes, sa_hits_scratch_bytes((int32_t)n, nq, kk));
-	}
-	DevBuf d_scratch, d_rect, d_hits, d_part;
-	if (!d_scratch.alloc(scratch_bytes, "the packed range of a query batch") ||
-	    !d_rect.alloc(sizeof(int32_t) * (size_t)nqb * (size_t)n, "the rectangle of a query batch") ||
-	    (want_hits && (!d_hits.alloc(2 * sizeof(int32_t) * (size_t)nqb * (size_t)k, "the hits of a query batch") ||
-			   !d_part.alloc(hits_bytes, "the partial hit lists"))))
+	const int32_t n = (int32_t)run.n;
+	const size_t cap = (size_t)run.nqb * (size_t)k;
+	int32_t *di = nullptr;
+	void *d_part = nullptr;
+	if (want_hits && (!run.alloc(di, 2 * sizeof(int32_t) * cap, "the hits of a query batch") ||
+			  !run.alloc(d_part, run.largest([&](int32_t, int32_t nq) { return sa_hits_scratch_bytes(n, nq, k); }), "the partial hit lists")))
 		return false;
-	struct Sync { /* the stream is drained before the buffers above are freed (declared last) */
-		hipStream_t s = nullptr;
-		hipEvent_t ev[4] = {};
-		~Sync()
-		{
-			if (s) {
-				(void)hipStreamSynchronize(s);
-				(void)hipStreamDestroy(s);
-			}
-			for (hipEvent_t e : ev)
-				if (e)
-					(void)hipEventDestroy(e);
-		}
-	} sy;
-	SA_HIP_CHECK(hipStreamCreateWithFlags(&sy.s, hipStreamNonBlocking), return false);
-	for (hipEvent_t &e : sy.ev)
-		SA_HIP_CHECK(hipEventCreate(&e), return false);
-	Last last;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
-		int32_t *const dr = static_cast<int32_t *>(d_rect.p);
-		int32_t *const di = static_cast<int32_t *>(d_hits.p), *const ds = di ? di + (size_t)nqb * (size_t)k : nullptr;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[0], sy.s), return false);
-		if (search_range_impl(ctx, (int32_t)q0, nq, dr, d_scratch.p, sy.s, sy.ev[1]) != 0)
+	int32_t *const ds = di ? di + cap : nullptr, *const dr = stage.raw();
+	if (!run.start())
+		return false;
+	const bool ok = run.each_batch([&](int64_t q0, int32_t nq) {
+		hipStream_t s = run.sy.s;
+		const size_t hits = sizeof(int32_t) * (size_t)nq * (size_t)k;
+		if (!stage.launch(q0, nq))
 			return false;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return false);
-		if (want_hits && hits_launch(dr, (int32_t)n, nq, k, di, ds, d_part.p, sy.s) != 0)
+		if (want_hits && (!run.stamp(SA_PH_SELECT) || sa_hits_launch(dr, n, nq, k, di, ds, d_part, s) != 0))
 			return false;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[3], sy.s), return false);
+		if (!run.stamp(SA_PH_END))
+			return false;
 		if (rect) {
-			SA_HIP_CHECK(hipMemcpyAsync(rect + q0 * n, dr, sizeof(int32_t) * (size_t)nq * (size_t)n, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(rect + q0 * n, dr, sizeof(int32_t) * (size_t)nq * (size_t)n, hipMemcpyDeviceToHost, s), return false);
 		}
 		if (want_hits) {
-			SA_HIP_CHECK(hipMemcpyAsync(index + q0 * k, di, sizeof(int32_t) * (size_t)nq * (size_t)k, hipMemcpyDeviceToHost, sy.s), return false);
-			SA_HIP_CHECK(hipMemcpyAsync(score + q0 * k, ds, sizeof(int32_t) * (size_t)nq * (size_t)k, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(index + q0 * k, di, hits, hipMemcpyDeviceToHost, s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(score + q0 * k, ds, hits, hipMemcpyDeviceToHost, s), return false);
 		}
-		SA_HIP_CHECK(hipStreamSynchronize(sy.s), return false); /* (the next batch reuses the buffers) */
-		float a = 0.f, g = 0.f, h = 0.f;
-		SA_HIP_CHECK(hipEventElapsedTime(&a, sy.ev[0], sy.ev[1]), return false);
-		SA_HIP_CHECK(hipEventElapsedTime(&g, sy.ev[1], sy.ev[2]), return false);
-		SA_HIP_CHECK(hipEventElapsedTime(&h, sy.ev[2], sy.ev[3]), return false);
-		last.align += (double)a * 1e-3;
-		last.gather += (double)g * 1e-3;
-		last.hits += (double)h * 1e-3;
-		last.batches++;
-	}
-	std::lock_guard<std::mutex> g(g_last_mutex);
-	g_last = last;
+		return true;
+	});
+	if (!ok)
+		return false;
+	const PhaseClock &t = run.sy.clock;
+	sa_search_last_set(t[SA_PH_ALIGN], t[SA_PH_GATHER], t[SA_PH_SELECT], run.batches);
 	return true;
 }
 
 } // namespace
-
-/* for sa_search_quantity.hip (sa_ctx.h) */
-bool sa_search_ctx_check(const char *who, const sa_ctx *ctx) { return search_ctx_check(who, ctx); }
-bool sa_search_queries_check(const char *who, const sa_ctx *ctx, int32_t q0, int32_t nq) { return queries_check(who, ctx, q0, nq); }
-bool sa_hits_check(const char *who, int64_t n_db, int64_t nq, int32_t k) { return hits_check(who, n_db, nq, k); }
-int sa_search_range_launch(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void *d_scratch, hipStream_t s, hipEvent_t mid)
-{
-	return search_range_impl(ctx, q0, nq, d_rect, d_scratch, s, mid);
-}
-void sa_search_last_set(double align, double gather, double hits, int32_t batches)
-{
-	std::lock_guard<std::mutex> g(g_last_mutex);
-	g_last.align = align;
-	g_last.gather = gather;
-	g_last.hits = hits;
-	g_last.batches = batches;
-}
-int sa_hits_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, int32_t *d_index, int32_t *d_score, void *d_scratch, hipStream_t s)
-{
-	return hits_launch(d_rect, n_db, nq, k, d_index, d_score, d_scratch, s);
-}
 
 extern "C" size_t sa_search_scratch_bytes(const sa_ctx *ctx, int32_t q0, int32_t nq)
 {
@@ -392,7 +318,7 @@ extern "C" size_t sa_search_scratch_bytes(const sa_ctx *ctx, int32_t q0, int32_t
 
 extern "C" int sa_ctx_search_range(sa_ctx *ctx, int32_t q0, int32_t nq, int32_t *d_rect, void *d_scratch, void *stream)
 {
-	return sa_guard("sa_ctx_search_range", 1, [&] { return search_range_impl(ctx, q0, nq, d_rect, d_scratch, (hipStream_t)stream, nullptr); });
+	return sa_guard("sa_ctx_search_range", 1, [&] { return sa_search_range_launch(ctx, q0, nq, d_rect, d_scratch, (hipStream_t)stream, nullptr); });
 }
 
 extern "C" size_t sa_hits_scratch_bytes(int32_t n_db, int32_t nq, int32_t k)
@@ -410,13 +336,13 @@ extern "C" int sa_ctx_hits(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, int32
 {
 	return sa_guard("sa_ctx_hits", 1, [&] {
 		const char *who = "sa_ctx_hits";
-		if (!search_ctx_check(who, ctx))
+		if (!sa_search_ctx_check(who, ctx))
 			return 1;
 		if (!d_rect || !d_index || !d_score) {
 			sa_set_error("%s: null argument", who);
 			return 1;
 		}
-		if (!hits_check(who, ctx->search_db, nq, k))
+		if (!sa_hits_check(who, ctx->search_db, nq, k))
 			return 1;
 		if (nq > ctx->search_queries) {
 			sa_set_error("%s: %d rows, the context has %d queries", who, nq, ctx->search_queries);
@@ -431,7 +357,7 @@ extern "C" int sa_ctx_hits(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, int32
 			return 1;
 		}
 		SA_HIP_CHECK(hipSetDevice(ctx->device), return 1);
-		return hits_launch(d_rect, ctx->search_db, nq, k, d_index, d_score, d_scratch, (hipStream_t)stream);
+		return sa_hits_launch(d_rect, ctx->search_db, nq, k, d_index, d_score, d_scratch, (hipStream_t)stream);
 	});
 }
 

@@ -26,9 +26,8 @@
 #include <cstring>
 #include <new>
 
-#include "sa_ctx.h"
 #include "sa_search_above_core.h"
-#include "sa_strands_core.h"
+#include "sa_search_run.h"
 
 struct sa_hitlist {
 	int32_t queries = 0;
@@ -204,39 +203,13 @@ bool above_check(const char *who, const sa_ctx *ctx, int32_t nq, const void *d_s
 	return true;
 }
 
-struct DevBuf {
-	void *p = nullptr;
-	size_t bytes = 0;
-	~DevBuf() { (void)hipFree(p); }
-	bool alloc(const char *who, size_t want, const char *what)
-	{
-		if (hipMalloc(&p, std::max<size_t>(want, 8)) != hipSuccess) {
-			(void)hipGetLastError();
-			p = nullptr;
-			sa_set_error("%s: %s (%.2f GiB) does not fit the device's memory", who, what, (double)want / (double)(1 << 30));
-			return false;
-		}
-		bytes = want;
-		return true;
-	}
-};
-
 /* host arrays that grow with the batches */
-bool grow(int32_t **p, size_t elems)
+template <class T> bool grow(T **p, size_t elems)
 {
-	void *q = realloc(*p, sizeof(int32_t) * std::max<size_t>(elems, 1));
+	void *q = realloc(*p, sizeof(T) * std::max<size_t>(elems, 1));
 	if (!q)
 		return false;
-	*p = static_cast<int32_t *>(q);
-	return true;
-}
-
-bool grow8(uint8_t **p, size_t elems)
-{
-	void *q = realloc(*p, std::max<size_t>(elems, 1));
-	if (!q)
-		return false;
-	*p = static_cast<uint8_t *>(q);
+	*p = static_cast<T *>(q);
 	return true;
 }
 
@@ -254,14 +227,8 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 		sa_set_error("%s: norm and pid_denom exclude each other", who);
 		return nullptr;
 	}
-	if (db.num < 1 || queries.num < 1) {
-		sa_set_error("%s: empty store (%d database sequences, %d queries; min: 1 each)", who, db.num, queries.num);
+	if (!sa_run_stores_not_empty(who, db, queries) || !sa_run_stores_not_null(who, db, queries))
 		return nullptr;
-	}
-	if (!db.seqs || !db.meta || !queries.seqs || !queries.meta) {
-		sa_set_error("%s: null sequence store", who);
-		return nullptr;
-	}
 	if (norm && !sa_norm_check(who, norm))
 		return nullptr;
 	if (pid_denom && !sa_identity_denom_check(who, *pid_denom))
@@ -271,82 +238,26 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 	const uint8_t *comp = comp_in ? comp_in : dna;
 	if (strands && !sa_strands_inputs_check(who, db, queries, sc, comp))
 		return nullptr;
-	if (sa_hip_device_count() <= 0) {
-		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
+	if (!sa_run_device_check())
 		return nullptr;
-	}
-	struct Ctx {
-		sa_ctx *c = nullptr;
-		~Ctx() { sa_ctx_destroy(c); }
-	} cx;
-	cx.c = strands ? sa_ctx_create_search_strands(0, db, queries, sc, comp) : sa_ctx_create_search(0, db, queries, sc);
-	if (!cx.c)
+	SearchRun run(who);
+	if (!run.adopt(strands ? sa_ctx_create_search_strands(0, db, queries, sc, comp) : sa_ctx_create_search(0, db, queries, sc), db, queries))
 		return nullptr;
-	sa_ctx *ctx = cx.c;
-	const int64_t n = db.num, m = queries.num, words = sa_strand_words(n);
-	const bool quantity = norm || pid_denom, aligned = !pid_denom;
-	/* Batch: as sa_hip_search_norm / _pid size it, with the scratch of this call in place of the hit lists.  Per query: the
-	 * range row (the longest, N + M - 1 elements; none under percent identity), a row of each rectangle (raw scores: the one),
-	 * and 8 bytes of scratch -- the entries of a batch are at most SA_HITS_WAVES + nq + 1, the rest is inside the quarter left
-	 * free.  The hits themselves are sized once they are counted. */
-	if (pid_denom && !sa_identity_payload_scratch(ctx))
+	/* The tail of a batch is its segment counts: the entries of a batch are at most SA_HITS_WAVES + nq + 1, the rest is inside the
+	 * quarter left free.  The hits themselves are sized once they are counted. */
+	RectStage stage(run, norm, pid_denom, strands);
+	if (!stage.begin(sa_batch_tail_above()))
 		return nullptr;
-	size_t free_b = 0, total_b = 0;
-	SA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b), return nullptr);
-	/* Both strands: the range row is N + 2 M - 1 elements at most (the two halves use the one buffer in turn), every rectangle has a
-	 * reverse twin, and a row of the strand bitmap is added. */
-	const int64_t per_query = strands ? (aligned ? 4 * (n + 2 * m) : 0) + (quantity ? 16 : 8) * n + 8 * words + 8
-					  : (aligned ? 4 * (n + m) : 0) + (quantity ? 8 : 4) * n + 8;
-	int64_t budget = (int64_t)(free_b - free_b / 4);
-	if (ctx->env.search_batch_bytes > 0)
-		budget = std::min<int64_t>(budget, ctx->env.search_batch_bytes);
-	const int32_t nqb = (int32_t)std::max<int64_t>(1, std::min<int64_t>(m, budget / per_query));
-	size_t range_bytes = 0, scratch_bytes = 0;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
-		if (aligned)
-			range_bytes = std::max(range_bytes, sa_search_scratch_bytes(ctx, (int32_t)(strands ? m + q0 : q0), nq));
-		scratch_bytes = std::max(scratch_bytes, sizeof(int64_t) * (size_t)sa_above_scratch_elems((int32_t)n, nq));
-	}
-	DevBuf d_range, d_rect, d_vrect, d_den, d_scratch, d_offsets, d_out, d_rrev, d_vrev, d_bits;
-	const size_t dens = (size_t)(strands ? n + 2 * m : n + m);
-	if ((aligned && !d_range.alloc(who, range_bytes, "the packed range of a query batch")) ||
-	    (norm && !d_den.alloc(who, sizeof(int32_t) * dens, "the denominators")) ||
-	    (strands && (!d_rrev.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the reverse rectangle of a query batch") ||
-			 (quantity && !d_vrev.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the reverse value rectangle of a query batch")) ||
-			 !d_bits.alloc(who, sizeof(uint64_t) * (size_t)nqb * (size_t)words, "the strand bitmap of a query batch"))) ||
-	    !d_rect.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the rectangle of a query batch") ||
-	    (quantity && !d_vrect.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the value rectangle of a query batch")) ||
-	    !d_scratch.alloc(who, scratch_bytes, "the segment counts") ||
-	    !d_offsets.alloc(who, sizeof(int64_t) * ((size_t)nqb + 1), "the offsets of a query batch"))
+	const int32_t n = (int32_t)run.n;
+	const int64_t m = run.m;
+	const bool quantity = stage.quantity;
+	int64_t *dsc = nullptr, *doff = nullptr;
+	if (!run.alloc(dsc, run.largest([&](int32_t, int32_t nq) { return sizeof(int64_t) * (size_t)sa_above_scratch_elems(n, nq); }), "the segment counts") ||
+	    !run.alloc(doff, sizeof(int64_t) * ((size_t)run.nqb + 1), "the offsets of a query batch"))
 		return nullptr;
-	struct Sync { /* the stream is drained before the buffers above are freed (declared after them) */
-		hipStream_t s = nullptr;
-		hipEvent_t ev[7] = {}; /* start, range aligned, rows moved, values done, counted + scanned, fill begins, filled */
-		/* both strands: values done (the fold begins; ev[3] is then "folded"), reverse range aligned, forward rows moved, strand take
-		 * begins, strands taken */
-		hipEvent_t evs[5] = {};
-		~Sync()
-		{
-			if (s) {
-				(void)hipStreamSynchronize(s);
-				(void)hipStreamDestroy(s);
-			}
-			for (hipEvent_t e : ev)
-				if (e)
-					(void)hipEventDestroy(e);
-			for (hipEvent_t e : evs)
-				if (e)
-					(void)hipEventDestroy(e);
-		}
-	} sy;
-	SA_HIP_CHECK(hipStreamCreateWithFlags(&sy.s, hipStreamNonBlocking), return nullptr);
-	for (hipEvent_t &e : sy.ev)
-		SA_HIP_CHECK(hipEventCreate(&e), return nullptr);
-	if (strands) {
-		for (hipEvent_t &e : sy.evs)
-			SA_HIP_CHECK(hipEventCreate(&e), return nullptr);
-	}
+	DevBuf &d_out = run.spare();
+	if (!run.start())
+		return nullptr;
 	struct Res {
 		sa_hitlist *h = nullptr;
 		~Res() { delete h; }
@@ -361,66 +272,20 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 	}
 	h->offsets[0] = 0;
 	const size_t arrays = quantity ? 3 : 2; /* device: index, value and, under a quantity, score */
-	std::vector<int32_t> h_den(norm && norm->denominators ? dens : 0);
-	std::vector<int64_t> h_off((size_t)nqb + 1);
-	double t_align = 0.0, t_gather = 0.0, t_quantity = 0.0, t_above = 0.0, t_strands = 0.0;
-	int32_t batches = 0;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
-		int32_t *const dr = static_cast<int32_t *>(d_rect.p), *const dv = quantity ? static_cast<int32_t *>(d_vrect.p) : dr;
-		int64_t *const dsc = static_cast<int64_t *>(d_scratch.p), *const doff = static_cast<int64_t *>(d_offsets.p);
-		int32_t *const drr = static_cast<int32_t *>(d_rrev.p), *const dvr = quantity ? static_cast<int32_t *>(d_vrev.p) : drr;
-		uint64_t *const dbits = static_cast<uint64_t *>(d_bits.p);
-		SA_HIP_CHECK(hipEventRecord(sy.ev[0], sy.s), return nullptr);
-		if (aligned) {
-			if (sa_search_range_launch(ctx, (int32_t)q0, nq, dr, d_range.p, sy.s, sy.ev[1]) != 0)
-				return nullptr;
-			if (strands) { /* the rows M + q0 .. through the same buffer of the range */
-				SA_HIP_CHECK(hipEventRecord(sy.evs[2], sy.s), return nullptr);
-				if (sa_search_range_launch(ctx, (int32_t)(m + q0), nq, drr, d_range.p, sy.s, sy.evs[1]) != 0)
-					return nullptr;
-			}
-			SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return nullptr);
-			if (norm) {
-				if (q0 == 0) { /* once per call */
-					SA_HIP_CHECK(sa_denominators_launch(ctx, norm->source, static_cast<int32_t *>(d_den.p), sy.s), return nullptr);
-				}
-				if (sa_normalize_rect_launch(dr, (int32_t)n, (int32_t)q0, nq, static_cast<const int32_t *>(d_den.p), norm->rule, dv, sy.s) != 0)
-					return nullptr;
-				if (strands && sa_normalize_rect_launch(drr, (int32_t)n, (int32_t)(m + q0), nq, static_cast<const int32_t *>(d_den.p), norm->rule,
-									 dvr, sy.s) != 0)
-					return nullptr;
-			}
-		} else {
-			const struct sa_identity_out out = { dr, nullptr, nullptr, dv, *pid_denom }, rev = { drr, nullptr, nullptr, dvr, *pid_denom };
-			SA_HIP_CHECK(hipEventRecord(sy.ev[1], sy.s), return nullptr);
-			if (strands) {
-				SA_HIP_CHECK(hipEventRecord(sy.evs[2], sy.s), return nullptr);
-				SA_HIP_CHECK(hipEventRecord(sy.evs[1], sy.s), return nullptr);
-			}
-			SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return nullptr);
-			if (!sa_identity_rect(who, ctx, (int32_t)q0, nq, &out, sy.s) || (strands && !sa_identity_rect(who, ctx, (int32_t)(m + q0), nq, &rev, sy.s)))
-				return nullptr;
-		}
-		if (strands) { /* in place: the folded values replace the forward values, the folded raw scores the forward raw scores */
-			SA_HIP_CHECK(hipEventRecord(sy.evs[0], sy.s), return nullptr);
-			if (sa_strand_fold_launch(dv, dvr, quantity ? dr : nullptr, quantity ? drr : nullptr, (int32_t)n, nq, dv, quantity ? dr : nullptr, dbits,
-						  sy.s) != 0)
-				return nullptr;
-		}
-		SA_HIP_CHECK(hipEventRecord(sy.ev[3], sy.s), return nullptr);
-		if (offsets_launch(dv, (int32_t)n, nq, min_value, doff, dsc, sy.s) != 0)
-			return nullptr;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[4], sy.s), return nullptr);
-		SA_HIP_CHECK(hipMemcpyAsync(h_off.data(), doff, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyDeviceToHost, sy.s), return nullptr);
-		if (q0 == 0 && !h_den.empty()) {
-			SA_HIP_CHECK(hipMemcpyAsync(h_den.data(), d_den.p, sizeof(int32_t) * h_den.size(), hipMemcpyDeviceToHost, sy.s), return nullptr);
-		}
-		SA_HIP_CHECK(hipStreamSynchronize(sy.s), return nullptr); /* E of the batch */
+	std::vector<int64_t> h_off((size_t)run.nqb + 1);
+	int32_t *const dr = stage.raw(), *const dv = stage.value();
+	const bool ok = run.each_batch([&](int64_t q0, int32_t nq) {
+		hipStream_t s = run.sy.s;
+		if (!stage.launch(q0, nq))
+			return false;
+		if (!run.stamp(SA_PH_SELECT) || offsets_launch(dv, n, nq, min_value, doff, dsc, s) != 0 || !run.stamp(SA_PH_END))
+			return false;
+		SA_HIP_CHECK(hipMemcpyAsync(h_off.data(), doff, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyDeviceToHost, s), return false);
+		if (!stage.copy_denominators(q0) || !run.sync()) /* E of the batch */
+			return false;
 		const int64_t e = h_off[(size_t)nq], at = h->count;
 		const size_t elems = (size_t)e, total = (size_t)(at + e);
 		const double gib = (double)elems * 4.0 * (double)arrays / (double)(1 << 30);
-		float ms_fill = 0.f, ms_take = 0.f;
 		if (elems) {
 			const size_t out_bytes = sizeof(int32_t) * arrays * elems + (strands ? elems : 0); /* (the strands: one byte per hit, last) */
 			if (d_out.bytes < out_bytes) { /* exact; the largest so far is kept */
@@ -432,78 +297,55 @@ sa_hitlist *above_impl(struct sa_input db, struct sa_input queries, const struct
 					d_out.p = nullptr;
 					sa_set_error("%s: the %lld hits of queries [%lld,+%d) (%.2f GiB) do not fit the device's memory", who, (long long)e,
 						     (long long)q0, nq, gib);
-					return nullptr;
+					return false;
 				}
 				d_out.bytes = out_bytes;
 			}
-			if (!grow(&h->index, total) || !grow(&h->value, total) || (quantity && !grow(&h->score, total)) || (strands && !grow8(&h->strand, total))) {
+			if (!grow(&h->index, total) || !grow(&h->value, total) || (quantity && !grow(&h->score, total)) || (strands && !grow(&h->strand, total))) {
 				sa_set_error("%s: the %lld hits of queries [%lld,+%d) (%.2f GiB, %lld hits before them) do not fit the host's memory", who,
 					     (long long)e, (long long)q0, nq, gib, (long long)at);
-				return nullptr;
+				return false;
 			}
 			int32_t *const di = static_cast<int32_t *>(d_out.p), *const dval = di + elems, *const dscore = quantity ? di + 2 * elems : nullptr;
-			SA_HIP_CHECK(hipEventRecord(sy.ev[5], sy.s), return nullptr);
-			if (fill_launch(dv, dr, (int32_t)n, nq, min_value, doff, dsc, di, dval, dscore, sy.s) != 0)
-				return nullptr;
-			SA_HIP_CHECK(hipEventRecord(sy.ev[6], sy.s), return nullptr);
+			if (!run.stamp(SA_PH_FILL) || fill_launch(dv, dr, n, nq, min_value, doff, dsc, di, dval, dscore, s) != 0)
+				return false;
 			if (strands) {
 				uint8_t *const dstrand = reinterpret_cast<uint8_t *>(di + arrays * elems);
-				SA_HIP_CHECK(hipEventRecord(sy.evs[3], sy.s), return nullptr);
-				if (sa_hits_above_strand_launch(dbits, (int32_t)n, nq, doff, di, dstrand, sy.s) != 0)
-					return nullptr;
-				SA_HIP_CHECK(hipEventRecord(sy.evs[4], sy.s), return nullptr);
-				SA_HIP_CHECK(hipMemcpyAsync(h->strand + at, dstrand, elems, hipMemcpyDeviceToHost, sy.s), return nullptr);
+				if (!run.stamp(SA_PH_STRAND_TAKE) || sa_hits_above_strand_launch(stage.bits(), n, nq, doff, di, dstrand, s) != 0 || !run.stamp(SA_PH_END))
+					return false;
+				SA_HIP_CHECK(hipMemcpyAsync(h->strand + at, dstrand, elems, hipMemcpyDeviceToHost, s), return false);
+			} else if (!run.stamp(SA_PH_END)) {
+				return false;
 			}
-			SA_HIP_CHECK(hipMemcpyAsync(h->index + at, di, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return nullptr);
-			SA_HIP_CHECK(hipMemcpyAsync(h->value + at, dval, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return nullptr);
+			SA_HIP_CHECK(hipMemcpyAsync(h->index + at, di, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(h->value + at, dval, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, s), return false);
 			if (quantity) {
-				SA_HIP_CHECK(hipMemcpyAsync(h->score + at, dscore, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return nullptr);
-			}
-			SA_HIP_CHECK(hipStreamSynchronize(sy.s), return nullptr); /* (the next batch reuses the buffers) */
-			SA_HIP_CHECK(hipEventElapsedTime(&ms_fill, sy.ev[5], sy.ev[6]), return nullptr);
-			if (strands) {
-				SA_HIP_CHECK(hipEventElapsedTime(&ms_take, sy.evs[3], sy.evs[4]), return nullptr);
+				SA_HIP_CHECK(hipMemcpyAsync(h->score + at, dscore, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, s), return false);
 			}
 		}
 		for (int32_t r = 0; r < nq; r++)
 			h->offsets[q0 + r + 1] = at + h_off[(size_t)r + 1];
 		h->count = at + e;
-		float ms[4] = {};
-		for (int t = 0; t < 4; t++)
-			SA_HIP_CHECK(hipEventElapsedTime(&ms[t], sy.ev[t], sy.ev[t + 1]), return nullptr);
-		if (strands) { /* the reverse half of alignment and gather; the fold is no part of the quantity */
-			float a = 0.f, g0 = 0.f, g1 = 0.f, q = 0.f, f = 0.f;
-			SA_HIP_CHECK(hipEventElapsedTime(&g0, sy.ev[1], sy.evs[2]), return nullptr);
-			SA_HIP_CHECK(hipEventElapsedTime(&a, sy.evs[2], sy.evs[1]), return nullptr);
-			SA_HIP_CHECK(hipEventElapsedTime(&g1, sy.evs[1], sy.ev[2]), return nullptr);
-			SA_HIP_CHECK(hipEventElapsedTime(&q, sy.ev[2], sy.evs[0]), return nullptr);
-			SA_HIP_CHECK(hipEventElapsedTime(&f, sy.evs[0], sy.ev[3]), return nullptr);
-			ms[0] += a;
-			ms[1] = g0 + g1;
-			ms[2] = q;
-			t_strands += ((double)f + (double)ms_take) * 1e-3;
-		}
-		t_align += (double)ms[0] * 1e-3;
-		t_gather += (double)ms[1] * 1e-3;
-		t_quantity += (double)ms[2] * 1e-3;
-		t_above += ((double)ms[3] + (double)ms_fill) * 1e-3;
-		batches++;
-	}
+		return true;
+	});
+	if (!ok)
+		return nullptr;
+	const PhaseClock &t = run.sy.clock;
+	const double t_above = t[SA_PH_SELECT] + t[SA_PH_FILL];
 	if (strands) {
-		if (!h->strand && !grow8(&h->strand, 0)) { /* (never a null pointer for a valid result) */
+		if (!h->strand && !grow(&h->strand, 0)) { /* (never a null pointer for a valid result) */
 			sa_set_error("%s: out of host memory", who);
 			return nullptr;
 		}
-		sa_strands_last_set(t_strands);
+		sa_strands_last_set(t[SA_PH_FOLD] + t[SA_PH_STRAND_TAKE]); /* (the fold is no part of the quantity) */
 	}
 	if (!quantity)
 		h->score = h->value; /* raw scores: value == score, one array */
-	if (!h_den.empty())
-		std::copy(h_den.begin(), h_den.end(), norm->denominators);
+	stage.publish_denominators();
 	g_last_above_seconds.store(t_above);
-	sa_search_quantity_last_set(quantity ? t_quantity : 0.0);
+	sa_search_quantity_last_set(t[SA_PH_QUANTITY]);
 	/* (under percent identity the sweep is the alignment as well: it is what delivers the scores) */
-	sa_search_last_set(aligned ? t_align : t_quantity, t_gather, t_above, batches);
+	sa_search_last_set(stage.aligned ? t[SA_PH_ALIGN] : t[SA_PH_QUANTITY], t[SA_PH_GATHER], t_above, run.batches);
 	res.h = nullptr;
 	return h;
 }

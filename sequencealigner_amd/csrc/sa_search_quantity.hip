@@ -21,8 +21,8 @@
 #include <cstdint>
 #include <vector>
 
-#include "sa_ctx.h"
 #include "sa_search_quantity_core.h"
+#include "sa_search_run.h"
 
 namespace {
 
@@ -77,8 +77,11 @@ __global__ __launch_bounds__(256) void sa_k_hits_take(const int32_t *__restrict_
 
 std::atomic<double> g_last_quantity_seconds{ 0.0 };
 
-int normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, int32_t nq, const int32_t *d_den, int32_t rule, int32_t *d_out,
-			  hipStream_t s)
+} // namespace
+
+/* the sweep of sa_ctx_normalize_rect, its arguments checked by the caller */
+int sa_normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, int32_t nq, const int32_t *d_den, int32_t rule, int32_t *d_out,
+			     hipStream_t s)
 {
 	const unsigned grid = (unsigned)std::min<int64_t>(sa_sq_pieces(n_db, nq), (int64_t)1 << 20);
 	switch (rule) {
@@ -96,7 +99,8 @@ int normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, int32
 	return 0;
 }
 
-int take_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, const int32_t *d_index, int32_t *d_out, hipStream_t s)
+/* the launch of sa_ctx_hits_take, its arguments checked by the caller */
+int sa_hits_take_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, const int32_t *d_index, int32_t *d_out, hipStream_t s)
 {
 	const int64_t hits = (int64_t)nq * k;
 	hipLaunchKernelGGL(sa_k_hits_take, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, s, d_rect, n_db, nq, k, d_index, d_out);
@@ -104,20 +108,9 @@ int take_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, cons
 	return 0;
 }
 
-struct DevBuf {
-	void *p = nullptr;
-	~DevBuf() { (void)hipFree(p); }
-	bool alloc(const char *who, size_t bytes, const char *what)
-	{
-		if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) {
-			(void)hipGetLastError();
-			p = nullptr;
-			sa_set_error("%s: %s (%.2f GiB) does not fit the device's memory", who, what, (double)bytes / (double)(1 << 30));
-			return false;
-		}
-		return true;
-	}
-};
+void sa_search_quantity_last_set(double seconds) { g_last_quantity_seconds.store(seconds); }
+
+namespace {
 
 /* what the two one-call forms ask for */
 struct Want {
@@ -141,139 +134,65 @@ bool quantity_impl(const char *who, struct sa_input db, struct sa_input queries,
 		sa_set_error("%s: nothing asked for (index, rect and vrect are all null)", who);
 		return false;
 	}
-	if (db.num < 1 || queries.num < 1) {
-		sa_set_error("%s: empty store (%d database sequences, %d queries; min: 1 each)", who, db.num, queries.num);
+	if (!sa_run_stores_not_empty(who, db, queries) || !sa_run_stores_not_null(who, db, queries))
 		return false;
-	}
-	if (!db.seqs || !db.meta || !queries.seqs || !queries.meta) {
-		sa_set_error("%s: null sequence store", who);
-		return false;
-	}
 	if (want_hits && !sa_hits_check(who, db.num, queries.num, k))
 		return false;
 	if (norm ? !sa_norm_check(who, norm) : !sa_identity_denom_check(who, denom))
 		return false;
-	if (sa_hip_device_count() <= 0) {
-		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
+	if (!sa_run_device_check())
 		return false;
-	}
-	struct Ctx {
-		sa_ctx *c = nullptr;
-		~Ctx() { sa_ctx_destroy(c); }
-	} cx;
-	cx.c = sa_ctx_create_search(0, db, queries, sc);
-	if (!cx.c)
+	SearchRun run(who);
+	if (!run.adopt(sa_ctx_create_search(0, db, queries, sc), db, queries))
 		return false;
-	sa_ctx *ctx = cx.c;
-	const int64_t n = db.num, m = queries.num;
-	/* Batch: as sa_hip_search sizes it, with the value rectangle counted.  Per query: the range row (the longest, N + M - 1
-	 * elements; none under percent identity, which runs no packed alignment), a row of each rectangle, and with hits index,
-	 * value, score and one partial list.  The identity sweep's payload scratch is the context's and is allocated before the free
-	 * memory is read, as sa_hip_identity does it. */
-	if (!norm && !sa_identity_payload_scratch(ctx))
+	RectStage stage(run, norm, norm ? nullptr : &denom, false);
+	if (!stage.begin(sa_batch_tail_topk(want_hits, true, false, k)))
 		return false;
-	size_t free_b = 0, total_b = 0;
-	SA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b), return false);
-	const int64_t per_query = (norm ? 4 * (n + m) : 0) + 8 * n + (want_hits ? 20 * (int64_t)k : 0);
-	int64_t budget = (int64_t)(free_b - free_b / 4);
-	if (ctx->env.search_batch_bytes > 0)
-		budget = std::min<int64_t>(budget, ctx->env.search_batch_bytes);
-	const int32_t nqb = (int32_t)std::max<int64_t>(1, std::min<int64_t>(m, budget / per_query));
-	size_t scratch_bytes = 0, part_bytes = 0;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
-		if (norm)
-			scratch_bytes = std::max(scratch_bytes, sa_search_scratch_bytes(ctx, (int32_t)q0, nq));
-		if (want_hits)
-			part_bytes = std::max(part_bytes, sa_hits_scratch_bytes((int32_t)n, nq, k));
-	}
-	DevBuf d_scratch, d_rect, d_vrect, d_den, d_hits, d_part;
-	if ((norm && (!d_scratch.alloc(who, scratch_bytes, "the packed range of a query batch") ||
-		      !d_den.alloc(who, sizeof(int32_t) * (size_t)(n + m), "the denominators"))) ||
-	    !d_rect.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the rectangle of a query batch") ||
-	    !d_vrect.alloc(who, sizeof(int32_t) * (size_t)nqb * (size_t)n, "the value rectangle of a query batch") ||
-	    (want_hits && (!d_hits.alloc(who, 3 * sizeof(int32_t) * (size_t)nqb * (size_t)k, "the hits of a query batch") ||
-			   !d_part.alloc(who, part_bytes, "the partial hit lists"))))
+	const int32_t n = (int32_t)run.n;
+	const size_t cap = (size_t)run.nqb * (size_t)k;
+	int32_t *di = nullptr;
+	void *d_part = nullptr;
+	if (want_hits && (!run.alloc(di, 3 * sizeof(int32_t) * cap, "the hits of a query batch") ||
+			  !run.alloc(d_part, run.largest([&](int32_t, int32_t nq) { return sa_hits_scratch_bytes(n, nq, k); }), "the partial hit lists")))
 		return false;
-	struct Sync { /* the stream is drained before the buffers above are freed (declared last) */
-		hipStream_t s = nullptr;
-		hipEvent_t ev[5] = {}; /* start, range aligned, rows moved (the quantity begins), values done, hits taken */
-		~Sync()
-		{
-			if (s) {
-				(void)hipStreamSynchronize(s);
-				(void)hipStreamDestroy(s);
-			}
-			for (hipEvent_t e : ev)
-				if (e)
-					(void)hipEventDestroy(e);
-		}
-	} sy;
-	SA_HIP_CHECK(hipStreamCreateWithFlags(&sy.s, hipStreamNonBlocking), return false);
-	for (hipEvent_t &e : sy.ev)
-		SA_HIP_CHECK(hipEventCreate(&e), return false);
-	std::vector<int32_t> h_den(norm && norm->denominators ? (size_t)(n + m) : 0);
-	double seconds = 0.0, t_align = 0.0, t_gather = 0.0, t_hits = 0.0;
-	int32_t batches = 0;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
-		const size_t hits = (size_t)nq * (size_t)k, cap = (size_t)nqb * (size_t)k, elems = (size_t)nq * (size_t)n;
-		int32_t *const dr = static_cast<int32_t *>(d_rect.p), *const dv = static_cast<int32_t *>(d_vrect.p);
-		int32_t *const di = static_cast<int32_t *>(d_hits.p), *const dval = di ? di + cap : nullptr, *const dsc = di ? di + 2 * cap : nullptr;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[0], sy.s), return false);
-		if (norm) {
-			if (sa_search_range_launch(ctx, (int32_t)q0, nq, dr, d_scratch.p, sy.s, sy.ev[1]) != 0)
-				return false;
-			SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return false);
-			if (q0 == 0) { /* once per call */
-				SA_HIP_CHECK(sa_denominators_launch(ctx, norm->source, static_cast<int32_t *>(d_den.p), sy.s), return false);
-			}
-			if (normalize_rect_launch(dr, (int32_t)n, (int32_t)q0, nq, static_cast<const int32_t *>(d_den.p), norm->rule, dv, sy.s) != 0)
-				return false;
-		} else {
-			const struct sa_identity_out out = { dr, nullptr, nullptr, dv, denom };
-			SA_HIP_CHECK(hipEventRecord(sy.ev[1], sy.s), return false);
-			SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return false);
-			if (!sa_identity_rect(who, ctx, (int32_t)q0, nq, &out, sy.s))
-				return false;
-		}
-		SA_HIP_CHECK(hipEventRecord(sy.ev[3], sy.s), return false);
-		if (want_hits && (sa_hits_launch(dv, (int32_t)n, nq, k, di, dval, d_part.p, sy.s) != 0 || take_launch(dr, (int32_t)n, nq, k, di, dsc, sy.s) != 0))
+	int32_t *const dval = di ? di + cap : nullptr, *const dsc = di ? di + 2 * cap : nullptr;
+	int32_t *const dr = stage.raw(), *const dv = stage.value();
+	if (!run.start())
+		return false;
+	const bool ok = run.each_batch([&](int64_t q0, int32_t nq) {
+		hipStream_t s = run.sy.s;
+		const size_t hits = sizeof(int32_t) * (size_t)nq * (size_t)k, elems = sizeof(int32_t) * (size_t)nq * (size_t)n;
+		if (!stage.launch(q0, nq))
 			return false;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[4], sy.s), return false);
+		if (want_hits && (!run.stamp(SA_PH_SELECT) || sa_hits_launch(dv, n, nq, k, di, dval, d_part, s) != 0 ||
+				  sa_hits_take_launch(dr, n, nq, k, di, dsc, s) != 0))
+			return false;
+		if (!run.stamp(SA_PH_END))
+			return false;
 		if (want_hits) {
-			SA_HIP_CHECK(hipMemcpyAsync(w.index + q0 * k, di, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(w.index + q0 * k, di, hits, hipMemcpyDeviceToHost, s), return false);
 			if (w.value) {
-				SA_HIP_CHECK(hipMemcpyAsync(w.value + q0 * k, dval, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, sy.s), return false);
+				SA_HIP_CHECK(hipMemcpyAsync(w.value + q0 * k, dval, hits, hipMemcpyDeviceToHost, s), return false);
 			}
 			if (w.score) {
-				SA_HIP_CHECK(hipMemcpyAsync(w.score + q0 * k, dsc, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, sy.s), return false);
+				SA_HIP_CHECK(hipMemcpyAsync(w.score + q0 * k, dsc, hits, hipMemcpyDeviceToHost, s), return false);
 			}
 		}
 		if (w.rect) {
-			SA_HIP_CHECK(hipMemcpyAsync(w.rect + q0 * n, dr, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(w.rect + q0 * n, dr, elems, hipMemcpyDeviceToHost, s), return false);
 		}
 		if (w.vrect) {
-			SA_HIP_CHECK(hipMemcpyAsync(w.vrect + q0 * n, dv, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(w.vrect + q0 * n, dv, elems, hipMemcpyDeviceToHost, s), return false);
 		}
-		if (q0 == 0 && !h_den.empty()) {
-			SA_HIP_CHECK(hipMemcpyAsync(h_den.data(), d_den.p, sizeof(int32_t) * h_den.size(), hipMemcpyDeviceToHost, sy.s), return false);
-		}
-		SA_HIP_CHECK(hipStreamSynchronize(sy.s), return false); /* (the next batch reuses the buffers) */
-		float ms[4] = {};
-		for (int t = 0; t < 4; t++)
-			SA_HIP_CHECK(hipEventElapsedTime(&ms[t], sy.ev[t], sy.ev[t + 1]), return false);
-		t_align += (double)ms[0] * 1e-3;
-		t_gather += (double)ms[1] * 1e-3;
-		seconds += (double)ms[2] * 1e-3;
-		t_hits += (double)ms[3] * 1e-3;
-		batches++;
-	}
-	if (!h_den.empty())
-		std::copy(h_den.begin(), h_den.end(), norm->denominators);
-	g_last_quantity_seconds.store(seconds);
+		return stage.copy_denominators(q0);
+	});
+	if (!ok)
+		return false;
+	stage.publish_denominators();
+	const PhaseClock &t = run.sy.clock;
+	g_last_quantity_seconds.store(t[SA_PH_QUANTITY]);
 	/* (under percent identity the sweep is the alignment as well: it is what delivers the scores) */
-	sa_search_last_set(norm ? t_align : seconds, t_gather, t_hits, batches);
+	sa_search_last_set(norm ? t[SA_PH_ALIGN] : t[SA_PH_QUANTITY], t[SA_PH_GATHER], t[SA_PH_SELECT], run.batches);
 	return true;
 }
 
@@ -308,19 +227,6 @@ bool search_plain(const char *who, struct sa_input db, struct sa_input queries, 
 
 } // namespace
 
-/* for sa_search_above.hip (sa_ctx.h) */
-int sa_normalize_rect_launch(const int32_t *d_rect, int32_t n_db, int32_t q0, int32_t nq, const int32_t *d_den, int32_t rule, int32_t *d_out,
-			     hipStream_t s)
-{
-	return normalize_rect_launch(d_rect, n_db, q0, nq, d_den, rule, d_out, s);
-}
-void sa_search_quantity_last_set(double seconds) { g_last_quantity_seconds.store(seconds); }
-/* for sa_strands.hip (sa_ctx.h) */
-int sa_hits_take_launch(const int32_t *d_rect, int32_t n_db, int32_t nq, int32_t k, const int32_t *d_index, int32_t *d_out, hipStream_t s)
-{
-	return take_launch(d_rect, n_db, nq, k, d_index, d_out, s);
-}
-
 extern "C" int sa_ctx_normalize_rect(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, int32_t q0, const int32_t *d_den, int32_t rule,
 				     int32_t *d_out, void *stream)
 {
@@ -339,7 +245,7 @@ extern "C" int sa_ctx_normalize_rect(sa_ctx *ctx, const int32_t *d_rect, int32_t
 			return 1;
 		}
 		SA_HIP_CHECK(hipSetDevice(ctx->device), return 1);
-		return normalize_rect_launch(d_rect, ctx->search_db, q0, nq, d_den, rule, d_out, (hipStream_t)stream);
+		return sa_normalize_rect_launch(d_rect, ctx->search_db, q0, nq, d_den, rule, d_out, (hipStream_t)stream);
 	});
 }
 
@@ -374,7 +280,7 @@ extern "C" int sa_ctx_hits_take(sa_ctx *ctx, const int32_t *d_rect, int32_t nq, 
 			return 1;
 		}
 		SA_HIP_CHECK(hipSetDevice(ctx->device), return 1);
-		return take_launch(d_rect, ctx->search_db, nq, k, d_index, d_out, (hipStream_t)stream);
+		return sa_hits_take_launch(d_rect, ctx->search_db, nq, k, d_index, d_out, (hipStream_t)stream);
 	});
 }
 

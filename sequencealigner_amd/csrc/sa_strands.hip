@@ -25,7 +25,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "sa_ctx.h"
+#include "sa_search_run.h"
 #include "sa_strands_core.h"
 
 namespace {
@@ -109,8 +109,11 @@ __global__ __launch_bounds__(ST_THREADS) void sa_k_hits_above_strand(const uint6
 
 std::atomic<double> g_last_strands_seconds{ 0.0 };
 
-int fold_launch(const int32_t *vf, const int32_t *vr, const int32_t *sf, const int32_t *sr, int32_t n_db, int32_t nq, int32_t *vbest, int32_t *sbest,
-		uint64_t *bits, hipStream_t s)
+} // namespace
+
+/* the launches of sa_ctx_strand_fold and sa_ctx_hits_above_strand, their arguments checked by the caller */
+int sa_strand_fold_launch(const int32_t *vf, const int32_t *vr, const int32_t *sf, const int32_t *sr, int32_t n_db, int32_t nq, int32_t *vbest,
+			  int32_t *sbest, uint64_t *bits, hipStream_t s)
 {
 	const int32_t S = sa_strand_segments(n_db, nq);
 	constexpr int WPB = ST_THREADS / 64;
@@ -124,21 +127,51 @@ int fold_launch(const int32_t *vf, const int32_t *vr, const int32_t *sf, const i
 	return 0;
 }
 
-int hits_strand_launch(const uint64_t *bits, int32_t n_db, int32_t nq, int32_t k, const int32_t *index, uint8_t *strand, hipStream_t s)
-{
-	const int64_t hits = (int64_t)nq * k;
-	hipLaunchKernelGGL(sa_k_hits_strand, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, s, bits, n_db, nq, k, index, strand);
-	SA_HIP_CHECK(hipGetLastError(), return 1);
-	return 0;
-}
-
-int above_strand_launch(const uint64_t *bits, int32_t n_db, int32_t nq, const int64_t *offsets, const int32_t *index, uint8_t *strand, hipStream_t s)
+int sa_hits_above_strand_launch(const uint64_t *bits, int32_t n_db, int32_t nq, const int64_t *offsets, const int32_t *index, uint8_t *strand,
+				hipStream_t s)
 {
 	const int32_t S = sa_strand_segments(n_db, nq);
 	constexpr int WPB = ST_THREADS / 64;
 	const int64_t waves = (int64_t)nq * S;
 	hipLaunchKernelGGL(sa_k_hits_above_strand, dim3((unsigned)((waves + WPB - 1) / WPB)), dim3(ST_THREADS), 0, s, bits, n_db, nq, S, offsets, index,
 			   strand);
+	SA_HIP_CHECK(hipGetLastError(), return 1);
+	return 0;
+}
+
+void sa_strands_last_set(double seconds) { g_last_strands_seconds.store(seconds); }
+
+/* what a strands context would refuse, said before a device is looked for */
+bool sa_strands_inputs_check(const char *who, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp)
+{
+	if ((int64_t)db.num + 2 * (int64_t)queries.num > INT32_MAX) {
+		sa_set_error("%s: %lld sequences exceed 32-bit sequence indices", who, (long long)db.num + 2 * (long long)queries.num);
+		return false;
+	}
+	int64_t bytes = 0;
+	for (int32_t k = 0; k < db.num; k++)
+		bytes += (int64_t)std::max<int32_t>(db.meta[k].len, 0) + 1;
+	for (int32_t k = 0; k < queries.num; k++) {
+		const sa_meta m = queries.meta[k];
+		if (m.len < 1 || m.off < 0) {
+			sa_set_error("Query sequence #%d has invalid offset/length (%d/%d)", k + 1, m.off, m.len);
+			return false;
+		}
+		bytes += 2 * ((int64_t)m.len + 1);
+	}
+	if (bytes > INT32_MAX) {
+		sa_set_error("%s: the concatenated sequence store exceeds 2 GiB", who);
+		return false;
+	}
+	return sa_strands_rc_checked(who, queries, comp, sc);
+}
+
+namespace {
+
+int hits_strand_launch(const uint64_t *bits, int32_t n_db, int32_t nq, int32_t k, const int32_t *index, uint8_t *strand, hipStream_t s)
+{
+	const int64_t hits = (int64_t)nq * k;
+	hipLaunchKernelGGL(sa_k_hits_strand, dim3((unsigned)((hits + 255) / 256)), dim3(256), 0, s, bits, n_db, nq, k, index, strand);
 	SA_HIP_CHECK(hipGetLastError(), return 1);
 	return 0;
 }
@@ -164,52 +197,12 @@ bool strands_check(const char *who, const sa_ctx *ctx, int32_t nq, const void *d
 	return true;
 }
 
-struct DevBuf {
-	void *p = nullptr;
-	~DevBuf() { (void)hipFree(p); }
-	bool alloc(const char *who, size_t bytes, const char *what)
-	{
-		if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) {
-			(void)hipGetLastError();
-			p = nullptr;
-			sa_set_error("%s: %s (%.2f GiB) does not fit the device's memory", who, what, (double)bytes / (double)(1 << 30));
-			return false;
-		}
-		return true;
-	}
-};
-
 struct Want {
 	int32_t *index, *value, *score;
 	uint8_t *strand;
 	int32_t *rect, *vrect;
 	uint8_t *srect;
 };
-
-/* what a strands context would refuse, said before a device is looked for */
-bool inputs_check(const char *who, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp)
-{
-	if ((int64_t)db.num + 2 * (int64_t)queries.num > INT32_MAX) {
-		sa_set_error("%s: %lld sequences exceed 32-bit sequence indices", who, (long long)db.num + 2 * (long long)queries.num);
-		return false;
-	}
-	int64_t bytes = 0;
-	for (int32_t k = 0; k < db.num; k++)
-		bytes += (int64_t)std::max<int32_t>(db.meta[k].len, 0) + 1;
-	for (int32_t k = 0; k < queries.num; k++) {
-		const sa_meta m = queries.meta[k];
-		if (m.len < 1 || m.off < 0) {
-			sa_set_error("Query sequence #%d has invalid offset/length (%d/%d)", k + 1, m.off, m.len);
-			return false;
-		}
-		bytes += 2 * ((int64_t)m.len + 1);
-	}
-	if (bytes > INT32_MAX) {
-		sa_set_error("%s: the concatenated sequence store exceeds 2 GiB", who);
-		return false;
-	}
-	return sa_strands_rc_checked(who, queries, comp, sc);
-}
 
 /* norm != NULL: normalised scores; pid_denom != NULL: percent identity; neither: raw scores */
 bool strands_impl(struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp_in, int32_t k, const Want &w,
@@ -233,14 +226,8 @@ bool strands_impl(struct sa_input db, struct sa_input queries, const struct sa_s
 		sa_set_error("%s: nothing asked for (index, rect, vrect and srect are all null)", who);
 		return false;
 	}
-	if (db.num < 1 || queries.num < 1) {
-		sa_set_error("%s: empty store (%d database sequences, %d queries; min: 1 each)", who, db.num, queries.num);
+	if (!sa_run_stores_not_empty(who, db, queries) || !sa_run_stores_not_null(who, db, queries))
 		return false;
-	}
-	if (!db.seqs || !db.meta || !queries.seqs || !queries.meta) {
-		sa_set_error("%s: null sequence store", who);
-		return false;
-	}
 	if (want_hits && !sa_hits_check(who, db.num, queries.num, k))
 		return false;
 	if (norm && !sa_norm_check(who, norm))
@@ -250,187 +237,82 @@ bool strands_impl(struct sa_input db, struct sa_input queries, const struct sa_s
 	uint8_t dna[SA_LUT_SIZE];
 	sa_strands_complement_table(dna);
 	const uint8_t *comp = comp_in ? comp_in : dna;
-	if (!inputs_check(who, db, queries, sc, comp))
+	if (!sa_strands_inputs_check(who, db, queries, sc, comp) || !sa_run_device_check())
 		return false;
-	if (sa_hip_device_count() <= 0) {
-		sa_set_error("No HIP devices available; libseqalign_hip has no CPU fallback");
+	SearchRun run(who);
+	if (!run.adopt(sa_ctx_create_search_strands(0, db, queries, sc, comp), db, queries))
 		return false;
-	}
-	struct Ctx {
-		sa_ctx *c = nullptr;
-		~Ctx() { sa_ctx_destroy(c); }
-	} cx;
-	cx.c = sa_ctx_create_search_strands(0, db, queries, sc, comp);
-	if (!cx.c)
+	RectStage stage(run, norm, pid_denom, true);
+	if (!stage.begin(sa_batch_tail_topk(want_hits, stage.quantity, true, k), true))
 		return false;
-	sa_ctx *ctx = cx.c;
-	const int64_t n = db.num, m = queries.num, words = sa_strand_words(n);
-	const bool quantity = norm || pid_denom, aligned = !pid_denom;
-	/* Batch: as sa_hip_search_norm / _pid size it, with both strands counted.  Per query: the range row (the longest, N + 2 M - 1
-	 * elements; the two halves of a batch use the one buffer in turn; none under percent identity), a forward and a reverse row of
-	 * each rectangle, a row of the bitmap, and with hits index, value, score, one partial list and the strands. */
-	if (pid_denom && !sa_identity_payload_scratch(ctx))
+	const int32_t n = (int32_t)run.n;
+	const int64_t words = sa_strand_words(n);
+	const bool quantity = stage.quantity;
+	const size_t cap = want_hits ? (size_t)run.nqb * (size_t)k : 0;
+	int32_t *di = nullptr;
+	uint8_t *dst = nullptr;
+	void *d_part = nullptr;
+	if (want_hits && (!run.alloc(di, 3 * sizeof(int32_t) * cap, "the hits of a query batch") || !run.alloc(dst, cap, "the strands of the hits") ||
+			  !run.alloc(d_part, run.largest([&](int32_t, int32_t nq) { return sa_hits_scratch_bytes(n, nq, k); }), "the partial hit lists")))
 		return false;
-	size_t free_b = 0, total_b = 0;
-	SA_HIP_CHECK(hipMemGetInfo(&free_b, &total_b), return false);
-	const int64_t per_query = (aligned ? 4 * (n + 2 * m) : 0) + (quantity ? 16 : 8) * n + 8 * words + (want_hits ? 21 * (int64_t)k : 0);
-	int64_t budget = (int64_t)(free_b - free_b / 4);
-	if (ctx->env.search_batch_bytes > 0)
-		budget = std::min<int64_t>(budget, ctx->env.search_batch_bytes);
-	const int32_t nqb = (int32_t)std::max<int64_t>(1, std::min<int64_t>(m, budget / per_query));
-	size_t range_bytes = 0, part_bytes = 0;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
-		if (aligned) /* (the reverse half begins M queries later: its range is the longer one) */
-			range_bytes = std::max(range_bytes, sa_search_scratch_bytes(ctx, (int32_t)(m + q0), nq));
-		if (want_hits)
-			part_bytes = std::max(part_bytes, sa_hits_scratch_bytes((int32_t)n, nq, k));
-	}
-	const size_t rect_bytes = sizeof(int32_t) * (size_t)nqb * (size_t)n, cap = want_hits ? (size_t)nqb * (size_t)k : 0;
-	DevBuf d_range, d_den, d_rf, d_rr, d_vf, d_vr, d_bits, d_hits, d_strand, d_part;
-	if ((aligned && !d_range.alloc(who, range_bytes, "the packed range of a query batch")) ||
-	    (norm && !d_den.alloc(who, sizeof(int32_t) * (size_t)(n + 2 * m), "the denominators")) ||
-	    !d_rf.alloc(who, rect_bytes, "the forward rectangle of a query batch") || !d_rr.alloc(who, rect_bytes, "the reverse rectangle of a query batch") ||
-	    (quantity && (!d_vf.alloc(who, rect_bytes, "the forward value rectangle of a query batch") ||
-			  !d_vr.alloc(who, rect_bytes, "the reverse value rectangle of a query batch"))) ||
-	    !d_bits.alloc(who, sizeof(uint64_t) * (size_t)nqb * (size_t)words, "the strand bitmap of a query batch") ||
-	    (want_hits && (!d_hits.alloc(who, 3 * sizeof(int32_t) * cap, "the hits of a query batch") || !d_strand.alloc(who, cap, "the strands of the hits") ||
-			   !d_part.alloc(who, part_bytes, "the partial hit lists"))))
+	int32_t *const dval = di ? di + cap : nullptr, *const dsc = di ? di + 2 * cap : nullptr;
+	int32_t *const rf = stage.raw(), *const vf = stage.value();
+	if (!run.start())
 		return false;
-	struct Sync { /* the stream is drained before the buffers above are freed (declared after them) */
-		hipStream_t s = nullptr;
-		/* start, forward range aligned, its rows moved, reverse range aligned, its rows moved, values done, folded, hits taken, strands taken */
-		hipEvent_t ev[9] = {};
-		~Sync()
-		{
-			if (s) {
-				(void)hipStreamSynchronize(s);
-				(void)hipStreamDestroy(s);
-			}
-			for (hipEvent_t e : ev)
-				if (e)
-					(void)hipEventDestroy(e);
-		}
-	} sy;
-	SA_HIP_CHECK(hipStreamCreateWithFlags(&sy.s, hipStreamNonBlocking), return false);
-	for (hipEvent_t &e : sy.ev)
-		SA_HIP_CHECK(hipEventCreate(&e), return false);
-	std::vector<int32_t> h_den(norm && norm->denominators ? (size_t)(n + 2 * m) : 0);
-	std::vector<uint64_t> h_bits(w.srect ? (size_t)nqb * (size_t)words : 0);
-	double t_align = 0.0, t_gather = 0.0, t_quantity = 0.0, t_hits = 0.0, t_strands = 0.0;
-	int32_t batches = 0;
-	for (int64_t q0 = 0; q0 < m; q0 += nqb) {
-		const int32_t nq = (int32_t)std::min<int64_t>(nqb, m - q0);
+	std::vector<uint64_t> h_bits(w.srect ? (size_t)run.nqb * (size_t)words : 0);
+	const bool ok = run.each_batch([&](int64_t q0, int32_t nq) {
+		hipStream_t s = run.sy.s;
 		const size_t hits = want_hits ? (size_t)nq * (size_t)k : 0, elems = (size_t)nq * (size_t)n;
-		int32_t *const rf = static_cast<int32_t *>(d_rf.p), *const rr = static_cast<int32_t *>(d_rr.p);
-		int32_t *const vf = quantity ? static_cast<int32_t *>(d_vf.p) : rf, *const vr = quantity ? static_cast<int32_t *>(d_vr.p) : rr;
-		uint64_t *const db_bits = static_cast<uint64_t *>(d_bits.p);
-		int32_t *const di = static_cast<int32_t *>(d_hits.p), *const dval = di ? di + cap : nullptr, *const dsc = di ? di + 2 * cap : nullptr;
-		uint8_t *const dst = static_cast<uint8_t *>(d_strand.p);
-		const int32_t *const den = static_cast<const int32_t *>(d_den.p);
-		SA_HIP_CHECK(hipEventRecord(sy.ev[0], sy.s), return false);
-		if (aligned) {
-			if (sa_search_range_launch(ctx, (int32_t)q0, nq, rf, d_range.p, sy.s, sy.ev[1]) != 0)
-				return false;
-			SA_HIP_CHECK(hipEventRecord(sy.ev[2], sy.s), return false);
-			if (sa_search_range_launch(ctx, (int32_t)(m + q0), nq, rr, d_range.p, sy.s, sy.ev[3]) != 0)
-				return false;
-			SA_HIP_CHECK(hipEventRecord(sy.ev[4], sy.s), return false);
-			if (norm) {
-				if (q0 == 0) { /* once per call */
-					SA_HIP_CHECK(sa_denominators_launch(ctx, norm->source, static_cast<int32_t *>(d_den.p), sy.s), return false);
-				}
-				if (sa_normalize_rect_launch(rf, (int32_t)n, (int32_t)q0, nq, den, norm->rule, vf, sy.s) != 0 ||
-				    sa_normalize_rect_launch(rr, (int32_t)n, (int32_t)(m + q0), nq, den, norm->rule, vr, sy.s) != 0)
-					return false;
-			}
-		} else {
-			const struct sa_identity_out fwd = { rf, nullptr, nullptr, vf, *pid_denom }, rev = { rr, nullptr, nullptr, vr, *pid_denom };
-			for (int t = 1; t <= 4; t++)
-				SA_HIP_CHECK(hipEventRecord(sy.ev[t], sy.s), return false);
-			if (!sa_identity_rect(who, ctx, (int32_t)q0, nq, &fwd, sy.s) || !sa_identity_rect(who, ctx, (int32_t)(m + q0), nq, &rev, sy.s))
-				return false;
-		}
-		SA_HIP_CHECK(hipEventRecord(sy.ev[5], sy.s), return false);
-		/* in place: the folded values replace the forward values, the folded raw scores the forward raw scores */
-		if (fold_launch(vf, vr, quantity ? rf : nullptr, quantity ? rr : nullptr, (int32_t)n, nq, vf, quantity ? rf : nullptr, db_bits, sy.s) != 0)
+		if (!stage.launch(q0, nq))
 			return false;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[6], sy.s), return false);
-		if (want_hits && (sa_hits_launch(vf, (int32_t)n, nq, k, di, dval, d_part.p, sy.s) != 0 ||
-				  (quantity && sa_hits_take_launch(rf, (int32_t)n, nq, k, di, dsc, sy.s) != 0)))
+		if (want_hits && (!run.stamp(SA_PH_SELECT) || sa_hits_launch(vf, n, nq, k, di, dval, d_part, s) != 0 ||
+				  (quantity && sa_hits_take_launch(rf, n, nq, k, di, dsc, s) != 0)))
 			return false;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[7], sy.s), return false);
-		if (want_hits && w.strand && hits_strand_launch(db_bits, (int32_t)n, nq, k, di, dst, sy.s) != 0)
+		if (want_hits && w.strand && (!run.stamp(SA_PH_STRAND_TAKE) || hits_strand_launch(stage.bits(), n, nq, k, di, dst, s) != 0))
 			return false;
-		SA_HIP_CHECK(hipEventRecord(sy.ev[8], sy.s), return false);
+		if (!run.stamp(SA_PH_END))
+			return false;
 		if (want_hits) {
-			SA_HIP_CHECK(hipMemcpyAsync(w.index + q0 * k, di, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(w.index + q0 * k, di, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, s), return false);
 			if (w.value) {
-				SA_HIP_CHECK(hipMemcpyAsync(w.value + q0 * k, dval, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, sy.s), return false);
+				SA_HIP_CHECK(hipMemcpyAsync(w.value + q0 * k, dval, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, s), return false);
 			}
 			if (w.score) { /* (raw scores: the value is the score) */
-				SA_HIP_CHECK(hipMemcpyAsync(w.score + q0 * k, quantity ? dsc : dval, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, sy.s),
-					     return false);
+				SA_HIP_CHECK(hipMemcpyAsync(w.score + q0 * k, quantity ? dsc : dval, sizeof(int32_t) * hits, hipMemcpyDeviceToHost, s), return false);
 			}
 			if (w.strand) {
-				SA_HIP_CHECK(hipMemcpyAsync(w.strand + q0 * k, dst, hits, hipMemcpyDeviceToHost, sy.s), return false);
+				SA_HIP_CHECK(hipMemcpyAsync(w.strand + q0 * k, dst, hits, hipMemcpyDeviceToHost, s), return false);
 			}
 		}
 		if (w.rect) {
-			SA_HIP_CHECK(hipMemcpyAsync(w.rect + q0 * n, rf, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(w.rect + q0 * n, rf, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, s), return false);
 		}
 		if (w.vrect) {
-			SA_HIP_CHECK(hipMemcpyAsync(w.vrect + q0 * n, vf, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, sy.s), return false);
+			SA_HIP_CHECK(hipMemcpyAsync(w.vrect + q0 * n, vf, sizeof(int32_t) * elems, hipMemcpyDeviceToHost, s), return false);
 		}
 		if (w.srect) {
-			SA_HIP_CHECK(hipMemcpyAsync(h_bits.data(), db_bits, sizeof(uint64_t) * (size_t)nq * (size_t)words, hipMemcpyDeviceToHost, sy.s),
-				     return false);
+			SA_HIP_CHECK(hipMemcpyAsync(h_bits.data(), stage.bits(), sizeof(uint64_t) * (size_t)nq * (size_t)words, hipMemcpyDeviceToHost, s), return false);
 		}
-		if (q0 == 0 && !h_den.empty()) {
-			SA_HIP_CHECK(hipMemcpyAsync(h_den.data(), d_den.p, sizeof(int32_t) * h_den.size(), hipMemcpyDeviceToHost, sy.s), return false);
-		}
-		SA_HIP_CHECK(hipStreamSynchronize(sy.s), return false); /* (the next batch reuses the buffers) */
+		if (!stage.copy_denominators(q0) || !run.sync())
+			return false;
 		if (w.srect) /* the bitmap crossed the bus, one byte per cell is what the caller reads */
 			for (int64_t r = 0; r < nq; r++)
 				for (int64_t d = 0; d < n; d++)
-					w.srect[(q0 + r) * n + d] = sa_strand_bit(h_bits.data() + r * words, (int32_t)n, (int32_t)d);
-		float ms[8] = {};
-		for (int t = 0; t < 8; t++)
-			SA_HIP_CHECK(hipEventElapsedTime(&ms[t], sy.ev[t], sy.ev[t + 1]), return false);
-		t_align += ((double)ms[0] + (double)ms[2]) * 1e-3;
-		t_gather += ((double)ms[1] + (double)ms[3]) * 1e-3;
-		t_quantity += (double)ms[4] * 1e-3;
-		t_strands += ((double)ms[5] + (double)ms[7]) * 1e-3;
-		t_hits += (double)ms[6] * 1e-3;
-		batches++;
-	}
-	if (!h_den.empty())
-		std::copy(h_den.begin(), h_den.end(), norm->denominators);
-	g_last_strands_seconds.store(t_strands);
-	sa_search_quantity_last_set(quantity ? t_quantity : 0.0);
+					w.srect[(q0 + r) * n + d] = sa_strand_bit(h_bits.data() + r * words, n, (int32_t)d);
+		return true;
+	});
+	if (!ok)
+		return false;
+	stage.publish_denominators();
+	const PhaseClock &t = run.sy.clock;
+	g_last_strands_seconds.store(t[SA_PH_FOLD] + t[SA_PH_STRAND_TAKE]);
+	sa_search_quantity_last_set(t[SA_PH_QUANTITY]);
 	/* (under percent identity the sweeps are the alignment as well: they are what delivers the scores) */
-	sa_search_last_set(aligned ? t_align : t_quantity, t_gather, t_hits, batches);
+	sa_search_last_set(stage.aligned ? t[SA_PH_ALIGN] : t[SA_PH_QUANTITY], t[SA_PH_GATHER], t[SA_PH_SELECT], run.batches);
 	return true;
 }
 
 } // namespace
-
-/* for sa_search_above.hip (sa_ctx.h) */
-bool sa_strands_inputs_check(const char *who, struct sa_input db, struct sa_input queries, const struct sa_scoring *sc, const uint8_t *comp)
-{
-	return inputs_check(who, db, queries, sc, comp);
-}
-int sa_strand_fold_launch(const int32_t *vf, const int32_t *vr, const int32_t *sf, const int32_t *sr, int32_t n_db, int32_t nq, int32_t *vbest,
-			  int32_t *sbest, uint64_t *bits, hipStream_t s)
-{
-	return fold_launch(vf, vr, sf, sr, n_db, nq, vbest, sbest, bits, s);
-}
-int sa_hits_above_strand_launch(const uint64_t *bits, int32_t n_db, int32_t nq, const int64_t *offsets, const int32_t *index, uint8_t *strand,
-				hipStream_t s)
-{
-	return above_strand_launch(bits, n_db, nq, offsets, index, strand, s);
-}
-void sa_strands_last_set(double seconds) { g_last_strands_seconds.store(seconds); }
 
 /* for sa_context.hip and the one-call forms (sa_ctx.h) */
 bool sa_strands_rc_checked(const char *who, struct sa_input in, const uint8_t *comp, const struct sa_scoring *sc)
@@ -508,7 +390,7 @@ extern "C" int sa_ctx_strand_fold(sa_ctx *ctx, const int32_t *d_vfwd, const int3
 			return 1;
 		}
 		SA_HIP_CHECK(hipSetDevice(ctx->device), return 1);
-		return fold_launch(d_vfwd, d_vrev, d_sfwd, d_srev, ctx->search_db, nq, d_vbest, d_sbest, d_bits, (hipStream_t)stream);
+		return sa_strand_fold_launch(d_vfwd, d_vrev, d_sfwd, d_srev, ctx->search_db, nq, d_vbest, d_sbest, d_bits, (hipStream_t)stream);
 	});
 }
 
@@ -549,7 +431,7 @@ extern "C" int sa_ctx_hits_above_strand(sa_ctx *ctx, const uint64_t *d_bits, int
 			return 1;
 		}
 		SA_HIP_CHECK(hipSetDevice(ctx->device), return 1);
-		return above_strand_launch(d_bits, ctx->search_db, nq, d_offsets, d_index, d_strand, (hipStream_t)stream);
+		return sa_hits_above_strand_launch(d_bits, ctx->search_db, nq, d_offsets, d_index, d_strand, (hipStream_t)stream);
 	});
 }
 
